@@ -18,6 +18,16 @@ FLOWSE_BENCH_SHARE_GPU=1 maps every rank to device 0 (then FLOWSE_BENCH_BACKEND=
 
 Metric: enhanced spectrogram-frames/sec at N=5 solver steps (frame = one STFT column of 256 bins).
 
+A plain run sets up, warms up, times the K steps and prints the line; nothing else runs on the GPU.  `--full` adds
+everything else the line can carry, each in runs of its own after the timed region: the roofline of the dominant
+kernel (the K steps again under the library's per-launch HIP events), the other precision modes, the single-utterance
+shape, one GPU's share of config[3], rank 0's gather tail, config[4], the CPU baseline with the oracle parity echo,
+and with N > 1 GPUs the strong-scaling config[3] pass.
+
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float32; see
+dump_outputs), so that two builds can be compared output for output: inputs and weights are synthetic and
+deterministic, the same for the same arguments in every run.
+
 `--workload vbdmd` runs BASELINE config[3] instead: 824 synthetic utterances of ragged length (T = 64 k, k in 2..10,
 the set SURVEY 8(d) prescribes when the VoiceBank-DEMAND test set is absent) through flowmse_amd.parallel.
 enhance_sharded -- equal-length batches dealt to the ranks by modelled time, N=5 Euler sampler, ONE final gather to rank 0 --
@@ -49,6 +59,39 @@ FULL_CFG = dict(nf=128, ch_mult=(1, 1, 2, 2, 2, 2, 2), num_res_blocks=2, attn_re
 def synth_state_dict(model):
     from flowmse_amd.util import synth
     return {n: torch.from_numpy(synth.synth_param(n, tuple(p.shape))) for n, p in model.named_parameters()}
+
+
+DUMP_MAX_BYTES = 60 * 2 ** 20          # --dump-outputs: all arrays together (npy headers included) stay under 64 MB
+
+
+def dump_outputs(dirname, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Write {name: tensor} as dirname/<name>.npy in float32 (complex tensors as their real view, trailing axis of 2).
+    When the arrays together hold more than max_bytes, each one is replaced by a fixed sample of its flattened elements:
+    the same share of every array, at indices drawn once from a generator with a fixed seed (sorted), so two runs of the
+    same command sample the same elements.  Returns {name: {"shape", "sampled_elements"}} for the result line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    flat = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        flat[name] = t.to("cpu", torch.float32).contiguous()
+    total = sum(t.numel() for t in flat.values())
+    keep = min(1.0, (max_bytes - 256 * len(flat)) / (4.0 * max(total, 1)))
+    info = {}
+    for name, t in flat.items():
+        a = t.numpy().reshape(-1)
+        sampled = None
+        if keep < 1.0:
+            k = max(1, int(a.size * keep))
+            idx = np.sort(np.random.default_rng(20240).choice(a.size, size=k, replace=False))
+            a, sampled = a[idx], k
+        else:
+            a = a.reshape(t.shape)
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        info[name] = {"shape": list(t.shape), "sampled_elements": sampled}
+    return info
 
 
 def cpu_baseline(sd, nsolver, frames, reps, budget_s=60.0, oracle_utt=None):
@@ -142,11 +185,12 @@ def vbdmd_plan(n, world, max_batch):
     return true_len, padded, plan, plan_summary(plan, padded, max_batch)
 
 
-def run_vbdmd(args, model, dev, world, rank, backend, share, share_of=None):
+def run_vbdmd(args, model, dev, world, rank, backend, share, share_of=None, dump_dir=None):
     """config[3]: the whole ragged set through enhance_sharded, timed end to end (batches -> deal -> sampler -> gather).
 
     share_of = (r, W) on ONE GPU: run exactly rank r's share of the W-rank partition of the whole set (what one GPU of
-    a W-GPU job executes), not a smaller set."""
+    a W-GPU job executes), not a smaller set.  dump_dir: rank 0 writes the last pass's enhanced spectrograms there
+    (dump_outputs), the utterances in index order along the frame axis."""
     from flowmse_amd.parallel import enhance_sharded
     from flowmse_amd.sampling import get_white_box_solver
     from flowmse_amd.util import synth
@@ -211,6 +255,8 @@ def run_vbdmd(args, model, dev, world, rank, backend, share, share_of=None):
     checked = not os.environ.get("FLOWSE_BENCH_NO_CHECK")
     if checked:
         assert all(bool(torch.isfinite(torch.view_as_real(out[i])).all()) for i in got), "non-finite output"
+    dumped = (dump_outputs(dump_dir, {"enhanced_spectrograms": torch.cat([out[i] for i in got], dim=1)})
+              if dump_dir else None)
     frames = sum(padded[i] for i in got)
     n_run = len(got)
     nfe_per_step = (NS - 1) * {"euler": 1, "heun": 2, "rk4": 4}[args.solver] + 1
@@ -242,6 +288,7 @@ def run_vbdmd(args, model, dev, world, rank, backend, share, share_of=None):
                    "launch_mode": launch_mode(graph_launches), "hip_graph_launches_rank0": graph_launches,
                    "finite_output_checked": checked,
                    "workspace_GB": round(ws_bytes / 2 ** 30, 2)},
+        "dumped_outputs": dumped,
         "frames_value_counts": "padded frames (what the kernels process); true (unpadded) frames/s = value * "
                                f"{sum(true_len[i] for i in got) / frames:.4f}",
         "plan": {k: psum[k] for k in ("frame_imbalance_max_over_mean", "model_time_imbalance_max_over_mean", "batch_fill",
@@ -457,21 +504,29 @@ def main():
     ap.add_argument("--solver", default="euler", choices=["euler", "heun", "rk4"],
                     help="ODE solver plugin (BASELINE config 5: --solver rk4 --nsolver 25 --batch 32 --frames 1024 "
                          "--precision fp16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the roofline, the other precision modes, shapes and "
+                         "workloads, the CPU baseline with the oracle parity echo and (N > 1 GPUs) the strong-scaling "
+                         "pass; a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the timed path's outputs of its last step to DIR/<name>.npy (float32, <= 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-reps", type=int, default=2)
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "bf16", "fp16"],
                     help="matrix-core operand mode of the large 3x3 convs (default: exact fp32)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the bf16x3 / bf16 operand-mode legs")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the other precision modes, shapes and workloads")
     ap.add_argument("--profile-all", action="store_true", help="per-op timing table to stderr (extra untimed pass)")
     ap.add_argument("--workload", default="config1", choices=["config1", "vbdmd"],
                     help="config1: BASELINE config[1] (one [batch,1,256,frames] batch per GPU, weak scaling; the default); "
                          "vbdmd: BASELINE config[3] (ragged utterance set sharded over the GPUs, strong scaling)")
     ap.add_argument("--utts", type=int, default=VBDMD_UTTS, help="--workload vbdmd: number of utterances")
     ap.add_argument("--no-strong", action="store_true",
-                    help="world > 1: skip the strong-scaling config[3] pass that is otherwise run after the timed region")
+                    help="--full, world > 1: skip the strong-scaling config[3] pass run after the timed region")
     ap.add_argument("--plan", action="store_true",
                     help="--workload vbdmd: print the partition over --gpus ranks (host only, no GPU needed) and exit")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.plan:
         assert args.workload == "vbdmd", "--plan describes the --workload vbdmd partition"
@@ -529,7 +584,7 @@ def main():
     model.dnn.set_precision(args.precision)
 
     if args.workload == "vbdmd":
-        out = run_vbdmd(args, model, dev, world, rank, backend, share)
+        out = run_vbdmd(args, model, dev, world, rank, backend, share, dump_dir=args.dump_outputs)
         if rank == 0:
             print(json.dumps(out), flush=True)
         if world > 1:
@@ -559,6 +614,7 @@ def main():
         t0 = time.perf_counter()
         for _ in range(args.steps):
             xx = step()
+        gathered = None
         if world > 1:                              # the path's only exchange: final gather of enhanced specs
             payload = torch.view_as_real(xx).contiguous()
             if backend != "nccl":
@@ -566,7 +622,7 @@ def main():
             gathered = [torch.empty_like(payload) for _ in range(world)] if rank == 0 else None
             dist.gather(payload, gathered, dst=0)
         barrier()
-        return xx, time.perf_counter() - t0
+        return xx, gathered, time.perf_counter() - t0
 
     for _ in range(max(args.warmup, 2 if graphs_on else 0)):   # a shape's hipGraph is captured on its second pass
         x = step()
@@ -574,14 +630,20 @@ def main():
     # (1) THE timed region: the product path as shipped -- plain (eager) launches of the shape's launch list by
     # default, one hipGraph replay per network evaluation only under FLOWSE_GRAPH=1; `launch_mode` in the line says
     # which one ran, from the library's own replay counter
-    x, elapsed = timed_region()
+    x, gathered, elapsed = timed_region()
     graph_launches = model.dnn.graph_launches() - g0          # counted by the library, not inferred from the env
-    # (2) the same K steps again with the library's per-launch HIP events (recorded on the launch stream) around the
-    # dominant kernel (plain launches of the identical launch list).  Its wall time is reported next to the timed
-    # region's (roofline.profiled_region_*).
-    model.dnn.profile_begin(0)
-    _, elapsed_prof = timed_region()
-    prof = model.dnn.profile_end()
+    dumped = None
+    if args.dump_outputs and rank == 0:            # what a caller receives: rank 0 holds every rank's batch after the gather
+        enhanced = x if world == 1 else torch.view_as_complex(torch.cat([g.to(dev) for g in gathered]))
+        dumped = dump_outputs(args.dump_outputs, {"enhanced_spectrograms": enhanced})
+    prof, elapsed_prof = {}, None
+    if args.full:
+        # (2) the same K steps again with the library's per-launch HIP events (recorded on the launch stream) around the
+        # dominant kernel (plain launches of the identical launch list).  Its wall time is reported next to the timed
+        # region's (roofline.profiled_region_*).
+        model.dnn.profile_begin(0)
+        _, _, elapsed_prof = timed_region()
+        prof = model.dnn.profile_end()
     per_rank_ms = [1e3 * elapsed / args.steps]
     if world > 1:                                  # MAX over ranks is the job's time; keep every rank's own clock too
         tt = torch.zeros(world, dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
@@ -613,9 +675,10 @@ def main():
                    "workspace_GB": round(ws_bytes / 2 ** 30, 2)},
         "per_rank_ms_per_step": [round(v, 3) for v in per_rank_ms],
         "achieved_TFLOPs_whole_path": value * nfe_per_step * FLOP_PER_FRAME_NFE / world / 1e12,
+        "full": args.full, "dumped_outputs": dumped,
     }
     vb_strong = None
-    if world > 1 and args.solver == "euler" and not args.no_strong:
+    if args.full and world > 1 and args.solver == "euler" and not args.no_strong:
         # The weak-scaling number above is ~N x by construction; the workload that shows what N GPUs buy is BASELINE
         # config[3]: the whole ragged set (fixed total work) dealt to the ranks, one final RCCL gather to rank 0.
         a3 = argparse.Namespace(**vars(args))
@@ -707,7 +770,7 @@ def main():
                 gbs = v["bytes"] / (v["ms"] * 1e-3) / 1e9 if v["ms"] > 0 else 0
                 print(f"# {k:44s} n={v['launches']:4d} {v['ms']:9.3f} ms {100*v['ms']/tot:5.1f}% "
                       f"{tf:7.1f} TF/s {gbs:8.0f} GB/s", file=sys.stderr)
-        if world == 1 and args.precision == "fp32" and args.solver == "euler" and not args.no_alt:
+        if args.full and world == 1 and args.precision == "fp32" and args.solver == "euler" and not args.no_alt:
             # the optional operand modes of the same kernels, same workload, reported beside the exact-fp32 value
             ref_x = x.clone()
             alts = {}
@@ -793,7 +856,7 @@ def main():
             vs["n1_full_set_reference"] = ref1
             vs["vs_N1_full_set"] = (vb_strong["value"] / ref1["value"]) if ref1 else None
             out.setdefault("alt_workloads", {})["vbdmd_strong"] = vs
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             want_oracle = args.solver == "euler" and T <= 256        # 1 utterance x N NFE of the CPU oracle: ~10 s at T = 256
             x_or, out["cpu_baseline"] = cpu_baseline(sd, NS, T, args.cpu_reps, oracle_utt=(rank * B) if want_oracle else None)
             out["gpu_vs_cpu"] = value / out["cpu_baseline"]["value"]

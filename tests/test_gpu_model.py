@@ -504,7 +504,7 @@ def test_bench_spawns_its_own_ranks():
         env["FLOWSE_BENCH_SHARE_GPU"] = "1"
         env["FLOWSE_BENCH_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "1",
-           "--frames", "64", "--no-cpu-baseline", "--no-alt", "--utts", "12"]
+           "--frames", "64", "--no-cpu-baseline", "--no-alt", "--utts", "12", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -513,7 +513,8 @@ def test_bench_spawns_its_own_ranks():
     assert out["n_gpus"] == 2 and len(out["per_rank_ms_per_step"]) == 2 and out["value"] > 0
     assert out["config"]["global_batch"] == 2
     assert out["config"]["collective_backend"] == ("nccl" if two else "gloo")
-    # world > 1: the strong-scaling config[3] pass rides in the same line (the weak-scaling value is ~N x by construction)
+    # world > 1, --full: the strong-scaling config[3] pass rides in the same line (the weak-scaling value is ~N x by
+    # construction)
     vs = out["alt_workloads"]["vbdmd_strong"]
     assert vs["scaling"] == "strong" and vs["value"] > 0 and vs["config"]["utterances"] == 12
     assert len(vs["per_rank"]["last_pass_sampler_ms"]) == 2 and len(vs["per_rank"]["last_pass_gather_ms"]) == 2
@@ -531,6 +532,33 @@ def test_bench_spawns_its_own_ranks():
         env2 = {k: v for k, v in os.environ.items() if not k.startswith("FLOWSE_BENCH")}
         r2 = subprocess.run(cmd, env=env2, capture_output=True, text=True, timeout=800)
         assert r2.returncode != 0 and "visible devices" in (r2.stderr + r2.stdout)
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_identical_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and nothing more (no --full legs in the line), and
+    --dump-outputs writes the last step's enhanced spectrograms: finite float32, bit-identical in a second process."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch",
+               "2", "--frames", "64", "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=500)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["full"] is False
+        assert abs(j["value"] - 3 * 2 * 64 / (3e-3 * j["ms_per_step"])) < 1e-6 * j["value"]
+        assert not any(k in j for k in ("roofline", "alt_precision", "alt_workloads", "cpu_baseline", "rel_l2_vs_oracle"))
+        assert j["dumped_outputs"]["enhanced_spectrograms"] == {"shape": [2, 1, 256, 64, 2], "sampled_elements": None}
+        outs.append(np.load(tmp_path / run / "enhanced_spectrograms.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (2, 1, 256, 64, 2) and np.isfinite(outs[0]).all()
+    assert np.array_equal(outs[0], outs[1]), "same arguments, different outputs"
 
 
 @pytest.mark.timeout(600)

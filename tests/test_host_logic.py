@@ -226,6 +226,42 @@ def test_plan_shards_config3_partition():
     assert plan_batches(range(3), [192, 128, 128], 8) == [(192, [0]), (128, [1, 2])]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per array (complex as its real view); above the size cap a seeded sample
+    that is the same in every run and keeps the whole under the cap."""
+    import bench
+    x = torch.view_as_complex(torch.arange(2 * 3 * 4 * 2, dtype=torch.float32).reshape(2, 3, 4, 2))
+    info = bench.dump_outputs(str(tmp_path / "a"), {"enhanced": x})
+    got = np.load(tmp_path / "a" / "enhanced.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 3, 4, 2) and info["enhanced"]["sampled_elements"] is None
+    assert np.array_equal(got, torch.view_as_real(x).numpy())
+    big = {"u": torch.linspace(-1, 1, 50000, dtype=torch.float64), "v": torch.ones(30000)}
+    cap = 64 * 1024
+    i1 = bench.dump_outputs(str(tmp_path / "b"), big, max_bytes=cap)
+    i2 = bench.dump_outputs(str(tmp_path / "c"), big, max_bytes=cap)
+    assert i1 == i2 and i1["u"]["sampled_elements"] and i1["v"]["sampled_elements"]
+    files = [tmp_path / d / (n + ".npy") for d in "bc" for n in "uv"]
+    assert sum(os.path.getsize(f) for f in files[:2]) <= cap
+    for n in "uv":
+        a, b = np.load(tmp_path / "b" / (n + ".npy")), np.load(tmp_path / "c" / (n + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    u = np.load(tmp_path / "b" / "u.npy")
+    assert np.all(np.diff(u) > 0) and np.isin(u, big["u"].float().numpy()).all()    # sorted indices into the array
+
+
+def test_bench_options():
+    """--full and --dump-outputs exist; --steps sets the timed steps and must be at least one (checked before any GPU
+    work)."""
+    import subprocess
+    import sys
+    h = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=120)
+    assert h.returncode == 0 and "--full" in h.stdout and "--dump-outputs" in h.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_gather_staging_buffer_is_reused_not_aliased():
     """Rank 0's host staging of the final gather (parallel._acquire_stage): two consecutive gathers reuse ONE buffer
     (no per-call allocation / page-locking) -- unless a result of the first is still alive, which must never be aliased."""

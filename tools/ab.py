@@ -3,7 +3,8 @@
 
     python tools/ab.py [--bench-args "..."] NAME [NAME ...]      # NAME = variants/NAME, or "base" for the shipped build
 
-Runs bench.py once per variant (fresh process, FLOWSE_LIB_PATH) and prints value / dominant-kernel time / fraction.
+Runs bench.py once per variant (fresh process, FLOWSE_LIB_PATH) and prints value / dominant-kernel time / fraction
+(the last two come from the --full line: keep --full in a --bench-args of your own).
 """
 import json
 import os
@@ -15,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     a = sys.argv[1:]
-    bargs = "--steps 5 --warmup 2 --no-alt --no-cpu-baseline"
+    bargs = "--full --steps 5 --warmup 2 --no-alt --no-cpu-baseline"    # --full: the line carries the roofline
     if a and a[0] == "--bench-args":
         bargs = a[1]
         a = a[2:]
