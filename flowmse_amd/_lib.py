@@ -82,6 +82,7 @@ SIGNATURES = {
     "flowse_op_fir_up": (_i, [_fp, _fp, _i, _i, _i, _i, _vp]),
     "flowse_op_fir_down": (_i, [_fp, _fp, _i, _i, _i, _i, _vp]),
     "flowse_op_attention": (_i, [_fp, _fp, _i, _i, _i, _vp]),
+    "flowse_op_attention_16": (_i, [_fp, _fp, _i, _i, _i, _i, _vp, _i64, _vp]),
     "flowse_op_gfp": (_i, [_fp, _fp, _fp, _i, _i, _vp]),
 }
 

@@ -186,8 +186,8 @@ __global__ __launch_bounds__(512, 2) void conv_smallm16b_kernel(ConvArgs a) {
     __syncthreads();
     const int PB = HW < BM ? HW : BM;
     const int groups = BM / PB;
-    if (tid < groups * BN) {
-        const int g = tid / BN, c = tid - g * BN;
+    for (int idx = tid; idx < groups * BN; idx += 512) {      // (H W = 1: more (block, channel) pairs than threads)
+        const int g = idx / BN, c = idx - g * BN;
         const int mg = m0 + g * PB;
         if (mg < M) {
             float sum = 0.f;

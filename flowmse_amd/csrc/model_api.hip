@@ -1098,6 +1098,28 @@ int flowse_op_fir_down(const float* in, float* out, int B, int H, int W, int C, 
 int flowse_op_attention(const float* qkv, float* out, int B, int L, int C, void* stream) {
     return launch_attention(qkv, B, L, C, out, static_cast<hipStream_t>(stream));
 }
+// 16-bit attention core: the fp32 tokens rounded to bf16 (dt 1) / half (dt 2) in scratch, attention16_kernel, result widened
+int flowse_op_attention_16(const float* qkv, float* out, int B, int L, int C, int dt, void* scratch, int64_t scratch_bytes,
+                           void* stream) {
+    if (!qkv || !out || !scratch || (dt != DT_BF16 && dt != DT_F16) || B < 1 || L < 1 || C < 1) {
+        set_error("flowse_op_attention_16: bad argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t n = (int64_t)B * L * C;
+    auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
+    const int64_t need = up(2 * 3 * n) + up(2 * n);
+    if (scratch_bytes < need) {
+        set_error("flowse_op_attention_16: scratch needs %lld bytes", (long long)need);
+        return ERR_ARG;
+    }
+    char* q16 = static_cast<char*>(scratch);
+    char* o16 = q16 + up(2 * 3 * n);
+    int rc = launch_convert(qkv, DT_F32, q16, dt, 3 * n, s);
+    if (rc == OK) rc = launch_attention(q16, B, L, C, o16, s, dt);
+    if (rc != OK) return rc;
+    return launch_convert(o16, dt, out, DT_F32, n, s);
+}
 int flowse_op_gfp(const float* t, const float* W, float* out, int B, int E, void* stream) {
     return launch_gfp(t, W, B, E, out, static_cast<hipStream_t>(stream));
 }

@@ -288,6 +288,11 @@ int flowse_op_fir_up(const float* in, float* out, int B, int H, int W, int C, vo
 int flowse_op_fir_down(const float* in, float* out, int B, int H, int W, int C, void* stream);
 /* softmax(q k^T C^-1/2) v over L tokens; qkv [B][L][3C], out [B][L][C] (layerspp.py:82-86). */
 int flowse_op_attention(const float* qkv, float* out, int B, int L, int C, void* stream);
+/* The same on the 16-bit matrix cores (attention16_kernel, as in the bf16 / fp16 storage modes of the model handle; dt 1 =
+ * bf16, 2 = IEEE half): qkv is rounded to dt on the way in, the result widened back.  `scratch`: device memory of at least
+ * 2*(4*B*L*C) + 512 bytes. */
+int flowse_op_attention_16(const float* qkv, float* out, int B, int L, int C, int dt, void* scratch, int64_t scratch_bytes,
+                           void* stream);
 /* GaussianFourierProjection(log t) (layerspp.py:39-41, ncsnpp.py:259): out [B][2E] */
 int flowse_op_gfp(const float* t, const float* W, float* out, int B, int E, void* stream);
 

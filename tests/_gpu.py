@@ -95,6 +95,18 @@ def attention(q, k, v):
     return out.permute(0, 2, 1).contiguous().cpu()
 
 
+def attention16(q, k, v, dt):
+    """The same through the 16-bit kernel (dt 1 = bf16, 2 = half): q, k, v are rounded to dt inside"""
+    B, Cc, Lt = q.shape
+    qkv = torch.cat([q.permute(0, 2, 1), k.permute(0, 2, 1), v.permute(0, 2, 1)], dim=2).contiguous().cuda()
+    out = torch.empty(B, Lt, Cc, device="cuda")
+    scratch = torch.empty(8 * B * Lt * Cc + 512, dtype=torch.uint8, device="cuda")
+    _lib.check(L.flowse_op_attention_16(_lib.ptr(qkv), _lib.ptr(out), B, Lt, Cc, dt, _lib.ptr(scratch), scratch.numel(),
+                                        stream()))
+    torch.cuda.synchronize()
+    return out.permute(0, 2, 1).contiguous().cpu()
+
+
 def gfp(t, W):
     B, E = t.numel(), W.numel()
     td, Wd = t.cuda().contiguous(), W.cuda().contiguous()

@@ -212,8 +212,8 @@ def test_full_sampler_vs_oracle_B8_T256_N5(full):
 def test_full_net_ragged_set_through_enhance_sharded(full):
     """BASELINE config[3] on one rank with the released architecture: 18 ragged utterances (true lengths 40..300 frames,
     padded to 64 k) through enhance_sharded (LPT shard -> equal-length batches of <= 4 -> N = 3 Euler sampler -> gather)
-    must equal enhancing each utterance alone (the reference's loop, evaluate.py:97-132), and two of them are checked
-    against the CPU oracle."""
+    must equal enhancing each utterance alone (the reference's loop, evaluate.py:97-132), and three of them (one a row of
+    the 320-frame batch) are checked against the CPU oracle."""
     from flowmse_amd.parallel import enhance_sharded
     from flowmse_amd.sampling import get_white_box_solver
     from flowmse_amd.util.other import pad_spec
@@ -248,7 +248,7 @@ def test_full_net_ragged_set_through_enhance_sharded(full):
     assert worst < 2e-5
     tb = C.param_tables()["full"]
     w = C.synth_weights(tb["names"], tb["shapes"])
-    for i in (1, 3):                                            # 40 -> 64 and 100 -> 128 frames
+    for i in (1, 3, 9):                                         # 40 -> 64, 100 -> 128 and 300 -> 320 frames
         Yc = pad_spec(specs[i][None, None]).cpu()
         ref, _ = S.euler_sample_net(w, O.make_cfg(), Yc, noise(i, Yc.shape[-1]), N=N)
         err = C.rel_l2(out[i], ref[0, 0, :, :lens[i]])
@@ -256,11 +256,14 @@ def test_full_net_ragged_set_through_enhance_sharded(full):
         assert err < TIGHT
 
 
-@pytest.mark.parametrize("B,T", [(1, 64), (1, 192), (3, 128), (8, 64)])
+@pytest.mark.parametrize("B,T", [(1, 64), (1, 192), (3, 128), (8, 64)] +
+                         [pytest.param(1, T, marks=pytest.mark.timeout(120)) for T in (320, 640, 1024)])
 def test_full_forward_shapes_vs_oracle(full, B, T):
     """Smallest legal utterance, a frame count that is not a power of two (W = 192, 96, 48, 24, 12, 6, 3), an odd
     batch, and the headline batch size B = 8 (its own kernel dispatch: Winograd plan / split slices are chosen from
-    B*H*W), with per-sample times spanning the grid ends (t = 0.03 amplifies the head by 33x)."""
+    B*H*W), with per-sample times spanning the grid ends (t = 0.03 amplifies the head by 33x).  T = 320 / 640 (BASELINE
+    config[3]'s padded lengths: level widths 40, 20, 10, 5 that no 16-column tiling covers) and T = 1024 (config[4]:
+    attention over 1024 tokens)."""
     from oracle import ncsnpp_oracle as O
     tb = C.param_tables()["full"]
     w = C.synth_weights(tb["names"], tb["shapes"])
@@ -325,6 +328,36 @@ def test_precision_modes_vs_oracle(full, mode, bound):
         full.dnn.set_precision("fp32")
     err = C.rel_l2(got.cpu(), ref)
     print(f"full forward [2,2,256,128] precision={mode} rel-L2 vs oracle", err)
+    assert err < bound
+
+
+@pytest.fixture(scope="module")
+def t1024_case():
+    """[1,2,256,1024] network input and the oracle's output on it (computed once for the precision modes below)"""
+    from oracle import ncsnpp_oracle as O
+    tb = C.param_tables()["full"]
+    w = C.synth_weights(tb["names"], tb["shapes"])
+    x = C.c64(synth.complex_normal(24, 1, (1, 1, 256, 1024), 0.5))
+    y = C.c64(synth.synth_spectrogram(56, 1, 256, 1024))
+    t = torch.tensor([0.2725])
+    inp = torch.cat([x, y], 1)
+    return inp, t, O.ncsnpp_forward(w, O.make_cfg(), inp, t)
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("mode,bound", [("bf16", 2.1e-2), ("fp16", 2.5e-3), ("bf16x3", 2.5e-5)])
+def test_precision_modes_T1024_vs_oracle(full, t1024_case, mode, bound):
+    """The storage / operand modes at BASELINE config[4]'s frame count (attention over 1024 tokens, the 16-bit attention
+    kernel's several key tiles per wave) against the CPU oracle; ceilings ~2x what the MI355X measures (bf16 1.06e-2,
+    half 1.23e-3, bf16x3 1.1e-5)."""
+    inp, t, ref = t1024_case
+    full.dnn.set_precision(mode)
+    try:
+        got = full.dnn(inp.cuda(), t.cuda())
+    finally:
+        full.dnn.set_precision("fp32")
+    err = C.rel_l2(got.cpu(), ref)
+    print(f"full forward [1,2,256,1024] precision={mode} rel-L2 vs oracle {err:.3e}")
     assert err < bound
 
 
@@ -564,25 +597,42 @@ def test_bench_plain_run_dumps_identical_outputs(tmp_path):
 @pytest.mark.timeout(600)
 def test_config5_shape(full):
     """BASELINE config 5 shape [32,1,256,1024] (32 GB workspace, 8.4 M pixels at level 0): one vector-field
-    evaluation is finite; sample 7 equals the same sample evaluated alone (batch independence, exact-fp32 mode);
-    the fp16 operand mode stays within 5e-3 of the fp32 result."""
+    evaluation is finite; samples 7 and 31 equal the same sample evaluated alone (batch independence, exact-fp32 mode);
+    the fp16 operand mode stays within 5e-3 of the fp32 result.  Sample 31 sits at the highest offsets of every level-0
+    tensor (1.07e9 elements at 128 channels, 2.1e9 at the 256-channel concat: a wrapping 32-bit offset would hit only
+    the late samples): in both modes it is also checked alone against in-batch and against the oracle forward."""
+    from oracle import ncsnpp_oracle as O
     B, T = 32, 1024
     g = torch.Generator(device="cuda").manual_seed(5)
     x = torch.view_as_complex(torch.randn(B, 1, 256, T, 2, device="cuda", generator=g) * 0.35)
     y = torch.view_as_complex(torch.randn(B, 1, 256, T, 2, device="cuda", generator=g) * 0.07)
     t = torch.linspace(0.05, 1.0, B, device="cuda")
+
+    def alone(i):
+        return full(x[i:i + 1].contiguous(), t[i:i + 1].contiguous(), y[i:i + 1].contiguous()).cpu()
+
     a = full(x, t, y)
     assert torch.isfinite(torch.view_as_real(a)).all()
-    one = full(x[7:8].contiguous(), t[7:8].contiguous(), y[7:8].contiguous())
-    assert C.rel_l2(one.cpu(), a[7:8].cpu()) < 2e-5
+    a = a.cpu()
+    for i in (7, 31):
+        assert C.rel_l2(alone(i), a[i:i + 1]) < 2e-5
+    tb = C.param_tables()["full"]
+    w = C.synth_weights(tb["names"], tb["shapes"])
+    ref31 = O.vf_forward(w, O.make_cfg(), x[31:32].cpu(), t[31:32].cpu(), y[31:32].cpu())
+    err31 = C.rel_l2(a[31:32], ref31)
     full.dnn.set_precision("fp16")
     try:
-        a16 = full(x, t, y)
+        a16 = full(x, t, y).cpu()
+        one16 = alone(31)
     finally:
         full.dnn.set_precision("fp32")
-    err = C.rel_l2(a16.cpu(), a.cpu())
-    print("config-5 shape: fp16 mode vs fp32 mode rel-L2", err)
+    err = C.rel_l2(a16, a)
+    err16_31, alone16 = C.rel_l2(a16[31:32], ref31), C.rel_l2(one16, a16[31:32])
+    print(f"config-5 shape: fp16 mode vs fp32 mode rel-L2 {err:.3e}; sample 31 vs oracle: fp32 {err31:.3e}, fp16 "
+          f"{err16_31:.3e}; fp16 sample 31 alone vs in batch {alone16:.3e}")
     assert err < 5e-3
+    assert err31 < TIGHT
+    assert err16_31 < 1.3e-3 and alone16 < 9e-4          # ~2x the MI355X's 6.2e-4 / 4.3e-4
 
 
 @pytest.mark.timeout(1200)
@@ -610,6 +660,44 @@ def test_config5_rk4_n25_sampler(full):
     print("config 5: sample alone vs in batch rel-L2", err, " |x|/|y| =", float(a.abs().mean() / Y.abs().mean()))
     assert err < 5e-3           # fp16 operands, different split plans at B = 1: rounding-level, not bitwise
     assert 0.05 < float(a.abs().mean() / Y.abs().mean()) < 20.0
+
+
+@pytest.fixture(scope="module")
+def config4_rk4_case():
+    """BASELINE config[4] inputs (B = 32, T = 1024: utterances 300..331) and the oracle's RK4 N = 2 samples 0 and 31
+    (S.rk_sample over O.vf_forward: 5 network evaluations each)"""
+    from oracle import ncsnpp_oracle as O
+    from oracle import sampler_oracle as S
+    B, T = 32, 1024
+    Y = torch.cat([C.c64(synth.synth_spectrogram(300 + i, 1, 256, T)) for i in range(B)])
+    Z = torch.cat([C.c64(synth.synth_noise(300 + i, 1, 256, T)) for i in range(B)])
+    tb = C.param_tables()["full"]
+    w = C.synth_weights(tb["names"], tb["shapes"])
+    cfg = O.make_cfg()
+    refs = {i: S.rk_sample(lambda x, tt, yy: O.vf_forward(w, cfg, x, tt, yy), Y[i:i + 1], Z[i:i + 1], tableau="rk4", N=2)
+            for i in (0, 31)}
+    return Y, Z, refs
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("mode,bound", [("fp32", 5 * TIGHT), ("fp16", 5e-3)])
+def test_config4_rk4_sampler_vs_oracle(full, config4_rk4_case, mode, bound):
+    """BASELINE config[4]'s solver at its real shape -- fused RK4 (flowse_rk_sample) over [32,1,256,1024], N = 2 (5 network
+    evaluations) -- with samples 0 and 31 (the lowest and highest offsets of the batch) against the oracle composition;
+    fp32 at the 5 x TIGHT of the small-size composition test (measured 2.7e-6), fp16 under ~2x the MI355X's measured
+    error (2.5e-3: the last Euler step at t = 0.03 amplifies the head's rounding)."""
+    from flowmse_amd.sampling import get_white_box_solver
+    Y, Z, refs = config4_rk4_case
+    full.dnn.set_precision(mode)
+    try:
+        got, n = get_white_box_solver("rk4", full.ode, full, Y=Y.cuda(), N=2, z=Z.cuda())()
+        got = got.cpu()
+    finally:
+        full.dnn.set_precision("fp32")
+    assert n == 2 and torch.isfinite(torch.view_as_real(got)).all()
+    errs = {i: C.rel_l2(got[i:i + 1], ref) for i, ref in refs.items()}
+    print(f"config[4] RK4 N=2 {mode}: rel-L2 vs oracle composition per sample {errs}")
+    assert max(errs.values()) < bound
 
 
 def test_rejects_cpu_and_bad_shapes(tiny):

@@ -374,13 +374,26 @@ def test_upfirdn2d_nchw(G, up, down, pad, ksz):
     assert C.rel_l2(got, ref) < TOL
 
 
-@pytest.mark.parametrize("Cc,Lt", [(32, 64), (64, 256), (256, 16), (256, 48), (128, 100), (256, 256)])
+def _attention_ref(q, k, v):
+    """softmax(q^T k / sqrt(C)) v^T in float64 (layerspp.py:82-86)"""
+    q, k, v = q.double(), k.double(), v.double()
+    w = F.softmax(torch.einsum("bci,bcj->bij", q, k) * (int(q.shape[1]) ** (-0.5)), dim=-1)
+    return torch.einsum("bij,bcj->bci", w, v)
+
+
+# (C, L): the kernels deal 32-key tiles round-robin to 8 waves, so L > 256 is where a wave owns several tiles and rescales its
+# own running softmax state between them.  L = 320 / 640 / 1024: the attention of the released network at T = 320 / 640 /
+# 1024 frames (H = 16); 290: wave 1's second tile holds 2 keys; 1000: a partial last tile on wave 7's fourth pass.
+ATT_CASES = [(32, 64), (64, 256), (256, 16), (256, 48), (128, 100), (256, 256),
+             (256, 320), (256, 640), (256, 1024), (128, 290), (64, 1000)]
+
+
+@pytest.mark.parametrize("Cc,Lt", ATT_CASES)
 def test_attention(G, Cc, Lt):
     q, k, v = rnd(30, (2, Cc, Lt)), rnd(31, (2, Cc, Lt)), rnd(32, (2, Cc, Lt))
-    w = torch.einsum("bci,bcj->bij", q, k) * (int(Cc) ** (-0.5))
-    w = F.softmax(w, dim=-1)
-    ref = torch.einsum("bij,bcj->bci", w, v)
-    assert C.rel_l2(G.attention(q, k, v), ref) < TOL
+    err = C.rel_l2(G.attention(q, k, v), _attention_ref(q, k, v))
+    print(f"attention C={Cc} L={Lt}: rel-L2 vs float64 {err:.3e}")
+    assert err < TOL
 
 
 def test_attention_peaked(G):
@@ -391,6 +404,68 @@ def test_attention_peaked(G):
     w = F.softmax(torch.einsum("bci,bcj->bij", q, k) * (int(Cc) ** (-0.5)), dim=-1)
     ref = torch.einsum("bij,bcj->bci", w, v)
     assert C.rel_l2(G.attention(q, k, v), ref) < TOL
+    assert C.rel_l2(G.attention(q, k, v), _attention_ref(q, k, v)) < TOL
+
+
+def _peaked_multi_tile():
+    """L = 1024 (4 key tiles per wave; tile t = keys 32t.., wave t % 8, that wave's pass t // 8) with keys planted so that
+    a wave's running max moves between its own tiles.  Ordinary logits: std 16, max ~55 per query.
+      query 5:   key 1000 (tile 31: wave 7, fourth pass) at logit 100 -- the maximum arrives last;
+      query 700: key 70 (tile 2: wave 2, first pass) at 100, key 850 (tile 26: wave 2, fourth pass) at 101 -- a large
+                 running max raised again by the same wave's later tile (rescale of a state that already holds weight);
+      query 300: key 100 (tile 3: wave 3, first pass) at 101, key 870 (tile 27: wave 3, fourth pass) at 100 -- the max
+                 comes first and a later tile of the same wave still carries e^-1 of the weight (no rescale, alpha = 1).
+    Both planted keys of a query carry comparable weight, so a wrong rescale factor moves the output by O(1); the
+    planted rows themselves are only fp32-conditioned to ~1e-5 (a logit of 100 carries ~1e-5 of rounding, which moves the
+    e^-1 weight split by as much), hence their own 1e-4 bound in the fp32 test."""
+    Cc, Lt = 64, 1024
+    q, k, v = rnd(36, (1, Cc, Lt), 4.0), rnd(37, (1, Cc, Lt), 4.0), rnd(38, (1, Cc, Lt))
+
+    def plant(qi, key, logit):
+        qq = q[0, :, qi]
+        k[0, :, key] = qq * (logit * Cc ** 0.5 / float(qq @ qq))
+
+    plant(5, 1000, 100.0)
+    plant(700, 70, 100.0)
+    plant(700, 850, 101.0)
+    plant(300, 100, 101.0)
+    plant(300, 870, 100.0)
+    return q, k, v
+
+
+def test_attention_peaked_multi_tile(G):
+    q, k, v = _peaked_multi_tile()
+    got, ref = G.attention(q, k, v), _attention_ref(q, k, v)
+    err = C.rel_l2(got, ref)
+    rows = {i: C.rel_l2(got[..., i], ref[..., i]) for i in (5, 300, 700)}
+    print(f"attention peaked L=1024: rel-L2 vs float64 {err:.3e}, planted queries {rows}")
+    assert err < TOL and max(rows.values()) < 1e-4
+
+
+# 16-bit attention core (flowse_op_attention_16 -> attention16_kernel, the bf16 / fp16 storage modes' attention): the reference
+# is float64 over q / k / v ROUNDED to the storage type, so the bound measures the kernel (16-bit P, fp32 accumulation and
+# softmax state, one rounding of the output), not the input rounding.  Ceilings ~2x what the MI355X measures over these
+# cases (bf16 2.0-2.1e-3, half 2.4-2.6e-4; planted rows of the peaked case 1.6e-3 / 2.3e-4).
+ATT16 = [(1, torch.bfloat16, 4.5e-3), (2, torch.float16, 5.5e-4)]
+
+
+@pytest.mark.parametrize("dt,ty,bound", ATT16, ids=["bf16", "fp16"])
+@pytest.mark.parametrize("Cc,Lt", ATT_CASES)
+def test_attention_16bit(G, Cc, Lt, dt, ty, bound):
+    q, k, v = (t.to(ty).float() for t in (rnd(30, (2, Cc, Lt)), rnd(31, (2, Cc, Lt)), rnd(32, (2, Cc, Lt))))
+    err = C.rel_l2(G.attention16(q, k, v, dt), _attention_ref(q, k, v))
+    print(f"attention16 C={Cc} L={Lt} {ty}: rel-L2 vs float64 of the rounded inputs {err:.3e}")
+    assert err < bound
+
+
+@pytest.mark.parametrize("dt,ty,bound", ATT16, ids=["bf16", "fp16"])
+def test_attention_16bit_peaked_multi_tile(G, dt, ty, bound):
+    q, k, v = (t.to(ty).float() for t in _peaked_multi_tile())
+    got, ref = G.attention16(q, k, v, dt), _attention_ref(q, k, v)
+    err = C.rel_l2(got, ref)
+    rows = {i: C.rel_l2(got[..., i], ref[..., i]) for i in (5, 300, 700)}
+    print(f"attention16 peaked L=1024 {ty}: rel-L2 vs float64 of the rounded inputs {err:.3e}, planted queries {rows}")
+    assert err < bound and max(rows.values()) < bound
 
 
 def test_gfp_golden(G):
