@@ -36,7 +36,7 @@ if not os.path.exists(LIB_PATH):
 
 lib = C.CDLL(LIB_PATH)
 
-_vp, _fp, _i, _i64, _f = C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float
+_vp, _fp, _i, _i64, _f, _d = C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 # name -> (restype, argtypes); every symbol declared in include/flowse_hip.h
 SIGNATURES = {
@@ -58,6 +58,8 @@ SIGNATURES = {
     "flowse_prior_sample": (_i, [_vp, _vp, _f, _vp, _i64, _vp]),
     "flowse_euler_sample": (_i, [_vp, _vp, _vp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _vp]),
     "flowse_rk_sample": (_i, [_vp, _vp, _vp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _i, _vp]),
+    "flowse_rk45_sample": (_i, [_vp, _vp, _vp, _d, _d, _d, _d, _d, _d, _i64, _i, _i, _i, C.POINTER(_i64), C.POINTER(_i),
+                               C.POINTER(_d), _i, C.POINTER(_i), _vp]),
     "flowse_model_graph_launches": (_i64, [_vp]),
     "flowse_axpy": (_i, [_vp, _vp, _f, _vp, _i64, _vp]),
     "flowse_stft_compress": (_i, [_fp, _i, _i, _f, _vp, _i, _i, _f, _f, _vp]),

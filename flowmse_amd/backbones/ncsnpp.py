@@ -292,6 +292,29 @@ class NCSNpp(nn.Module):
                                                  self.TABLEAUS[tableau], B, F, T, _lib.current_stream()))
         return x
 
+    def rk45_sample(self, x, y, t0, t_bound, rtol, atol, first_step=None, max_step=float("inf"), max_nfev=100000):
+        """Adaptive Dormand-Prince 5(4) from t0 to t_bound, in place on x: one C-ABI call that takes the steps scipy's
+        ``solve_ivp(method="RK45")`` takes (flowse_rk45_sample in include/flowse_hip.h; one 8-byte read-back per
+        attempted step).  ``first_step=None``: scipy's initial-step selection.  Returns
+        ``(x, nfev, status, accepted_times)`` with scipy's nfev and ``solution.t[1:]``; status 0 = reached t_bound,
+        -1 = step size too small (x = last accepted state), -2 = the next step would exceed ``max_nfev``."""
+        if x.dim() != 4:
+            raise ValueError(f"expected x of shape [B,1,F,T], got {tuple(x.shape)}")
+        self._check_io(x, y, _ShapeOnly((x.shape[0],)))
+        if not (x.is_contiguous() and y.is_contiguous()):
+            raise ValueError("x and y must be contiguous")
+        self._ensure_uploaded(x.device)
+        cap = int(max_nfev) // 6 + 2            # every accepted step costs 6 evaluations
+        times = (C.c_double * cap)()
+        nfev, status, nacc = C.c_int64(), C.c_int(), C.c_int()
+        B, _, F, T = x.shape
+        with torch.cuda.device(x.device), self.weights_frozen():
+            _lib.check(_lib.lib.flowse_rk45_sample(
+                self._handle, _lib.ptr(x), _lib.ptr(y), float(t0), float(t_bound), float(rtol), float(atol),
+                0.0 if first_step is None else float(first_step), float(max_step), int(max_nfev), B, F, T,
+                C.byref(nfev), C.byref(status), times, cap, C.byref(nacc), _lib.current_stream()))
+        return x, int(nfev.value), int(status.value), list(times[:min(nacc.value, cap)])
+
     def euler_sample(self, x, y, ts, dts):
         """In-place N-step Euler integration on x (see flowse_euler_sample in include/flowse_hip.h)."""
         return self.rk_sample(x, y, ts, dts, "euler")

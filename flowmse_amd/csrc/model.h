@@ -174,6 +174,8 @@ struct flowse_model {
     int64_t graph_launches = 0;            // hipGraphLaunch calls made by this handle (flowse_model_graph_launches)
     float* d_rk = nullptr;                 // fixed-step RK scratch: stage input + slope accumulator, 2 x [B,1,F,T] complex64
     size_t d_rk_floats = 0;
+    char* d_rk45 = nullptr;                // adaptive RK45 state (flowse_rk45_sample): y, y_new, K1..K7, stage input, norms
+    size_t d_rk45_bytes = 0;
     // single-module handles (flowse_block_create): one ResnetBlockBigGANpp / AttnBlockpp / Combine behind the same
     // weight packer, plan builder and kernels as the full network -- unit parity against the reference's modules
     int block_kind = -1;                   // -1: full network; else FLOWSE_BLOCK_*
@@ -220,5 +222,11 @@ int storage_type_for(const flowse_model* m);
 // model_plan.hip
 int build_plan(flowse_model* m, Plan* plan, int B, int F, int T);
 int build_block_plan(flowse_model* m, Plan* plan, int B, int H, int W, int C1);
+// model_api.hip: plan lookup / execution and the stream fence shared by every C-ABI sampler
+int get_plan(flowse_model* m, int B, int F, int T, Plan** out);
+int exec_plan(flowse_model* m, Plan* p, hipStream_t s);
+int enter_stream(flowse_model* m, hipStream_t caller, hipStream_t* work);
+int leave_stream(flowse_model* m, hipStream_t caller, hipStream_t work);
+int reserve_times(flowse_model* m, size_t need);      // d_ts holds at least `need` floats (growth synchronises)
 
 }  // namespace flowse

@@ -30,7 +30,7 @@ static int check_device(const flowse_model* m) {
     return OK;
 }
 
-static int get_plan(flowse_model* m, int B, int F, int T, Plan** out) {
+int get_plan(flowse_model* m, int B, int F, int T, Plan** out) {
     if (!m->d_w) {
         set_error("weights not loaded: call flowse_model_load_weights first");
         return ERR_STATE;
@@ -111,7 +111,7 @@ static int run_plan(flowse_model* m, Plan* p, hipStream_t s) {
 // slower than plain launches at batch 1, equal at batch 8): first call per shape eager (also performs the one-time
 // per-device kernel attribute setup), second call captures the same launch list into a hipGraph, afterwards one
 // hipGraphLaunch per call.  Profiling (per-launch events) always runs plain launches.
-static int exec_plan(flowse_model* m, Plan* p, hipStream_t s) {
+int exec_plan(flowse_model* m, Plan* p, hipStream_t s) {
     if (!m->use_graph || m->prof_mode != -1 || s == nullptr) return run_plan(m, p, s);   // (NULL: see enter_stream)
     if (p->exec) {
         FLOWSE_HIP(hipGraphLaunch(p->exec, s));
@@ -157,7 +157,7 @@ static int exec_plan(flowse_model* m, Plan* p, hipStream_t s) {
 // Stream the work of one C-ABI call runs on.  A real stream: that stream.  The NULL stream: it cannot be captured, so
 // (unless graphs are off / a profile is being taken) the call moves to the handle's internal stream, which first waits
 // for everything the caller has enqueued on the NULL stream; leave_stream() makes the NULL stream wait for the call.
-static int enter_stream(flowse_model* m, hipStream_t caller, hipStream_t* work) {
+int enter_stream(flowse_model* m, hipStream_t caller, hipStream_t* work) {
     *work = caller;
     if (caller != nullptr || !m->use_graph || m->prof_mode != -1) return OK;
     if (!m->gstream) {
@@ -170,13 +170,25 @@ static int enter_stream(flowse_model* m, hipStream_t caller, hipStream_t* work) 
     *work = m->gstream;
     return OK;
 }
-static int leave_stream(flowse_model* m, hipStream_t caller, hipStream_t work) {
+int leave_stream(flowse_model* m, hipStream_t caller, hipStream_t work) {
     if (work == caller) return OK;
     FLOWSE_HIP(hipEventRecord(m->ev_out, work));
     FLOWSE_HIP(hipStreamWaitEvent(caller, m->ev_out, 0));
     return OK;
 }
 
+
+int reserve_times(flowse_model* m, size_t need) {
+    if (need > m->d_ts_floats) {
+        FLOWSE_HIP(hipDeviceSynchronize());
+        if (m->d_ts) FLOWSE_HIP(hipFree(m->d_ts));
+        m->d_ts = nullptr;
+        m->d_ts_floats = 0;
+        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_ts), need * sizeof(float)));
+        m->d_ts_floats = need;
+    }
+    return OK;
+}
 
 static void free_device_state(flowse_model* m) {
     int cur = 0;
@@ -203,6 +215,9 @@ static void free_device_state(flowse_model* m) {
     if (m->d_rk) (void)hipFree(m->d_rk);
     m->d_rk = nullptr;
     m->d_rk_floats = 0;
+    if (m->d_rk45) (void)hipFree(m->d_rk45);
+    m->d_rk45 = nullptr;
+    m->d_rk45_bytes = 0;
     if (m->gstream) (void)hipStreamDestroy(m->gstream);
     if (m->ev_in) (void)hipEventDestroy(m->ev_in);
     if (m->ev_out) (void)hipEventDestroy(m->ev_out);
@@ -578,18 +593,6 @@ int flowse_prior_sample(const void* y, const void* z, float sigma, void* x_out, 
 
 int flowse_axpy(const void* x, const void* k, float dt, void* out, int64_t numel_complex, void* stream) {
     return flowse_prior_sample(x, k, dt, out, numel_complex, stream);
-}
-
-static int reserve_times(flowse_model* m, size_t need) {
-    if (need > m->d_ts_floats) {
-        FLOWSE_HIP(hipDeviceSynchronize());
-        if (m->d_ts) FLOWSE_HIP(hipFree(m->d_ts));
-        m->d_ts = nullptr;
-        m->d_ts_floats = 0;
-        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_ts), need * sizeof(float)));
-        m->d_ts_floats = need;
-    }
-    return OK;
 }
 
 int flowse_euler_sample(flowse_model* m, void* x_inout, const void* y, const float* ts, const float* dts, int N, int B,

@@ -189,6 +189,11 @@ class VFModel(nn.Module):
         """Fused N-step fixed-step loop ('euler' | 'heun' | 'rk4'), in place on x: one library call, no host sync."""
         return self.dnn.rk_sample(x, y, timesteps, stepsizes, tableau)
 
+    def rk45_sample_(self, x, y, t0, t_bound, rtol, atol, first_step=None, max_step=float("inf"), max_nfev=100000):
+        """Adaptive RK45 (scipy's step control) in place on x: one library call.  Returns ``(x, nfev, status,
+        accepted_times)`` (used by sampling.get_black_box_solver)."""
+        return self.dnn.rk45_sample(x, y, t0, t_bound, rtol, atol, first_step, max_step, max_nfev)
+
     # ------------------------------------------------------------------ spectrogram helpers (model.py:190-203)
     def to_audio(self, spec, length=None):
         return self._istft(self._backward_transform(spec), length)

@@ -12,12 +12,16 @@ generic plugin loop, exactly like the reference; that loop keeps its time grid o
 device tensor back either.
 """
 import contextlib
+import math
+import numbers
+import os
+import warnings
 
 import torch
 
 from .odesolvers import ODEsolver, ODEsolverRegistry
 
-__all__ = ["ODEsolverRegistry", "ODEsolver", "get_white_box_solver", "get_black_box_solver", "time_grid"]
+__all__ = ["ODEsolverRegistry", "ODEsolver", "get_white_box_solver", "get_black_box_solver", "fused_rk45", "time_grid"]
 
 
 def time_grid(T_rev, t_eps, N, device="cpu"):
@@ -99,17 +103,66 @@ def from_flattened_numpy(x, shape):
     return torch.from_numpy(x.reshape(shape))
 
 
+_RK45_FUSED_KWARGS = frozenset(("first_step", "max_step"))
+
+
+def fused_rk45(method, VF_fn, y, rtol, atol, solver_kwargs):
+    """True when ``get_black_box_solver`` runs the solve as one library call (``VF_fn.rk45_sample_``) instead of scipy:
+    RK45, a HIP-backed field, a device state, scalar tolerances and no ``solve_ivp`` option beyond ``first_step`` /
+    ``max_step``.  ``FLOWSE_RK45_HOST=1`` (read per call) forces scipy."""
+    return (os.environ.get("FLOWSE_RK45_HOST", "0") != "1" and isinstance(method, str) and method == "RK45"
+            and callable(getattr(VF_fn, "rk45_sample_", None)) and bool(getattr(y, "is_cuda", False))
+            and _real_scalar(rtol) and _real_scalar(atol) and set(solver_kwargs) <= _RK45_FUSED_KWARGS)
+
+
+def _real_scalar(v):
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+
+def _rk45_fused(VF_fn, x, y, T_rev, t_eps, rtol, atol, first_step=None, max_step=math.inf):
+    """The device solve with scipy's argument checks (validate_tol / validate_first_step / validate_max_step)."""
+    from scipy.integrate._ivp.common import EPS
+    if rtol < 100 * EPS:
+        warnings.warn("At least one element of `rtol` is too small. "
+                      f"Setting `rtol = np.maximum(rtol, {100 * EPS})`.", stacklevel=3)
+        rtol = max(rtol, 100 * EPS)
+    if atol < 0:
+        raise ValueError("`atol` must be positive.")
+    if max_step <= 0:
+        raise ValueError("`max_step` must be positive.")
+    if first_step is not None:
+        if first_step <= 0:
+            raise ValueError("`first_step` must be positive.")
+        if first_step > abs(float(t_eps) - float(T_rev)):
+            raise ValueError("`first_step` exceeds bounds.")
+    x, nfev, status, _ = VF_fn.rk45_sample_(x, y, float(T_rev), float(t_eps), float(rtol), float(atol),
+                                            first_step=first_step, max_step=float(max_step))
+    if status == -2:
+        raise RuntimeError(f"flowse_rk45_sample: stopped after {nfev} network evaluations (max_nfev)")
+    return x, nfev
+
+
 def get_black_box_solver(ode, VF_fn, y, rtol=1e-5, atol=1e-5, T_rev=1.0, t_eps=0.03, N=30, method="RK45",
                          device="cuda", z=None, **kwargs):
     """Adaptive black-box sampler (reference: flowmse/sampling/__init__.py:64-114): scipy ``solve_ivp`` on the
     flattened complex state from T_rev down to t_eps (NOT to 0), each right-hand side evaluation being one call
     of ``VF_fn`` (host <-> device round trip per evaluation, as in the reference).  Returns ``(x, nfe)``.
-    ``evaluate.py`` imports but never calls it; provided for API completeness."""
+    ``evaluate.py`` imports but never calls it; provided for API completeness.
+
+    When :func:`fused_rk45` holds (RK45 on a HIP-backed ``VFModel``) the solve is one C-ABI call
+    (``flowse_rk45_sample``) that keeps the state on the device and takes the steps scipy takes -- same nfev, same
+    accepted times, same end point up to the summation order of the error norm; the only host traffic is one 8-byte
+    error norm per attempted step.  Everything else (other methods, array tolerances, ``t_eval``, ``dense_output``,
+    ``events``, any other callable field) runs scipy exactly as before."""
     from scipy import integrate
 
     def ode_solver(**solver_kwargs):
         with torch.no_grad():
             x = (ode.prior_sampling(y.shape, y, z)[0] if z is not None else ode.prior_sampling(y.shape, y)[0]).to(device)
+            if fused_rk45(method, VF_fn, y, rtol, atol, solver_kwargs):
+                xd = x.to(device=y.device, dtype=torch.complex64).contiguous()
+                xd, nfev = _rk45_fused(VF_fn, xd, y.contiguous(), T_rev, t_eps, rtol, atol, **solver_kwargs)
+                return xd.to(device), nfev
 
             def ode_func(t, xf):
                 xt = from_flattened_numpy(xf, y.shape).to(device).type(torch.complex64)

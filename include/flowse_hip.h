@@ -164,6 +164,30 @@ int flowse_euler_sample(flowse_model* m, void* x_inout, const void* y, const flo
 #define FLOWSE_TABLEAU_RK4 2
 int flowse_rk_sample(flowse_model* m, void* x_inout, const void* y, const float* ts, const float* dts, int N,
                      int tableau, int B, int F, int T, void* stream);
+/* Adaptive Dormand-Prince 5(4): the reference's black-box sampler (flowmse/sampling/__init__.py:64-114,
+ * scipy.integrate.solve_ivp(ode_func, (t0, t_bound), x, method="RK45", rtol, atol)) with the state on the device.  The
+ * controller is a line-by-line port of scipy 1.15's RungeKutta._step_impl / rk_step / select_initial_step and
+ * OdeSolver.step, all scalars in double, and takes the same steps: y / y_new are complex128 as in scipy, the slopes
+ * K1..K7 complex64 (network outputs), each network input complex64(stage state) as the reference's ode_func casts it,
+ * and the stage combinations repeat numpy's operation order (only the RMS norm's summation order differs, ~1e-16
+ * relative; it is a fixed partition and order, so two identical solves are bitwise identical).
+ * x_inout: complex64 [B,1,F,T], start state in, complex64(y at the last accepted time) out.  The batch is ONE ODE
+ * system with one error norm, as in the reference.  first_step <= 0: scipy's select_initial_step, else the given
+ * first step (0 < first_step <= |t_bound - t0|); max_step may be +inf.  nfev_out counts network evaluations as scipy's
+ * nfev does (1 for f0, 1 for the initial-step probe unless first_step is given, 6 per attempted step); status_out 0 =
+ * finished at t_bound, -1 = step size fell below scipy's minimum (scipy's status -1; x holds the last accepted state),
+ * -2 = the next attempted step would exceed max_nfev (a fail-fast cap scipy does not have).  t_accepted (may be NULL
+ * when t_cap == 0) receives the first t_cap accepted times (scipy's solution.t[1:]); n_accepted the number of them.
+ * Each evaluation is the shape's launch list with VF = -dnn (flowse_vf_forward mode 1; plain launches or, under
+ * FLOWSE_GRAPH=1, one hipGraph launch), its time ones(B) * t passed by value.  Synchronisation: unlike the samplers
+ * above this call is NOT free of host synchronisation -- the step controller reads one 8-byte error norm back per
+ * attempted step (and one per norm of select_initial_step: three), waiting on the stream each time.  The work
+ * buffers (2 x complex128 + 8 x complex64 per element) are allocated per handle on first use; growing them
+ * synchronises the device once. */
+int flowse_rk45_sample(flowse_model* m, void* x_inout, const void* y, double t0, double t_bound, double rtol,
+                       double atol, double first_step, double max_step, int64_t max_nfev, int B, int F, int T,
+                       int64_t* nfev_out, int* status_out, double* t_accepted, int t_cap, int* n_accepted,
+                       void* stream);
 /* Number of hipGraphLaunch calls this handle has issued so far (0 while every evaluation ran as plain launches). */
 int64_t flowse_model_graph_launches(const flowse_model* m);
 /* One generic explicit update from a caller-held slope: x <- x + dt * k (complex64 as float pairs). */
