@@ -189,9 +189,13 @@ struct Builder {
             int taps, const Tn* res, float scale, bool out_is_res = false, bool cin4 = false,
             const GnBuf* gin = nullptr, bool gin_silu = false, int64_t wq_off = -1, int out_dt = -1,
             SkPartial* defer = nullptr, const SkPartial* extra = nullptr, GnFuse* gnf = nullptr,
-            const ScFold* fold = nullptr, bool no_stats = false) {
+            const ScFold* fold = nullptr, bool no_stats = false, int64_t bias_sc = -1) {
         flowse_model* M = m;
         const int C1 = a.C, C2 = b2 ? b2->C : 0, H = a.H, Wd = a.W, Bn = B;
+        if (bias_sc >= 0 && dense_row0 >= 0) {           // both ride on ConvArgs::bias2
+            set_error("internal: a second per-channel bias and a Dense row on one conv (%s)", label.c_str());
+            failed = true;
+        }
         {   // a deferred reduction leaves no output tensor: decide before anything is allocated
             const bool in16_ = a.dt != DT_F32;
             const int ks_ = cin4 ? 1 : in16_ ? ((conv_supports_head4(Bn, H, Wd, C1, C2, Cout, taps) || conv16_uses_halo(Bn, H, Wd, C1, C2, Cout, taps))
@@ -284,8 +288,9 @@ struct Builder {
             c.C2 = C2;
             c.w = M->W(w);
             c.bias = bias >= 0 ? M->W(bias) : nullptr;
-            c.bias2 = dense_row0 >= 0 ? M->A(table_off) + dense_row0 : nullptr;
-            c.bias2_stride = M->dense_rows;
+            // bias_sc: a second per-channel bias from the weight blob (the same row for every sample: stride 0)
+            c.bias2 = dense_row0 >= 0 ? M->A(table_off) + dense_row0 : bias_sc >= 0 ? M->W(bias_sc) : nullptr;
+            c.bias2_stride = dense_row0 >= 0 ? M->dense_rows : 0;
             c.res = hasres ? M->A(r_off) : nullptr;
             c.out = M->A(o_off);
             c.B = Bn; c.H = H; c.W = Wd; c.Cout = Cout;
@@ -456,6 +461,13 @@ struct Builder {
                              conv16_uses_pc(B, Ho, Wo, mod.out_ch, 0, mod.out_ch, 9) &&
                              fusable_shape(m->act_dt, Ho, Wo, mod.out_ch, 0) && (x1.C % 32) == 0 && (xc2 % 32) == 0 &&
                              x1.C + xc2 >= 96 && x1.dt == m->act_dt;
+        // fp32 up blocks whose shortcut is a launch of its own: Conv_2 has no spatial extent and upsample_2d filters every
+        // channel alike, so W . up(x) = up(W . x) -- the 1x1 runs BEFORE the upsampling, on a quarter of the pixels, and the
+        // upsampled raw x never exists.  Only the bias does not commute (up(const) is not constant at the image border):
+        // Conv_1's epilogue adds it, once per output element.  Up to 2048 low-resolution pixels over the batch the reference's order
+        // stays (small-image kernels, shortcuts merged into split-K reductions: not measured in the other order).
+        const bool sc_low = mod.up && mod.shortcut && !merge_sc && !fold_sc && m->act_dt == DT_F32 && x1.dt == DT_F32 &&
+                            (int64_t)B * x1.H * x1.W > 2048 && !getenv("FLOWSE_NO_SC_LOW");
         Tn xr;
         if (!mod.up && !mod.down) {
             if (mod.shortcut && !fold_sc) {
@@ -474,6 +486,17 @@ struct Builder {
                           nullptr, false, -1, -1, nullptr, nullptr, &gf);
                 release(h0);
             }
+        } else if (sc_low) {
+            Tn xl = conv("conv2_1x1", x1, nullptr, mod.w_c2, -1, -1, mod.out_ch, 1, nullptr, 1.f, false, false, nullptr, false, -1,
+                         -1, nullptr, nullptr, nullptr, nullptr, true);
+            xs = fir(xl, true, nullptr, false, nullptr);
+            release(xl);
+            GnBuf g0 = gn(x1, x2, mod.w_gn0_g, mod.w_gn0_b);
+            Tn hr = fir(x1, true, &g0, true, nullptr);
+            gn_release(g0);
+            h1 = conv("conv0_3x3", hr, nullptr, mod.w_c0, -1, mod.dense_row0, mod.out_ch, 9, nullptr, 1.f, false, false,
+                      nullptr, false, mod.wq_c0, -1, nullptr, nullptr, &gf);
+            release(hr);
         } else {
             GnBuf g0 = gn(x1, x2, mod.w_gn0_g, mod.w_gn0_b);
             Tn hr = fir(x1, mod.up, &g0, true, nullptr, false, &xr);      // act(GN(x)) and x resampled in one pass
@@ -508,6 +531,7 @@ struct Builder {
             fo.bias = mod.w_c2_b;
         }
         const ScFold* fold = fold_sc ? &fo : nullptr;
+        const int64_t bias_sc = sc_low ? mod.w_c2_b : -1;   // Conv_2's bias, left out of the low-resolution 1x1
         if (fold && ((gf.done && gf.apply) || !fusable(h1, 0) || !conv16_uses_pc(B, h1.H, h1.W, h1.C, 0, mod.out_ch, 9) ||
                      getenv("FLOWSE_SCFOLD_LATE"))) {          // (the variable: test hook that forces this branch)
             // The fold was planned from PREDICTED shapes / types and the shortcut launch skipped; the Conv_1 that exists does not
@@ -521,12 +545,12 @@ struct Builder {
         }
         if (gf.done && gf.apply) {                       // h1 already is act(GroupNorm_1(Conv_0(.)))
             out = conv("conv1_3x3", h1, nullptr, mod.w_c1, mod.w_c1_b, -1, mod.out_ch, 9, resid, rs2, false, false, nullptr,
-                       false, -1, -1, nullptr, extra);
+                       false, -1, -1, nullptr, extra, nullptr, nullptr, false, bias_sc);
             release(h1);
         } else if (fusable(h1, 0)) {
             GnBuf g1 = gf.done ? gf.g : gn(h1, nullptr, mod.w_gn1_g, mod.w_gn1_b);
             out = conv(fold ? "conv1_3x3_gn_sc" : "conv1_3x3_gn", h1, nullptr, mod.w_c1, mod.w_c1_b, -1, mod.out_ch, 9, resid, rs2,
-                       false, false, &g1, true, mod.wq_c1, -1, nullptr, extra, nullptr, fold);
+                       false, false, &g1, true, mod.wq_c1, -1, nullptr, extra, nullptr, fold, false, bias_sc);
             gn_release(g1);
             release(h1);
             if (fold && (mod.up || mod.down)) release(xr);
@@ -534,7 +558,7 @@ struct Builder {
             Tn h2 = gn_norm(h1, nullptr, mod.w_gn1_g, mod.w_gn1_b, true);
             release(h1);
             out = conv("conv1_3x3", h2, nullptr, mod.w_c1, mod.w_c1_b, -1, mod.out_ch, 9, resid, rs2, false, false, nullptr,
-                       false, -1, -1, nullptr, extra);
+                       false, -1, -1, nullptr, extra, nullptr, nullptr, false, bias_sc);
             release(h2);
         }
         if (sp.valid) arena.release(sp.part_off);
