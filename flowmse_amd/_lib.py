@@ -17,6 +17,8 @@ LIB_PATH = os.environ.get("FLOWSE_LIB_PATH") or os.path.join(_HERE, "libflowse_h
 
 FLOWSE_MAX_LEVELS = 8
 FLOWSE_MAX_ATTN = 4
+FLOWSE_MAX_LANES = 4
+FLOWSE_BYTES_WEIGHTS, FLOWSE_BYTES_OWNED = 0, 1
 
 
 class FlowseError(RuntimeError):
@@ -45,6 +47,9 @@ SIGNATURES = {
     "flowse_device_count": (_i, []),
     "flowse_model_create": (_i, [C.POINTER(flowse_config), C.POINTER(_vp)]),
     "flowse_model_destroy": (None, [_vp]),
+    "flowse_model_view_create": (_i, [_vp, C.POINTER(_vp)]),
+    "flowse_model_device_bytes": (_i64, [_vp, _i]),
+    "flowse_model_weight_holders": (_i, [_vp]),
     "flowse_block_create": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "flowse_block_forward": (_i, [_vp, _fp, _i, _fp, _fp, _fp, _i, _i, _i, _vp]),
     "flowse_model_num_params": (_i, [_vp]),
@@ -58,6 +63,8 @@ SIGNATURES = {
     "flowse_prior_sample": (_i, [_vp, _vp, _f, _vp, _i64, _vp]),
     "flowse_euler_sample": (_i, [_vp, _vp, _vp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _vp]),
     "flowse_rk_sample": (_i, [_vp, _vp, _vp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _i, _vp]),
+    "flowse_rk_sample_multi": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _i,
+                                   C.POINTER(_f), C.POINTER(_f), _i, _i, _vp]),
     "flowse_rk45_sample": (_i, [_vp, _vp, _vp, _d, _d, _d, _d, _d, _d, _i64, _i, _i, _i, C.POINTER(_i64), C.POINTER(_i),
                                C.POINTER(_d), _i, C.POINTER(_i), _vp]),
     "flowse_model_graph_launches": (_i64, [_vp]),

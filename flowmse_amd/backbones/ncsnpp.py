@@ -112,6 +112,7 @@ class NCSNpp(nn.Module):
             p = nn.Parameter(torch.zeros(*shape), requires_grad=not name.endswith("all_modules.0.W"))
             _set_nested(self, name, p)
         self.reset_parameters()
+        self._views = []                       # view handles on this network's uploaded weights (views())
         self._uploaded_versions = None
         self._uploaded_device = None
         self._frozen_depth = 0
@@ -186,6 +187,7 @@ class NCSNpp(nn.Module):
             torch.cuda.set_device(device)
         blob = self.canonical_blob().contiguous()
         assert blob.numel() == self._blob_numel
+        self._drop_views()                     # the library refuses to repack a weight set that views still refer to
         _lib.check(_lib.lib.flowse_model_load_weights(self._handle, C.c_void_p(blob.data_ptr()), blob.numel()))
         self._uploaded_versions = [p._version for p in self._params_in_order()]
         self._uploaded_device = torch.cuda.current_device()
@@ -236,6 +238,7 @@ class NCSNpp(nn.Module):
             self._frozen_checked = False
 
     def _apply(self, fn, *a, **k):
+        self._drop_views()
         r = super()._apply(fn, *a, **k)
         self.__dict__.pop("_plist", None)
         self.mark_dirty()
@@ -273,6 +276,67 @@ class NCSNpp(nn.Module):
         return self.vf_call(x[:, 0:1], time_cond, x[:, 1:2], 0)
 
     TABLEAUS = {"euler": 0, "heun": 1, "rk4": 2}
+
+    # ------------------------------------------------------------------ views: several lanes on one set of weights
+    def _drop_views(self):
+        views, self._views = getattr(self, "_views", []), []
+        for v in views:
+            _lib.lib.flowse_model_destroy(v)
+
+    def views(self, k):
+        """The first ``k - 1`` view handles of this network (flowse_model_view_create): full handles that share the
+        uploaded weights and own their workspace, plans and stream.  Created on demand and kept until the weights are
+        uploaded again, the precision changes or the network is deleted -- do not keep them across such calls.  Plain
+        handle values (``ctypes.c_void_p``), not modules: ``state_dict`` / ``parameters()`` know nothing of them.
+        Must be called with the device of the uploaded weights current, after a call or ``reserve`` has uploaded them."""
+        if not 1 <= k <= _lib.FLOWSE_MAX_LANES:
+            raise ValueError(f"lanes must be 1..{_lib.FLOWSE_MAX_LANES}, got {k}")
+        if self._uploaded_versions is None:
+            raise RuntimeError("NCSNpp.views(): no weights uploaded yet")
+        while len(self._views) < k - 1:
+            h = C.c_void_p()
+            _lib.check(_lib.lib.flowse_model_view_create(self._handle, C.byref(h)))
+            self._views.append(h)
+        return self._views[:k - 1]
+
+    def rk_sample_multi(self, xs, ys, ts, dts, tableau="euler", lanes=2, lane_of=None):
+        """``rk_sample`` on several items in one C-ABI call, on ``lanes`` streams (flowse_rk_sample_multi in
+        include/flowse_hip.h): every ``xs[i]`` is integrated in place and ends bit-identical to
+        ``rk_sample(xs[i], ys[i], ts, dts, tableau)``.  Items may differ in batch size and length.  ``lane_of[i]`` (default
+        ``i % lanes``) is the lane of item i; items of one lane run in list order, lane 0 on the current stream.  A
+        throughput option for small batches: each item's own latency goes up."""
+        if len(xs) != len(ys) or not xs:
+            raise ValueError("xs and ys must be non-empty lists of the same length")
+        n = len(xs)
+        lanes = int(lanes)
+        if not 1 <= lanes <= _lib.FLOWSE_MAX_LANES:
+            raise ValueError(f"lanes must be 1..{_lib.FLOWSE_MAX_LANES}, got {lanes}")
+        lane_of = [i % lanes for i in range(n)] if lane_of is None else [int(v) for v in lane_of]
+        if len(lane_of) != n or any(not 0 <= v < lanes for v in lane_of):
+            raise ValueError(f"lane_of must name a lane in 0..{lanes - 1} for each of the {n} items")
+        dev = xs[0].device
+        for x, y in zip(xs, ys):
+            if x.dim() != 4:
+                raise ValueError(f"expected x of shape [B,1,F,T], got {tuple(x.shape)}")
+            self._check_io(x, y, _ShapeOnly((x.shape[0],)))
+            if not (x.is_contiguous() and y.is_contiguous()):
+                raise ValueError("x and y must be contiguous")
+            if x.device != dev or y.device != dev or x.shape[2] != xs[0].shape[2]:
+                raise ValueError("all items must live on one device and have the same number of frequency bins")
+        self._ensure_uploaded(dev)
+        N = len(ts)
+        ts_a = (C.c_float * N)(*[float(v) for v in ts])
+        dts_a = (C.c_float * N)(*[float(v) for v in dts])
+        with torch.cuda.device(dev):
+            handles = [self._handle] + self.views(max(lane_of) + 1)      # no view for a lane that holds no item
+            h_a = (C.c_void_p * n)(*[handles[v].value for v in lane_of])
+            x_a = (C.c_void_p * n)(*[x.data_ptr() for x in xs])
+            y_a = (C.c_void_p * n)(*[y.data_ptr() for y in ys])
+            B_a = (C.c_int * n)(*[x.shape[0] for x in xs])
+            T_a = (C.c_int * n)(*[x.shape[3] for x in xs])
+            _lib.check(_lib.lib.flowse_rk_sample_multi(h_a, n, x_a, y_a, B_a, T_a, xs[0].shape[2], ts_a, dts_a, N,
+                                                       self.TABLEAUS[tableau], _lib.current_stream()))
+        return xs
 
     def rk_sample(self, x, y, ts, dts, tableau="euler"):
         """In-place N-step fixed-step integration on x: one C-ABI call for the whole loop (flowse_rk_sample in
@@ -333,6 +397,7 @@ class NCSNpp(nn.Module):
 
     def set_precision(self, mode):
         """'fp32' (default, exact fp32 MFMA) | 'bf16x3' (split-bf16, fp32-class) | 'bf16' (BASELINE config 3)."""
+        self._drop_views()
         _lib.check(_lib.lib.flowse_model_set_precision(self._handle, self.PRECISIONS[mode]))
         self.precision = mode
         self.mark_dirty()
@@ -349,6 +414,7 @@ class NCSNpp(nn.Module):
         return json.loads(buf.value.decode())
 
     def load_state_dict(self, *a, **k):
+        self._drop_views()
         r = super().load_state_dict(*a, **k)
         self.__dict__.pop("_plist", None)
         self.mark_dirty()
@@ -356,6 +422,7 @@ class NCSNpp(nn.Module):
 
     def __del__(self):
         try:
+            self._drop_views()
             if getattr(self, "_handle", None):
                 _lib.lib.flowse_model_destroy(self._handle)
                 self._handle = None

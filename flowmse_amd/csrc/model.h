@@ -120,12 +120,11 @@ struct ProfAcc {
     double ms = 0.0, flops = 0.0, bytes = 0.0, issued = 0.0;
 };
 
-}  // namespace flowse
-
-using namespace flowse;
-
-struct flowse_model {
-    flowse_config cfg;
+// Everything that is derived from the weights: the device buffers and the host tables that index them.  One set may be
+// referred to by several handles (flowse_model_view_create); it is freed with its last holder.  Handles of one set are
+// used from one host thread at a time, so the count is a plain int.
+struct WeightSet {
+    int holders = 1;                       // live handles that refer to this set
     std::vector<Module> mods;
     std::vector<ParamInfo> params;
     int64_t blob_numel = 0;
@@ -159,13 +158,24 @@ struct flowse_model {
     float* d_wsm = nullptr;                // fragment-order copy of the conv weights with 32-aligned channel counts (conv_smallm_kernel)
     int64_t d_wsm_numel = 0;
     std::set<int64_t> wsm_offs;            // packed weight offsets (d_w) that have a copy at the SAME offset in d_wsm
+    int device = -1;                       // HIP device that owns every d_* buffer of the set and of its handles
+    bool storage16() const { return act_dt != DT_F32; }
+};
+
+}  // namespace flowse
+
+using namespace flowse;
+
+struct flowse_model {
+    flowse_config cfg;
+    WeightSet* wt = nullptr;               // never null; shared with the parent when is_view
+    bool is_view = false;                  // made by flowse_model_view_create: may not load weights or change the precision
     char* d_ws = nullptr;                  // activation workspace
     size_t d_ws_bytes = 0;
     float* d_ts = nullptr;                 // [N][B] solver times
     size_t d_ts_floats = 0;
     std::map<std::tuple<int, int, int>, Plan> plans;
     CallBlock* d_call = nullptr;           // per-call arguments of the boundary kernels, in device memory
-    int device = -1;                       // HIP device that owns every d_* buffer of this handle
     bool use_graph = false;                // FLOWSE_GRAPH=1: replay each shape's launch list as a hipGraph (slower, measured)
     // Callers on the NULL (legacy default) stream -- PyTorch's default stream IS the NULL stream -- cannot be captured;
     // their work runs on this internal stream instead, fenced against the NULL stream by events on both sides.
@@ -193,9 +203,9 @@ struct flowse_model {
     double prof_tot_flops = 0.0, prof_tot_issued = 0.0;    // over every launch between _begin and _end
     int64_t prof_tot_launches = 0;
 
-    float* W(int64_t off) const { return d_w + off; }
+    float* W(int64_t off) const { return wt->d_w + off; }
     float* A(size_t off) const { return reinterpret_cast<float*>(d_ws + off); }
-    bool storage16() const { return act_dt != DT_F32; }
+    bool storage16() const { return wt->storage16(); }
 };
 
 namespace flowse {

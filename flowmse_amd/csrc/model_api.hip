@@ -22,16 +22,16 @@ static void clear_plans(flowse_model* m) {
 static int check_device(const flowse_model* m) {
     int dev = 0;
     FLOWSE_HIP(hipGetDevice(&dev));
-    if (m->device >= 0 && dev != m->device) {
+    if (m->wt->device >= 0 && dev != m->wt->device) {
         set_error("model handle is bound to HIP device %d but device %d is current (reload the weights on the new "
-                  "device, or hipSetDevice back)", m->device, dev);
+                  "device, or hipSetDevice back)", m->wt->device, dev);
         return ERR_STATE;
     }
     return OK;
 }
 
 int get_plan(flowse_model* m, int B, int F, int T, Plan** out) {
-    if (!m->d_w) {
+    if (!m->wt->d_w) {
         set_error("weights not loaded: call flowse_model_load_weights first");
         return ERR_STATE;
     }
@@ -154,17 +154,21 @@ int exec_plan(flowse_model* m, Plan* p, hipStream_t s) {
     return OK;
 }
 
+// The handle's internal stream and its two fence events, made on first use.  The stream is non-blocking: a blocking one
+// would serialise against the NULL stream, which is where PyTorch's default stream puts the caller's work.
+static int ensure_stream(flowse_model* m) {
+    if (!m->gstream) FLOWSE_HIP(hipStreamCreateWithFlags(&m->gstream, hipStreamNonBlocking));
+    if (!m->ev_in) FLOWSE_HIP(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
+    if (!m->ev_out) FLOWSE_HIP(hipEventCreateWithFlags(&m->ev_out, hipEventDisableTiming));
+    return OK;
+}
 // Stream the work of one C-ABI call runs on.  A real stream: that stream.  The NULL stream: it cannot be captured, so
 // (unless graphs are off / a profile is being taken) the call moves to the handle's internal stream, which first waits
 // for everything the caller has enqueued on the NULL stream; leave_stream() makes the NULL stream wait for the call.
 int enter_stream(flowse_model* m, hipStream_t caller, hipStream_t* work) {
     *work = caller;
     if (caller != nullptr || !m->use_graph || m->prof_mode != -1) return OK;
-    if (!m->gstream) {
-        FLOWSE_HIP(hipStreamCreateWithFlags(&m->gstream, hipStreamNonBlocking));
-        FLOWSE_HIP(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
-        FLOWSE_HIP(hipEventCreateWithFlags(&m->ev_out, hipEventDisableTiming));
-    }
+    if (const int rc = ensure_stream(m)) return rc;
     FLOWSE_HIP(hipEventRecord(m->ev_in, nullptr));
     FLOWSE_HIP(hipStreamWaitEvent(m->gstream, m->ev_in, 0));
     *work = m->gstream;
@@ -190,34 +194,17 @@ int reserve_times(flowse_model* m, size_t need) {
     return OK;
 }
 
-static void free_device_state(flowse_model* m) {
-    int cur = 0;
-    const bool sw = m->device >= 0 && hipGetDevice(&cur) == hipSuccess && cur != m->device;
-    if (sw) (void)hipSetDevice(m->device);
-    if (m->device >= 0) (void)hipDeviceSynchronize();
+// The buffers only this handle holds: workspace, plans, time table, RK scratch, CallBlock, stream, events, profiler.
+// Called with the set's device current and idle.
+static void free_owned_state(flowse_model* m) {
     clear_plans(m);
-    if (m->d_w) (void)hipFree(m->d_w);
     if (m->d_ws) (void)hipFree(m->d_ws);
     if (m->d_ts) (void)hipFree(m->d_ts);
-    if (m->d_wq) (void)hipFree(m->d_wq);
-    if (m->d_w16) (void)hipFree(m->d_w16);
-    if (m->d_wfrag) (void)hipFree(m->d_wfrag);
-    if (m->d_wino) (void)hipFree(m->d_wino);
-    if (m->d_wino2) (void)hipFree(m->d_wino2);
-    m->d_wino2 = nullptr;
-    m->d_wino2_numel = 0;
-    if (m->d_wsm) (void)hipFree(m->d_wsm);
-    if (m->d_wsm16) (void)hipFree(m->d_wsm16);
-    m->d_wsm16 = nullptr;
-    m->d_wsm = nullptr;
-    m->d_wsm_numel = 0;
     if (m->d_call) (void)hipFree(m->d_call);
     if (m->d_rk) (void)hipFree(m->d_rk);
-    m->d_rk = nullptr;
-    m->d_rk_floats = 0;
     if (m->d_rk45) (void)hipFree(m->d_rk45);
-    m->d_rk45 = nullptr;
-    m->d_rk45_bytes = 0;
+    m->d_ws = nullptr; m->d_ts = nullptr; m->d_call = nullptr; m->d_rk = nullptr; m->d_rk45 = nullptr;
+    m->d_ws_bytes = m->d_ts_floats = m->d_rk_floats = m->d_rk45_bytes = 0;
     if (m->gstream) (void)hipStreamDestroy(m->gstream);
     if (m->ev_in) (void)hipEventDestroy(m->ev_in);
     if (m->ev_out) (void)hipEventDestroy(m->ev_out);
@@ -226,14 +213,125 @@ static void free_device_state(flowse_model* m) {
     for (hipEvent_t e : m->prof_pool) (void)hipEventDestroy(e);
     m->prof_pool.clear();
     m->prof_used = 0;
-    m->d_w = nullptr; m->d_ws = nullptr; m->d_ts = nullptr; m->d_wino = nullptr; m->d_call = nullptr;
-    m->d_wq = nullptr;
-    m->d_w16 = nullptr;
-    m->d_wfrag = nullptr;
-    m->d_w_numel = m->d_wq_numel = m->d_wino_numel = m->d_w16_numel = m->d_wfrag_numel = 0;
-    m->d_ws_bytes = m->d_ts_floats = 0;
-    m->device = -1;
+}
+
+// Every device buffer of a weight set; the host tables stay (the next upload rewrites them).
+static void free_weight_buffers(WeightSet* w) {
+    void* bufs[] = {w->d_w, w->d_wq, w->d_w16, w->d_wfrag, w->d_wino, w->d_wino2, w->d_wsm, w->d_wsm16};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    w->d_w = w->d_wino = w->d_wino2 = w->d_wsm = w->d_wsm16 = nullptr;
+    w->d_wq = w->d_w16 = w->d_wfrag = nullptr;
+    w->d_w_numel = w->d_wq_numel = w->d_w16_numel = w->d_wfrag_numel = 0;
+    w->d_wino_numel = w->d_wino2_numel = w->d_wsm_numel = 0;
+    w->device = -1;
+}
+
+// Frees what the handle owns and, when it is the set's only holder, the weight buffers too (the handle keeps its, now
+// empty, set).  A handle whose set has other holders only lets go of its own buffers.
+static void free_device_state(flowse_model* m) {
+    WeightSet* w = m->wt;
+    int cur = 0;
+    const bool sw = w->device >= 0 && hipGetDevice(&cur) == hipSuccess && cur != w->device;
+    if (sw) (void)hipSetDevice(w->device);
+    if (w->device >= 0) (void)hipDeviceSynchronize();
+    free_owned_state(m);
+    if (w->holders == 1) free_weight_buffers(w);
     if (sw) (void)hipSetDevice(cur);
+}
+
+// ---------------------------------------------------------------------------------- fixed-step RK, one evaluation at a time
+// The network evaluations of one solve over the reference's grid.  A step that ends at (or numerically below) t = 0 is
+// the reference's own Euler update: the field divides by t and embeds log t, so no stage may be evaluated at the end
+// point of such a step (it is the LAST step of the reference's grid, whose length equals the last grid time,
+// sampling/__init__.py:53).
+struct RkGrid {
+    int stages;
+    std::vector<float> nfe_t;               // time of every network evaluation, in order
+    struct Eval { int step, stage, of; float h; };
+    std::vector<Eval> evals;
+    RkGrid(const float* ts, const float* dts, int N, int tableau)
+        : stages(tableau == FLOWSE_TABLEAU_RK4 ? 4 : tableau == FLOWSE_TABLEAU_HEUN ? 2 : 1) {
+        for (int i = 0; i < N; ++i) {
+            const float t = ts[i], h = dts[i];
+            const bool lands = (double)t - (double)h <= 1e-6 * std::max(1.0, std::fabs((double)t));
+            const int st = lands ? 1 : stages;
+            const float dt = -h;
+            nfe_t.push_back(t);
+            if (st == 2) nfe_t.push_back(t + dt);
+            if (st == 4) {
+                const float th = t + 0.5f * dt;
+                nfe_t.push_back(th);
+                nfe_t.push_back(th);
+                nfe_t.push_back(t + dt);
+            }
+            for (int j = 0; j < st; ++j) evals.push_back(Eval{i, j, st, h});
+        }
+    }
+};
+
+// time table and RK scratch of one [B,1,F,T] solve on handle m (growth synchronises the device)
+static int reserve_rk(flowse_model* m, const RkGrid& g, int B, int F, int T) {
+    const int rc = reserve_times(m, g.nfe_t.size() * (size_t)B);
+    if (rc != OK) return rc;
+    const size_t state = (size_t)2 * B * F * T;                 // floats of one complex64 [B,1,F,T] tensor
+    if (g.stages > 1 && m->d_rk_floats < 2 * state) {
+        FLOWSE_HIP(hipDeviceSynchronize());
+        if (m->d_rk) FLOWSE_HIP(hipFree(m->d_rk));
+        m->d_rk = nullptr;
+        m->d_rk_floats = 0;
+        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_rk), 2 * state * sizeof(float)));
+        m->d_rk_floats = 2 * state;
+    }
+    return OK;
+}
+
+struct RkRun {
+    flowse_model* m = nullptr;
+    Plan* p = nullptr;
+    float* x = nullptr;
+    const float* y = nullptr;
+    int B = 0, F = 0, T = 0;
+    size_t k = 0;                                                // index of the next network evaluation
+    bool done(const RkGrid& g) const { return k == g.evals.size(); }
+    // Enqueues evaluation k (before the first one, the table of times) on s.  may_graph: through exec_plan, which may
+    // replay a captured graph; otherwise always plain launches.
+    int issue(const RkGrid& g, hipStream_t s, bool may_graph) {
+        if (k == 0) {
+            // vec_t = ones(B) * t (sampling/__init__.py:55), written on the device by a kernel that receives the times by value
+            const int rc = launch_fill_times(m->d_ts, g.nfe_t.data(), (int)g.nfe_t.size(), B, s);
+            if (rc != OK) return rc;
+        }
+        const size_t state = (size_t)2 * B * F * T;
+        float* const xs = m->d_rk;                                   // stage input
+        float* const acc = m->d_rk ? m->d_rk + state : nullptr;      // x + sum_j b_j h v_j so far
+        const RkGrid::Eval& e = g.evals[k];
+        const float* const t = m->d_ts + k * B;
+        const float h = e.h;
+        CallBlock cb{x, y, t, x, 2, h};                              // single-stage step: x += h v(x, t)
+        auto stage = [&](const float* in, float* out, const float* acc_in, float* acc_out, float a, float b) {
+            cb = CallBlock{in, y, t, out, 3, 0.f, x, acc_in, acc_out, a, b};
+        };
+        if (e.of == 2) {
+            if (e.stage == 0) stage(x, xs, x, acc, h, 0.5f * h);
+            else stage(xs, nullptr, acc, x, 0.f, 0.5f * h);
+        } else if (e.of == 4) {
+            if (e.stage == 0) stage(x, xs, x, acc, 0.5f * h, h / 6.0f);
+            else if (e.stage == 1) stage(xs, xs, acc, acc, 0.5f * h, h / 3.0f);
+            else if (e.stage == 2) stage(xs, xs, acc, acc, h, h / 3.0f);
+            else stage(xs, nullptr, acc, x, 0.f, h / 6.0f);
+        }
+        ++k;
+        const int rc = launch_set_call(m->d_call, cb, s);
+        if (rc != OK) return rc;
+        return may_graph ? exec_plan(m, p, s) : run_plan(m, p, s);
+    }
+};
+
+static bool weights_shared(const flowse_model* m, const char* what) {
+    if (!m->is_view && m->wt->holders == 1) return false;
+    set_error("%s: the weight set is shared by %d handles; destroy the views first", what, m->wt->holders);
+    return true;
 }
 
 }  // namespace flowse
@@ -257,6 +355,7 @@ int flowse_model_create(const flowse_config* cfg, flowse_model** out) {
         return ERR_ARG;
     }
     flowse_model* m = new flowse_model();
+    m->wt = new WeightSet();
     m->cfg = *cfg;
     // hipGraph replay of the launch list is opt-in (FLOWSE_GRAPH=1): measured on MI355X / ROCm 7.2 a replayed graph of
     // ~400 short kernel nodes runs 5 % SLOWER than the same launches issued eagerly from the C loop at [1,1,256,256]
@@ -265,6 +364,7 @@ int flowse_model_create(const flowse_config* cfg, flowse_model** out) {
     m->use_graph = getenv("FLOWSE_GRAPH") != nullptr;
     const int rc = build_structure(m);
     if (rc != OK) {
+        delete m->wt;
         delete m;
         return rc;
     }
@@ -275,6 +375,7 @@ int flowse_model_create(const flowse_config* cfg, flowse_model** out) {
 void flowse_model_destroy(flowse_model* m) {
     if (!m) return;
     free_device_state(m);
+    if (--m->wt->holders == 0) delete m->wt;
     delete m;
 }
 
@@ -287,10 +388,11 @@ int flowse_block_create(int kind, int in_ch, int out_ch, int up, int down, int t
         return ERR_ARG;
     }
     flowse_model* m = new flowse_model();
+    m->wt = new WeightSet();
     memset(&m->cfg, 0, sizeof(m->cfg));
     m->use_graph = false;
     m->block_kind = kind;
-    m->temb_dim = temb_dim;
+    m->wt->temb_dim = temb_dim;
     if (kind == FLOWSE_BLOCK_RESNET) add_module(m, resblock_module(in_ch, out_ch, up != 0, down != 0));
     else add_module(m, simple_module(kind == FLOWSE_BLOCK_ATTN ? M_ATTN : M_COMBINE, in_ch, out_ch));
     *out = m;
@@ -304,12 +406,12 @@ int flowse_block_forward(flowse_model* m, const float* in1, int C1, const float*
         set_error("flowse_block_forward: bad argument (not a block handle, or a required pointer is null)");
         return ERR_ARG;
     }
-    if (!m->d_w) {
+    if (!m->wt->d_w) {
         set_error("weights not loaded: call flowse_model_load_weights first");
         return ERR_STATE;
     }
     if (const int rc = check_device(m)) return rc;
-    if (!in2 && m->block_kind == FLOWSE_BLOCK_RESNET) C1 = m->mods[0].in_ch;
+    if (!in2 && m->block_kind == FLOWSE_BLOCK_RESNET) C1 = m->wt->mods[0].in_ch;
     auto key = std::make_tuple(B, H, W, C1);
     auto it = m->block_plans.find(key);
     if (it == m->block_plans.end()) {
@@ -334,17 +436,17 @@ int flowse_block_forward(flowse_model* m, const float* in1, int C1, const float*
     return run_plan(m, p, static_cast<hipStream_t>(stream));
 }
 
-int flowse_model_num_params(const flowse_model* m) { return m ? (int)m->params.size() : 0; }
-int flowse_model_num_modules(const flowse_model* m) { return m ? (int)m->mods.size() : 0; }
-int64_t flowse_model_blob_numel(const flowse_model* m) { return m ? m->blob_numel : 0; }
+int flowse_model_num_params(const flowse_model* m) { return m ? (int)m->wt->params.size() : 0; }
+int flowse_model_num_modules(const flowse_model* m) { return m ? (int)m->wt->mods.size() : 0; }
+int64_t flowse_model_blob_numel(const flowse_model* m) { return m ? m->wt->blob_numel : 0; }
 
 int flowse_model_param_info(const flowse_model* m, int index, char* name, int name_cap, int64_t shape[4], int* ndim,
                             int64_t* offset) {
-    if (!m || index < 0 || index >= (int)m->params.size()) {
+    if (!m || index < 0 || index >= (int)m->wt->params.size()) {
         set_error("flowse_model_param_info: bad index %d", index);
         return ERR_ARG;
     }
-    const ParamInfo& p = m->params[index];
+    const ParamInfo& p = m->wt->params[index];
     if (name && name_cap > 0) {
         strncpy(name, p.name.c_str(), name_cap - 1);
         name[name_cap - 1] = 0;
@@ -361,22 +463,23 @@ int flowse_model_set_precision(flowse_model* m, int mode) {
         set_error("flowse_model_set_precision: mode must be 0 (fp32), 1 (bf16x3), 2 (bf16) or 3 (fp16)");
         return ERR_ARG;
     }
-    if (mode != m->precision) {
-        if (m->d_w) {            // weights must be re-uploaded so that the operand planes match the mode
+    if (mode != m->wt->precision) {
+        if (weights_shared(m, "flowse_model_set_precision")) return ERR_STATE;
+        if (m->wt->d_w) {            // weights must be re-uploaded so that the operand planes match the mode
             if (const int rc = check_device(m)) return rc;      // before any state changes: a failure leaves the handle as is
             FLOWSE_HIP(hipDeviceSynchronize());
             clear_plans(m);
-            FLOWSE_HIP(hipFree(m->d_w));
-            m->d_w = nullptr;
-            m->d_w_numel = 0;
-            if (m->d_w16) {      // the 16-bit twin belongs to the mode that is being left
-                FLOWSE_HIP(hipFree(m->d_w16));
-                m->d_w16 = nullptr;
-                m->d_w16_numel = 0;
+            FLOWSE_HIP(hipFree(m->wt->d_w));
+            m->wt->d_w = nullptr;
+            m->wt->d_w_numel = 0;
+            if (m->wt->d_w16) {      // the 16-bit twin belongs to the mode that is being left
+                FLOWSE_HIP(hipFree(m->wt->d_w16));
+                m->wt->d_w16 = nullptr;
+                m->wt->d_w16_numel = 0;
             }
         }
-        m->precision = mode;
-        m->act_dt = DT_F32;      // recomputed by the next flowse_model_load_weights
+        m->wt->precision = mode;
+        m->wt->act_dt = DT_F32;      // recomputed by the next flowse_model_load_weights
         clear_plans(m);
     }
     return OK;
@@ -387,166 +490,167 @@ int flowse_model_load_weights(flowse_model* m, const float* blob, int64_t numel)
         set_error("flowse_model_load_weights: null argument");
         return ERR_ARG;
     }
-    if (numel != m->blob_numel) {
+    if (numel != m->wt->blob_numel) {
         set_error("flowse_model_load_weights: blob has %lld floats, model needs %lld", (long long)numel,
-                  (long long)m->blob_numel);
+                  (long long)m->wt->blob_numel);
         return ERR_ARG;
     }
+    if (weights_shared(m, "flowse_model_load_weights")) return ERR_STATE;      // before the packer rewrites shared tables
     Packer pk;
     const int rc = pack_weights(m, blob, pk);
     if (rc != OK) return rc;
     int dev = 0;
     FLOWSE_HIP(hipGetDevice(&dev));
-    if (m->device >= 0 && m->device != dev) free_device_state(m);      // the handle moves to the current device
-    m->device = dev;
+    if (m->wt->device >= 0 && m->wt->device != dev) free_device_state(m);      // the handle moves to the current device
+    m->wt->device = dev;
     FLOWSE_HIP(hipDeviceSynchronize());
     clear_plans(m);          // closures captured weight offsets of the previous packing
     if (!m->d_call) FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_call), sizeof(CallBlock)));
-    if (m->d_w && m->d_w_numel < (int64_t)pk.host.size()) {
-        FLOWSE_HIP(hipFree(m->d_w));
-        m->d_w = nullptr;
+    if (m->wt->d_w && m->wt->d_w_numel < (int64_t)pk.host.size()) {
+        FLOWSE_HIP(hipFree(m->wt->d_w));
+        m->wt->d_w = nullptr;
     }
-    if (!m->d_w) {
-        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_w), pk.host.size() * sizeof(float)));
-        m->d_w_numel = (int64_t)pk.host.size();
+    if (!m->wt->d_w) {
+        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_w), pk.host.size() * sizeof(float)));
+        m->wt->d_w_numel = (int64_t)pk.host.size();
     }
-    FLOWSE_HIP(hipMemcpy(m->d_w, pk.host.data(), pk.host.size() * sizeof(float), hipMemcpyHostToDevice));
-    m->act_dt = storage_type_for(m);
+    FLOWSE_HIP(hipMemcpy(m->wt->d_w, pk.host.data(), pk.host.size() * sizeof(float), hipMemcpyHostToDevice));
+    m->wt->act_dt = storage_type_for(m);
     if (m->storage16()) {                    // elementwise 16-bit twin of the packed blob (conv weights keep their offsets)
         const int64_t n16 = ((int64_t)pk.host.size() + 3) & ~(int64_t)3;
-        if (m->d_w16 && m->d_w16_numel < n16) {
-            FLOWSE_HIP(hipFree(m->d_w16));
-            m->d_w16 = nullptr;
+        if (m->wt->d_w16 && m->wt->d_w16_numel < n16) {
+            FLOWSE_HIP(hipFree(m->wt->d_w16));
+            m->wt->d_w16 = nullptr;
         }
-        if (!m->d_w16) {
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_w16), n16 * sizeof(uint16_t)));
-            m->d_w16_numel = n16;
+        if (!m->wt->d_w16) {
+            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_w16), n16 * sizeof(uint16_t)));
+            m->wt->d_w16_numel = n16;
         }
-        const int crc = launch_convert(m->d_w, DT_F32, m->d_w16, m->act_dt, (int64_t)pk.host.size() & ~(int64_t)3, nullptr);
+        const int crc = launch_convert(m->wt->d_w, DT_F32, m->wt->d_w16, m->wt->act_dt, (int64_t)pk.host.size() & ~(int64_t)3, nullptr);
         if (crc != OK) return crc;
         // fragment-order copies for the producer / consumer 3x3 kernel, same offsets as in d_w16
-        m->frag_offs.clear();
-        if (m->d_wfrag && m->d_wfrag_numel < n16) {
-            FLOWSE_HIP(hipFree(m->d_wfrag));
-            m->d_wfrag = nullptr;
+        m->wt->frag_offs.clear();
+        if (m->wt->d_wfrag && m->wt->d_wfrag_numel < n16) {
+            FLOWSE_HIP(hipFree(m->wt->d_wfrag));
+            m->wt->d_wfrag = nullptr;
         }
-        if (!m->d_wfrag) {
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_wfrag), n16 * sizeof(uint16_t)));
-            m->d_wfrag_numel = n16;
+        if (!m->wt->d_wfrag) {
+            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wfrag), n16 * sizeof(uint16_t)));
+            m->wt->d_wfrag_numel = n16;
         }
         for (auto& r : pk.wino) {
             if ((r.Cout % 128) != 0 || (int64_t)r.Cout * 9 * r.Cin * 2 >= (1LL << 31)) continue;
-            const int frc = launch_pc16_weights(m->d_w16 + r.off, r.Cout, r.Cin, m->d_wfrag + r.off, nullptr);
+            const int frc = launch_pc16_weights(m->wt->d_w16 + r.off, r.Cout, r.Cin, m->wt->d_wfrag + r.off, nullptr);
             if (frc != OK) return frc;
-            m->frag_offs.insert(r.off);
+            m->wt->frag_offs.insert(r.off);
         }
         // ... and for every other conv with 32-aligned channel counts (1x1 shortcuts, attention projections, 3x3 with
         // Cout % 128 != 0): the 16-bit small-image kernel reads the same layout
         if (conv16_smallm_ok(1, 4, 4, 32, 0, 32, 1)) {
             for (auto& r : pk.smallm) {
-                if (m->frag_offs.count(r.off) || (int64_t)r.Cout * r.taps * r.Cin * 2 >= (1LL << 31)) continue;
-                const int frc = launch_pc16_weights(m->d_w16 + r.off, r.Cout, r.Cin, m->d_wfrag + r.off, nullptr, r.taps);
+                if (m->wt->frag_offs.count(r.off) || (int64_t)r.Cout * r.taps * r.Cin * 2 >= (1LL << 31)) continue;
+                const int frc = launch_pc16_weights(m->wt->d_w16 + r.off, r.Cout, r.Cin, m->wt->d_wfrag + r.off, nullptr, r.taps);
                 if (frc != OK) return frc;
-                m->frag_offs.insert(r.off);
+                m->wt->frag_offs.insert(r.off);
             }
         }
         pk.wino.clear();                     // no fp32 Winograd kernels run on 16-bit activations
     }
     // F(4,3) Winograd weights, derived on the device from the packed fp32 weights just uploaded
-    m->wino_of.clear();
+    m->wt->wino_of.clear();
     int64_t wino_total = 0;
     for (auto& r : pk.wino) {
-        m->wino_of[r.off] = wino_total;
+        m->wt->wino_of[r.off] = wino_total;
         wino_total += (conv_wino_numel(r.Cout, r.Cin) + 63) & ~(int64_t)63;
     }
-    if (m->d_wino && m->d_wino_numel < wino_total) {
-        FLOWSE_HIP(hipFree(m->d_wino));
-        m->d_wino = nullptr;
+    if (m->wt->d_wino && m->wt->d_wino_numel < wino_total) {
+        FLOWSE_HIP(hipFree(m->wt->d_wino));
+        m->wt->d_wino = nullptr;
     }
-    if (!m->d_wino && wino_total > 0) {
-        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_wino), wino_total * sizeof(float)));
-        m->d_wino_numel = wino_total;
+    if (!m->wt->d_wino && wino_total > 0) {
+        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wino), wino_total * sizeof(float)));
+        m->wt->d_wino_numel = wino_total;
     }
     for (auto& r : pk.wino) {
-        float* dst = m->d_wino + m->wino_of[r.off];
-        const int wrc = launch_f43_weights(m->d_w + r.off, r.Cout, r.Cin, dst, nullptr);
+        float* dst = m->wt->d_wino + m->wt->wino_of[r.off];
+        const int wrc = launch_f43_weights(m->wt->d_w + r.off, r.Cout, r.Cin, dst, nullptr);
         if (wrc != OK) return wrc;
     }
     // fragment-order copies for the small-M kernel (fp32 activations only), at the same offsets as in d_w
-    m->wsm_offs.clear();
+    m->wt->wsm_offs.clear();
     if (!m->storage16() && !pk.smallm.empty() && conv_smallm_ok(1, 4, 4, 32, 0, 32, 1)) {
         const int64_t nw = (int64_t)pk.host.size();
-        if (m->d_wsm && m->d_wsm_numel < nw) {
-            FLOWSE_HIP(hipFree(m->d_wsm));
-            FLOWSE_HIP(hipFree(m->d_wsm16));
-            m->d_wsm = m->d_wsm16 = nullptr;
+        if (m->wt->d_wsm && m->wt->d_wsm_numel < nw) {
+            FLOWSE_HIP(hipFree(m->wt->d_wsm));
+            FLOWSE_HIP(hipFree(m->wt->d_wsm16));
+            m->wt->d_wsm = m->wt->d_wsm16 = nullptr;
         }
-        if (!m->d_wsm) {
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_wsm), nw * sizeof(float)));
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_wsm16), nw * sizeof(float)));
-            m->d_wsm_numel = nw;
+        if (!m->wt->d_wsm) {
+            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wsm), nw * sizeof(float)));
+            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wsm16), nw * sizeof(float)));
+            m->wt->d_wsm_numel = nw;
         }
         for (auto& r : pk.smallm) {
             if ((int64_t)r.Cout * r.taps * r.Cin * 4 >= (1LL << 31)) continue;
-            int src = launch_smallm_weights(m->d_w + r.off, r.Cout, r.taps, r.Cin, m->d_wsm + r.off, nullptr);
-            if (src == OK) src = launch_smallm_weights(m->d_w + r.off, r.Cout, r.taps, r.Cin, m->d_wsm16 + r.off, nullptr, true);
+            int src = launch_smallm_weights(m->wt->d_w + r.off, r.Cout, r.taps, r.Cin, m->wt->d_wsm + r.off, nullptr);
+            if (src == OK) src = launch_smallm_weights(m->wt->d_w + r.off, r.Cout, r.taps, r.Cin, m->wt->d_wsm16 + r.off, nullptr, true);
             if (src != OK) return src;
-            m->wsm_offs.insert(r.off);
+            m->wt->wsm_offs.insert(r.off);
         }
     }
     // F(4,3) x F(2,3) weights of the same convs (the two-dimensional kernel takes the large images)
-    m->wino2_of.clear();
+    m->wt->wino2_of.clear();
     if (conv_w2d_enabled()) {
         int64_t w2_total = 0;
         for (auto& r : pk.wino) {
             if ((int64_t)r.Cout * 24 * r.Cin * 4 >= (1LL << 31)) continue;
-            m->wino2_of[r.off] = w2_total;
+            m->wt->wino2_of[r.off] = w2_total;
             w2_total += (conv_w2d_numel(r.Cout, r.Cin) + 63) & ~(int64_t)63;
         }
-        if (m->d_wino2 && m->d_wino2_numel < w2_total) {
-            FLOWSE_HIP(hipFree(m->d_wino2));
-            m->d_wino2 = nullptr;
+        if (m->wt->d_wino2 && m->wt->d_wino2_numel < w2_total) {
+            FLOWSE_HIP(hipFree(m->wt->d_wino2));
+            m->wt->d_wino2 = nullptr;
         }
-        if (!m->d_wino2 && w2_total > 0) {
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_wino2), w2_total * sizeof(float)));
-            m->d_wino2_numel = w2_total;
+        if (!m->wt->d_wino2 && w2_total > 0) {
+            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wino2), w2_total * sizeof(float)));
+            m->wt->d_wino2_numel = w2_total;
         }
         for (auto& r : pk.wino) {
-            const auto it = m->wino2_of.find(r.off);
-            if (it == m->wino2_of.end()) continue;
-            const int wrc = launch_w2d_weights(m->d_w + r.off, r.Cout, r.Cin, m->d_wino2 + it->second, nullptr);
+            const auto it = m->wt->wino2_of.find(r.off);
+            if (it == m->wt->wino2_of.end()) continue;
+            const int wrc = launch_w2d_weights(m->wt->d_w + r.off, r.Cout, r.Cin, m->wt->d_wino2 + it->second, nullptr);
             if (wrc != OK) return wrc;
         }
     }
     FLOWSE_HIP(hipDeviceSynchronize());
     // optional bf16 planes for the 3x3 ResBlock convolutions the halo kernel can take
-    for (auto& mod : m->mods) mod.wq_c0 = mod.wq_c1 = -1;
-    if (m->precision != 0 && !m->storage16()) {
-        const int terms = m->precision == 1 ? 3 : 1;
+    for (auto& mod : m->wt->mods) mod.wq_c0 = mod.wq_c1 = -1;
+    if (m->wt->precision != 0 && !m->storage16()) {
+        const int terms = m->wt->precision == 1 ? 3 : 1;
         std::vector<uint16_t> q;
-        for (auto& mod : m->mods) {
+        for (auto& mod : m->wt->mods) {
             if (mod.kind != M_RESBLOCK || (mod.out_ch % 128) != 0) continue;
             if ((mod.in_ch % 32) == 0) {
                 mod.wq_c0 = (int64_t)q.size();
                 q.resize(q.size() + conv_bf16_numel(mod.out_ch, mod.in_ch, terms));
-                pack_conv_bf16(blob + m->params[mod.p0 + 2].offset, mod.out_ch, mod.in_ch, terms, q.data() + mod.wq_c0,
-                               m->precision == 3);
+                pack_conv_bf16(blob + m->wt->params[mod.p0 + 2].offset, mod.out_ch, mod.in_ch, terms, q.data() + mod.wq_c0,
+                               m->wt->precision == 3);
             }
             mod.wq_c1 = (int64_t)q.size();
             q.resize(q.size() + conv_bf16_numel(mod.out_ch, mod.out_ch, terms));
-            pack_conv_bf16(blob + m->params[mod.p0 + 8].offset, mod.out_ch, mod.out_ch, terms, q.data() + mod.wq_c1,
-                           m->precision == 3);
+            pack_conv_bf16(blob + m->wt->params[mod.p0 + 8].offset, mod.out_ch, mod.out_ch, terms, q.data() + mod.wq_c1,
+                           m->wt->precision == 3);
         }
-        if (m->d_wq && m->d_wq_numel < (int64_t)q.size()) {
-            FLOWSE_HIP(hipFree(m->d_wq));
-            m->d_wq = nullptr;
+        if (m->wt->d_wq && m->wt->d_wq_numel < (int64_t)q.size()) {
+            FLOWSE_HIP(hipFree(m->wt->d_wq));
+            m->wt->d_wq = nullptr;
         }
-        if (!m->d_wq && !q.empty()) {
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_wq), q.size() * sizeof(uint16_t)));
-            m->d_wq_numel = (int64_t)q.size();
+        if (!m->wt->d_wq && !q.empty()) {
+            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wq), q.size() * sizeof(uint16_t)));
+            m->wt->d_wq_numel = (int64_t)q.size();
         }
         if (!q.empty())
-            FLOWSE_HIP(hipMemcpy(m->d_wq, q.data(), q.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            FLOWSE_HIP(hipMemcpy(m->wt->d_wq, q.data(), q.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     }
     return OK;
 }
@@ -614,76 +718,150 @@ int flowse_rk_sample(flowse_model* m, void* x_inout, const void* y, const float*
         set_error("flowse_rk_sample / flowse_euler_sample: bad argument");
         return ERR_ARG;
     }
-    Plan* p = nullptr;
-    int rc = get_plan(m, B, F, T, &p);
+    RkRun run;
+    run.m = m;
+    run.x = static_cast<float*>(x_inout);
+    run.y = static_cast<const float*>(y);
+    run.B = B; run.F = F; run.T = T;
+    int rc = get_plan(m, B, F, T, &run.p);
     if (rc != OK) return rc;
-    const int stages = tableau == FLOWSE_TABLEAU_RK4 ? 4 : tableau == FLOWSE_TABLEAU_HEUN ? 2 : 1;
-    // a step that ends at (or numerically below) t = 0 is the reference's own Euler update: the field divides by t and
-    // embeds log t, so no stage may be evaluated at the end point of such a step (it is the LAST step of the reference's
-    // grid, whose length equals the last grid time, sampling/__init__.py:53)
-    std::vector<float> nfe_t;
-    std::vector<int> step_stages(N);
-    for (int i = 0; i < N; ++i) {
-        const float t = ts[i], h = dts[i];
-        const bool lands = (double)t - (double)h <= 1e-6 * std::max(1.0, std::fabs((double)t));
-        const int st = lands ? 1 : stages;
-        step_stages[i] = st;
-        const float dt = -h;
-        nfe_t.push_back(t);
-        if (st == 2) nfe_t.push_back(t + dt);
-        if (st == 4) {
-            const float th = t + 0.5f * dt;
-            nfe_t.push_back(th);
-            nfe_t.push_back(th);
-            nfe_t.push_back(t + dt);
-        }
-    }
-    rc = reserve_times(m, nfe_t.size() * (size_t)B);
+    const RkGrid grid(ts, dts, N, tableau);
+    rc = reserve_rk(m, grid, B, F, T);
     if (rc != OK) return rc;
-    const size_t state = (size_t)2 * B * F * T;                 // floats of one complex64 [B,1,F,T] tensor
-    if (stages > 1 && m->d_rk_floats < 2 * state) {
-        FLOWSE_HIP(hipDeviceSynchronize());
-        if (m->d_rk) FLOWSE_HIP(hipFree(m->d_rk));
-        m->d_rk = nullptr;
-        m->d_rk_floats = 0;
-        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_rk), 2 * state * sizeof(float)));
-        m->d_rk_floats = 2 * state;
-    }
     hipStream_t caller = static_cast<hipStream_t>(stream), s = nullptr;
     rc = enter_stream(m, caller, &s);
     if (rc != OK) return rc;
-    // vec_t = ones(B) * t (sampling/__init__.py:55), written on the device by a kernel that receives the times by value
-    rc = launch_fill_times(m->d_ts, nfe_t.data(), (int)nfe_t.size(), B, s);
-    float* const x = static_cast<float*>(x_inout);
-    const float* const yy = static_cast<const float*>(y);
-    float* const xs = m->d_rk;                                   // stage input
-    float* const acc = m->d_rk ? m->d_rk + state : nullptr;      // x + sum_j b_j h v_j so far
-    size_t k = 0;                                                // index of the next network evaluation
-    auto stage = [&](const float* in, float* out, const float* acc_in, float* acc_out, float a, float b) {
-        CallBlock cb{in, yy, m->d_ts + (k++) * B, out, 3, 0.f, x, acc_in, acc_out, a, b};
-        int r = launch_set_call(m->d_call, cb, s);
-        if (r == OK) r = exec_plan(m, p, s);
-        return r;
-    };
-    for (int i = 0; i < N && rc == OK; ++i) {
-        const float h = dts[i];
-        if (step_stages[i] == 1) {
-            CallBlock cb{x, yy, m->d_ts + (k++) * B, x, 2, h};
-            rc = launch_set_call(m->d_call, cb, s);
-            if (rc == OK) rc = exec_plan(m, p, s);
-        } else if (step_stages[i] == 2) {
-            rc = stage(x, xs, x, acc, h, 0.5f * h);
-            if (rc == OK) rc = stage(xs, nullptr, acc, x, 0.f, 0.5f * h);
-        } else {
-            rc = stage(x, xs, x, acc, 0.5f * h, h / 6.0f);
-            if (rc == OK) rc = stage(xs, xs, acc, acc, 0.5f * h, h / 3.0f);
-            if (rc == OK) rc = stage(xs, xs, acc, acc, h, h / 3.0f);
-            if (rc == OK) rc = stage(xs, nullptr, acc, x, 0.f, h / 6.0f);
-        }
-    }
+    while (rc == OK && !run.done(grid)) rc = run.issue(grid, s, true);
     const int rc2 = leave_stream(m, caller, s);
     return rc != OK ? rc : rc2;
 }
+
+// Several fixed-step solves at once, one lane (stream) per distinct handle; see include/flowse_hip.h.  Each item issues
+// exactly the launches flowse_rk_sample issues for it, in the same order on one stream, and no kernel of the library
+// reads what another launch of another lane writes: the results are those of the single calls, bit for bit.
+int flowse_rk_sample_multi(flowse_model* const* handles, int n_items, void* const* x_inout, const void* const* y,
+                           const int* B, const int* T, int F, const float* ts, const float* dts, int N, int tableau,
+                           void* stream) {
+    if (!handles || n_items < 1 || !x_inout || !y || !B || !T || !ts || !dts || N < 1 ||
+        tableau < FLOWSE_TABLEAU_EULER || tableau > FLOWSE_TABLEAU_RK4) {
+        set_error("flowse_rk_sample_multi: bad argument (null table, n_items < 1, N < 1 or unknown tableau)");
+        return ERR_ARG;
+    }
+    struct Lane { flowse_model* m; std::vector<RkRun> runs; size_t cur = 0; };
+    std::vector<Lane> lanes;
+    for (int i = 0; i < n_items; ++i) {
+        if (!handles[i] || !x_inout[i] || !y[i] || handles[i]->block_kind >= 0) {
+            set_error("flowse_rk_sample_multi: item %d has a null pointer or a single-module handle", i);
+            return ERR_ARG;
+        }
+        size_t l = 0;
+        while (l < lanes.size() && lanes[l].m != handles[i]) ++l;
+        if (l == lanes.size()) {
+            if (l == FLOWSE_MAX_LANES) {
+                set_error("flowse_rk_sample_multi: more than %d distinct handles (one lane, i.e. one stream, per handle; a "
+                          "process has 4 hardware queues by default)", FLOWSE_MAX_LANES);
+                return ERR_ARG;
+            }
+            Lane ln;
+            ln.m = handles[i];
+            lanes.push_back(ln);
+        }
+        RkRun run;
+        run.m = handles[i];
+        run.x = static_cast<float*>(x_inout[i]);
+        run.y = static_cast<const float*>(y[i]);
+        run.B = B[i]; run.F = F; run.T = T[i];
+        lanes[l].runs.push_back(run);
+    }
+    for (auto& ln : lanes)
+        if (ln.m->prof_mode != -1) {
+            set_error("flowse_rk_sample_multi: a handle has a profile open (flowse_profile_end first)");
+            return ERR_STATE;
+        }
+    if (n_items == 1) return flowse_rk_sample(handles[0], x_inout[0], y[0], ts, dts, N, tableau, B[0], F, T[0], stream);
+    // Everything that can allocate (and therefore synchronise the device or free a buffer) comes before the first launch:
+    // plans, then per lane the workspace, time table and RK scratch of its largest item, then streams and events.
+    const RkGrid grid(ts, dts, N, tableau);
+    for (auto& ln : lanes) {
+        for (auto& run : ln.runs) {
+            const int rc = get_plan(ln.m, run.B, run.F, run.T, &run.p);
+            if (rc != OK) return rc;
+        }
+        for (auto& run : ln.runs) {
+            const int rc = reserve_rk(ln.m, grid, run.B, run.F, run.T);
+            if (rc != OK) return rc;
+        }
+        const int rc = ensure_stream(ln.m);
+        if (rc != OK) return rc;
+    }
+    hipStream_t caller = static_cast<hipStream_t>(stream);
+    FLOWSE_HIP(hipEventRecord(lanes[0].m->ev_in, caller));
+    for (size_t l = 1; l < lanes.size(); ++l) FLOWSE_HIP(hipStreamWaitEvent(lanes[l].m->gstream, lanes[0].m->ev_in, 0));
+    // round-robin, one network evaluation per lane and turn: every lane has work queued within the first evaluation's
+    // enqueue time.  Plain launches only (a captured graph with parallel branches is what this path must not make).
+    int rc = OK;
+    for (bool busy = true; busy && rc == OK;) {
+        busy = false;
+        for (size_t l = 0; l < lanes.size() && rc == OK; ++l) {
+            Lane& ln = lanes[l];
+            while (ln.cur < ln.runs.size() && ln.runs[ln.cur].done(grid)) ++ln.cur;
+            if (ln.cur == ln.runs.size()) continue;
+            rc = ln.runs[ln.cur].issue(grid, l == 0 ? caller : ln.m->gstream, false);
+            busy = true;
+        }
+    }
+    // join every lane into the caller's stream, also after a failed launch (what was enqueued still runs)
+    for (size_t l = 1; l < lanes.size(); ++l) {
+        const hipError_t e1 = hipEventRecord(lanes[l].m->ev_out, lanes[l].m->gstream);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(caller, lanes[l].m->ev_out, 0) : e1;
+        if (e2 != hipSuccess && rc == OK) {
+            set_error("flowse_rk_sample_multi: joining lane %zu failed: %s", l, hipGetErrorString(e2));
+            rc = ERR_HIP;
+        }
+    }
+    return rc;
+}
+
+int flowse_model_view_create(flowse_model* parent, flowse_model** out) {
+    if (!parent || !out) {
+        set_error("flowse_model_view_create: null argument");
+        return ERR_ARG;
+    }
+    if (parent->block_kind >= 0) {
+        set_error("flowse_model_view_create: the parent is a single-module handle (flowse_block_create)");
+        return ERR_ARG;
+    }
+    if (!parent->wt->d_w) {
+        set_error("flowse_model_view_create: the parent has no weights loaded (flowse_model_load_weights first)");
+        return ERR_STATE;
+    }
+    if (const int rc = check_device(parent)) return rc;
+    CallBlock* call = nullptr;
+    FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&call), sizeof(CallBlock)));
+    flowse_model* v = new flowse_model();
+    v->cfg = parent->cfg;
+    v->wt = parent->wt;
+    v->is_view = true;
+    v->use_graph = parent->use_graph;
+    v->d_call = call;
+    ++v->wt->holders;
+    *out = v;
+    return OK;
+}
+
+int64_t flowse_model_device_bytes(const flowse_model* m, int what) {
+    if (!m || (what != FLOWSE_BYTES_WEIGHTS && what != FLOWSE_BYTES_OWNED)) return 0;
+    if (what == FLOWSE_BYTES_OWNED)
+        return (int64_t)m->d_ws_bytes + (int64_t)m->d_rk45_bytes + 4 * (int64_t)(m->d_ts_floats + m->d_rk_floats) +
+               (m->d_call ? (int64_t)sizeof(CallBlock) : 0);
+    const WeightSet* w = m->wt;
+    auto n = [](const void* p, int64_t numel) { return p ? numel : (int64_t)0; };
+    return 4 * (n(w->d_w, w->d_w_numel) + n(w->d_wino, w->d_wino_numel) + n(w->d_wino2, w->d_wino2_numel) +
+                n(w->d_wsm, w->d_wsm_numel) + n(w->d_wsm16, w->d_wsm_numel)) +
+           2 * (n(w->d_wq, w->d_wq_numel) + n(w->d_w16, w->d_w16_numel) + n(w->d_wfrag, w->d_wfrag_numel));
+}
+
+int flowse_model_weight_holders(const flowse_model* m) { return (m && m->wt->d_w) ? m->wt->holders : 0; }
 
 int64_t flowse_model_graph_launches(const flowse_model* m) { return m ? m->graph_launches : 0; }
 

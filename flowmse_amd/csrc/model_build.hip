@@ -28,14 +28,14 @@ static bool in_list(const int32_t* v, int n, int x) {
 // 16-bit storage applies when every wide tensor of the network has a multiple of 32 channels (what the 16-bit
 // matrix-core kernels tile by); otherwise precision 2 / 3 only switch the operands of the big 3x3 convs (fp32 storage).
 int storage_type_for(const flowse_model* m) {
-    if (m->precision < 2) return DT_F32;
-    for (const auto& mod : m->mods) {
+    if (m->wt->precision < 2) return DT_F32;
+    for (const auto& mod : m->wt->mods) {
         if (mod.kind == M_RESBLOCK || mod.kind == M_ATTN || mod.kind == M_GN)
             if ((mod.in_ch % 32) || (mod.out_ch % 32)) return DT_F32;
         if ((mod.kind == M_COMBINE && (mod.out_ch % 32)) || (mod.kind == M_CONV3 && mod.out_ch != 4 && (mod.out_ch % 32)))
             return DT_F32;
     }
-    return m->precision == 2 ? DT_BF16 : DT_F16;
+    return m->wt->precision == 2 ? DT_BF16 : DT_F16;
 }
 
 // ---- parameter table helpers
@@ -50,16 +50,16 @@ static void add_param(flowse_model* m, const std::string& name, std::initializer
         p.numel *= s;
     }
     for (; i < 4; ++i) p.shape[i] = 1;
-    p.offset = m->blob_numel;
-    m->blob_numel += p.numel;
-    m->params.push_back(p);
+    p.offset = m->wt->blob_numel;
+    m->wt->blob_numel += p.numel;
+    m->wt->params.push_back(p);
 }
 
 void add_module(flowse_model* m, Module mod) {
-    const int idx = (int)m->mods.size();
+    const int idx = (int)m->wt->mods.size();
     const std::string pre = "all_modules." + std::to_string(idx) + ".";
-    mod.p0 = (int)m->params.size();
-    const int64_t ci = mod.in_ch, co = mod.out_ch, td = m->temb_dim;
+    mod.p0 = (int)m->wt->params.size();
+    const int64_t ci = mod.in_ch, co = mod.out_ch, td = m->wt->temb_dim;
     switch (mod.kind) {
         case M_GFP:
             add_param(m, pre + "W", {co});
@@ -105,7 +105,7 @@ void add_module(flowse_model* m, Module mod) {
             }
             break;
     }
-    m->mods.push_back(mod);
+    m->wt->mods.push_back(mod);
 }
 
 Module resblock_module(int in_ch, int out_ch, bool up, bool down) {
@@ -141,9 +141,9 @@ int build_structure(flowse_model* m) {
             return ERR_ARG;
         }
     const int nf = c.nf, L = c.num_levels;
-    m->temb_dim = 4 * nf;
+    m->wt->temb_dim = 4 * nf;
     // output_layer is registered before all_modules (ncsnpp.py:97) -> first in parameters()
-    m->out_w_p = (int)m->params.size();
+    m->wt->out_w_p = (int)m->wt->params.size();
     add_param(m, "output_layer.weight", {2, 4, 1, 1});
     add_param(m, "output_layer.bias", {2});
 
@@ -211,23 +211,23 @@ static int64_t pack_copy(Packer& pk, const float* src, int64_t n) {
 }
 
 int pack_weights(flowse_model* m, const float* blob, Packer& pk) {
-    auto P = [&](int idx) { return blob + m->params[idx].offset; };
+    auto P = [&](int idx) { return blob + m->wt->params[idx].offset; };
     // count Dense_0 rows
     int rows = 0;
-    for (auto& mod : m->mods)
+    for (auto& mod : m->wt->mods)
         if (mod.kind == M_RESBLOCK) {
             mod.dense_row0 = rows;
             rows += mod.out_ch;
         }
-    m->dense_rows = rows;
-    const int td = m->temb_dim;
-    m->w_dense = pk.put((int64_t)rows * td);
-    m->w_dense_b = pk.put(rows);
+    m->wt->dense_rows = rows;
+    const int td = m->wt->temb_dim;
+    m->wt->w_dense = pk.put((int64_t)rows * td);
+    m->wt->w_dense_b = pk.put(rows);
     if (m->block_kind < 0) {
-        m->w_out = pack_copy(pk, P(m->out_w_p), 8);
-        m->w_out_b = pack_copy(pk, P(m->out_w_p + 1), 2);
+        m->wt->w_out = pack_copy(pk, P(m->wt->out_w_p), 8);
+        m->wt->w_out_b = pack_copy(pk, P(m->wt->out_w_p + 1), 2);
     }
-    for (auto& mod : m->mods) {
+    for (auto& mod : m->wt->mods) {
         const int p = mod.p0, ci = mod.in_ch, co = mod.out_ch;
         switch (mod.kind) {
             case M_GFP:
@@ -254,10 +254,10 @@ int pack_weights(flowse_model* m, const float* blob, Packer& pk) {
                 mod.w_gn0_b = pack_copy(pk, P(p + 1), ci);
                 mod.w_c0 = pack_conv(pk, P(p + 2), co, ci, 9);
                 // Dense_0 rows into the stacked table; Conv_0.bias folded into the table's bias
-                memcpy(pk.host.data() + m->w_dense + (int64_t)mod.dense_row0 * td, P(p + 4),
+                memcpy(pk.host.data() + m->wt->w_dense + (int64_t)mod.dense_row0 * td, P(p + 4),
                        (size_t)co * td * sizeof(float));
                 for (int r = 0; r < co; ++r)
-                    pk.host[m->w_dense_b + mod.dense_row0 + r] = P(p + 5)[r] + P(p + 3)[r];
+                    pk.host[m->wt->w_dense_b + mod.dense_row0 + r] = P(p + 5)[r] + P(p + 3)[r];
                 mod.w_gn1_g = pack_copy(pk, P(p + 6), co);
                 mod.w_gn1_b = pack_copy(pk, P(p + 7), co);
                 mod.w_c1 = pack_conv(pk, P(p + 8), co, co, 9);

@@ -50,7 +50,7 @@ struct Builder {
     Tn alloc(int H, int W, int C, int dt = -1) {
         Tn t;
         t.B = B; t.H = H; t.W = W; t.C = C;
-        t.dt = dt >= 0 ? dt : (C > 4 ? m->act_dt : DT_F32);
+        t.dt = dt >= 0 ? dt : (C > 4 ? m->wt->act_dt : DT_F32);
         t.off = arena.alloc(t.bytes());
         return t;
     }
@@ -230,19 +230,19 @@ struct Builder {
             st_nblk = conv_cin4_stats_blocks(Bn, H, Wd, Cout);
         // conv_ksplit / conv_fused_stats_blocks judge the small-M kernel by the TOTAL channel count; a concat whose parts are
         // not 32-aligned (not in the released net) runs the unsplit flat kernel instead: its statistics geometry applies
-        const bool use_smallm = !in16 && !cin4 && M->wsm_offs.count(w) && conv_smallm_ok(Bn, H, Wd, C1, C2, Cout, taps);
+        const bool use_smallm = !in16 && !cin4 && M->wt->wsm_offs.count(w) && conv_smallm_ok(Bn, H, Wd, C1, C2, Cout, taps);
         if (!in16 && !cin4 && !use_smallm && st_nblk > 0 && conv_smallm_ok(Bn, H, Wd, C1 + C2, 0, Cout, taps))
             st_nblk = (H * Wd) % 128 == 0 ? H * Wd / 128 : 0;
-        const bool use_stream = !in16 && !cin4 && ks == 1 && M->wsm_offs.count(w) && conv1x1_stream_ok(Bn, H, Wd, C1, C2, Cout, taps);
+        const bool use_stream = !in16 && !cin4 && ks == 1 && M->wt->wsm_offs.count(w) && conv1x1_stream_ok(Bn, H, Wd, C1, C2, Cout, taps);
         if (!in16 && !cin4 && !use_stream && st_nblk > 0 && conv1x1_stream_ok(Bn, H, Wd, C1 + C2, 0, Cout, taps))
             st_nblk = (H * Wd) % 128 == 0 ? H * Wd / 128 : 0;
         if (in16 && !cin4 && st_nblk > 0 && conv16_smallm_ok(Bn, H, Wd, C1 + C2, 0, Cout, taps) &&
-            !(M->frag_offs.count(w) && conv16_smallm_ok(Bn, H, Wd, C1, C2, Cout, taps)))
+            !(M->wt->frag_offs.count(w) && conv16_smallm_ok(Bn, H, Wd, C1, C2, Cout, taps)))
             st_nblk = (H * Wd) % 128 == 0 ? H * Wd / 128 : 0;
         // the two-dimensional Winograd kernel takes this launch: statistics in 4 x 16 pixel strips
-        const auto w2_it = M->wino2_of.find(w);
-        const int64_t wino2_off = (!in16 && taps == 9 && !cin4 && ks == 1 && w2_it != M->wino2_of.end() &&
-                                   !(wq_off >= 0 && M->precision != 0) && conv_supports_fused_gn(Bn, H, Wd, C1, C2, Cout, taps) &&
+        const auto w2_it = M->wt->wino2_of.find(w);
+        const int64_t wino2_off = (!in16 && taps == 9 && !cin4 && ks == 1 && w2_it != M->wt->wino2_of.end() &&
+                                   !(wq_off >= 0 && M->wt->precision != 0) && conv_supports_fused_gn(Bn, H, Wd, C1, C2, Cout, taps) &&
                                    conv_supports_w2d(Bn, H, Wd, C1, C2, Cout, taps)) ? w2_it->second : -1;
         if (wino2_off >= 0 && st_nblk > 0) st_nblk = H * Wd / 64;
         if (defer || gnf) st_nblk = 0;                   // no output here / the statistics are finished inside the reduction
@@ -258,11 +258,11 @@ struct Builder {
         const size_t st_off = o.st_off;
         const bool has_gin = gin != nullptr;
         const GnBuf gbuf = has_gin ? *gin : GnBuf();
-        const bool use_bf16 = !M->storage16() && wq_off >= 0 && M->precision != 0 && taps == 9 &&
+        const bool use_bf16 = !M->storage16() && wq_off >= 0 && M->wt->precision != 0 && taps == 9 &&
                               conv_supports_bf16(Bn, H, Wd, C1, C2, Cout, taps);
-        const int terms = M->precision == 1 ? 3 : 1;
-        const auto wino_it = M->wino_of.find(w);
-        const int64_t wino_off = (!in16 && taps == 9 && !cin4 && wino_it != M->wino_of.end() &&
+        const int terms = M->wt->precision == 1 ? 3 : 1;
+        const auto wino_it = M->wt->wino_of.find(w);
+        const int64_t wino_off = (!in16 && taps == 9 && !cin4 && wino_it != M->wt->wino_of.end() &&
                                   conv_supports_wino(Bn, H, Wd, C1, C2, Cout, taps)) ? wino_it->second : -1;
         const size_t part_off = ks > 1 ? arena.alloc((size_t)ks * Bn * H * Wd * Cout * sizeof(float)) : 0;
         const size_t table_off = M_table_off;     // by value: the Builder dies before the plan runs
@@ -273,7 +273,7 @@ struct Builder {
         const int FC1 = has_fold ? fold->s1->C : 0, FC2 = has_fold && fold->s2 ? fold->s2->C : 0;
         const int64_t fold_w = has_fold ? fold->w : -1, fold_b = has_fold ? fold->bias : -1;
         if (has_fold && (res || extra || ks != 1 || !in16 || taps != 9 || fold->s1->H != H || fold->s1->W != Wd ||
-                         fold->s1->dt != idt || !M->frag_offs.count(w) || !M->frag_offs.count(fold_w))) {
+                         fold->s1->dt != idt || !M->wt->frag_offs.count(w) || !M->wt->frag_offs.count(fold_w))) {
             set_error("internal: shortcut fold requested for a conv that cannot take it (%s)", label.c_str());
             failed = true;
         }
@@ -290,7 +290,7 @@ struct Builder {
             c.bias = bias >= 0 ? M->W(bias) : nullptr;
             // bias_sc: a second per-channel bias from the weight blob (the same row for every sample: stride 0)
             c.bias2 = dense_row0 >= 0 ? M->A(table_off) + dense_row0 : bias_sc >= 0 ? M->W(bias_sc) : nullptr;
-            c.bias2_stride = dense_row0 >= 0 ? M->dense_rows : 0;
+            c.bias2_stride = dense_row0 >= 0 ? M->wt->dense_rows : 0;
             c.res = hasres ? M->A(r_off) : nullptr;
             c.out = M->A(o_off);
             c.B = Bn; c.H = H; c.W = Wd; c.Cout = Cout;
@@ -314,28 +314,28 @@ struct Builder {
                 c.SC1 = FC1;
                 c.sc2 = FC2 ? M->A(f2_off) : nullptr;
                 c.SC2 = FC2;
-                c.wfrag_sc = M->d_wfrag + fold_w;
+                c.wfrag_sc = M->wt->d_wfrag + fold_w;
                 c.bias_x = fold_b >= 0 ? M->W(fold_b) : nullptr;
             }
             c.in_dt = idt;
             c.out_dt = odt;
             if (in16) {                                   // [Cout][taps][Cin] in the storage type: same offsets as d_w
-                c.wq = M->d_w16 + w;
-                if (M->frag_offs.count(w)) c.wfrag = M->d_wfrag + w;
+                c.wq = M->wt->d_w16 + w;
+                if (M->wt->frag_offs.count(w)) c.wfrag = M->wt->d_wfrag + w;
                 c.terms = 1;
                 c.wq_f16 = idt == DT_F16 ? 1 : 0;
             } else if (use_bf16) {
-                c.wq = M->d_wq + wq_off;
+                c.wq = M->wt->d_wq + wq_off;
                 c.terms = terms;
-                c.wq_f16 = M->precision == 3 ? 1 : 0;
+                c.wq_f16 = M->wt->precision == 3 ? 1 : 0;
             }
-            if (wino_off >= 0) c.wino = M->d_wino + wino_off;
-            if (wino2_off >= 0) c.wino2 = M->d_wino2 + wino2_off;
+            if (wino_off >= 0) c.wino = M->wt->d_wino + wino_off;
+            if (wino2_off >= 0) c.wino2 = M->wt->d_wino2 + wino2_off;
             if (use_smallm) {
-                c.wsm = M->d_wsm + w;
-                c.wsm16 = M->d_wsm16 + w;
+                c.wsm = M->wt->d_wsm + w;
+                c.wsm16 = M->wt->d_wsm16 + w;
             }
-            if (use_stream) c.wsm = M->d_wsm + w;
+            if (use_stream) c.wsm = M->wt->d_wsm + w;
             return c;
         };
         const double flops = 2.0 * Bn * H * Wd * (double)Cout * (taps * (C1 + C2) + (FC1 + FC2));
@@ -449,24 +449,24 @@ struct Builder {
         gf.w_gamma = mod.w_gn1_g;
         gf.w_beta = mod.w_gn1_b;
         gf.silu = true;
-        gf.apply = !fusable_shape(m->act_dt, Ho, Wo, mod.out_ch, 0);
+        gf.apply = !fusable_shape(m->wt->act_dt, Ho, Wo, mod.out_ch, 0);
         SkPartial sp;
         const bool merge_sc = mod.shortcut && sk_two_pass(x1.dt, Ho, Wo, mod.out_ch, mod.out_ch, 9) &&
                               sk_two_pass(x1.dt, Ho, Wo, mod.in_ch, mod.out_ch, 1);
         // 16-bit storage, Conv_1 on the producer / consumer kernel: the shortcut Conv_2(x) runs as extra K steps of Conv_1's
         // launch (ConvArgs::sc1) -- no launch, no round trip of its output through HBM, one read of x less
         const int xc2 = (!mod.up && !mod.down && x2) ? x2->C : 0;
-        const bool fold_sc = mod.shortcut && m->act_dt != DT_F32 && !merge_sc && !getenv("FLOWSE_NO_SCFOLD") &&
-                             m->frag_offs.count(mod.w_c1) && m->frag_offs.count(mod.w_c2) &&
+        const bool fold_sc = mod.shortcut && m->wt->act_dt != DT_F32 && !merge_sc && !getenv("FLOWSE_NO_SCFOLD") &&
+                             m->wt->frag_offs.count(mod.w_c1) && m->wt->frag_offs.count(mod.w_c2) &&
                              conv16_uses_pc(B, Ho, Wo, mod.out_ch, 0, mod.out_ch, 9) &&
-                             fusable_shape(m->act_dt, Ho, Wo, mod.out_ch, 0) && (x1.C % 32) == 0 && (xc2 % 32) == 0 &&
-                             x1.C + xc2 >= 96 && x1.dt == m->act_dt;
+                             fusable_shape(m->wt->act_dt, Ho, Wo, mod.out_ch, 0) && (x1.C % 32) == 0 && (xc2 % 32) == 0 &&
+                             x1.C + xc2 >= 96 && x1.dt == m->wt->act_dt;
         // fp32 up blocks whose shortcut is a launch of its own: Conv_2 has no spatial extent and upsample_2d filters every
         // channel alike, so W . up(x) = up(W . x) -- the 1x1 runs BEFORE the upsampling, on a quarter of the pixels, and the
         // upsampled raw x never exists.  Only the bias does not commute (up(const) is not constant at the image border):
         // Conv_1's epilogue adds it, once per output element.  Up to 2048 low-resolution pixels over the batch the reference's order
         // stays (small-image kernels, shortcuts merged into split-K reductions: not measured in the other order).
-        const bool sc_low = mod.up && mod.shortcut && !merge_sc && !fold_sc && m->act_dt == DT_F32 && x1.dt == DT_F32 &&
+        const bool sc_low = mod.up && mod.shortcut && !merge_sc && !fold_sc && m->wt->act_dt == DT_F32 && x1.dt == DT_F32 &&
                             (int64_t)B * x1.H * x1.W > 2048 && !getenv("FLOWSE_NO_SC_LOW");
         Tn xr;
         if (!mod.up && !mod.down) {
@@ -616,9 +616,9 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
     bd.plan = plan;
     bd.B = B;
     flowse_model* M = m;
-    const int nf = c.nf, td = m->temb_dim;
+    const int nf = c.nf, td = m->wt->temb_dim;
     size_t mi = 0;
-    auto next = [&]() -> const Module& { return m->mods[mi++]; };
+    auto next = [&]() -> const Module& { return m->wt->mods[mi++]; };
 
     // ---- time embedding (depends only on t)
     const Module& gfp = next();
@@ -626,7 +626,7 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
     const Module& lin2 = next();
     const size_t e0 = bd.arena.alloc((size_t)B * 2 * nf * 4), e1 = bd.arena.alloc((size_t)B * td * 4),
                  e2 = bd.arena.alloc((size_t)B * td * 4);
-    bd.M_table_off = bd.arena.alloc((size_t)B * m->dense_rows * 4);
+    bd.M_table_off = bd.arena.alloc((size_t)B * m->wt->dense_rows * 4);
     const size_t table = bd.M_table_off;
     {
         const int64_t wg = gfp.w_a, w1 = lin1.w_a, b1 = lin1.w_a_b, w2 = lin2.w_a, b2 = lin2.w_a_b;
@@ -639,8 +639,8 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
             return launch_linear(M->A(e1), B, td, M->W(w2), M->W(b2), td, 1, M->A(e2), td, s);
         });
         bd.op("dense_table", [=](hipStream_t s) {
-            return launch_linear(M->A(e2), B, td, M->W(M->w_dense), M->W(M->w_dense_b), M->dense_rows, 0,
-                                 M->A(table), M->dense_rows, s);
+            return launch_linear(M->A(e2), B, td, M->W(M->wt->w_dense), M->W(M->wt->w_dense_b), M->wt->dense_rows, 0,
+                                 M->A(table), M->wt->dense_rows, s);
         });
     }
     // ---- feature pack + input conv
@@ -725,15 +725,15 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
         }
     }
     bd.release(h);
-    if (!hs.empty() || mi != m->mods.size()) {
-        set_error("internal: plan consumed %zu of %zu modules, %zu skips left", mi, m->mods.size(), hs.size());
+    if (!hs.empty() || mi != m->wt->mods.size()) {
+        set_error("internal: plan consumed %zu of %zu modules, %zu skips left", mi, m->wt->mods.size(), hs.size());
         return ERR_STATE;
     }
     // ---- head (+ solver update)
     {
         const size_t p = pyr.off;
         bd.op("head", [=](hipStream_t s) {
-            return launch_head(M->A(p), nullptr, M->W(M->w_out), M->W(M->w_out_b), B, F, T, 0, nullptr, 0.f, nullptr, s,
+            return launch_head(M->A(p), nullptr, M->W(M->wt->w_out), M->W(M->wt->w_out_b), B, F, T, 0, nullptr, 0.f, nullptr, s,
                                M->d_call);
         });
     }
@@ -744,7 +744,7 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
 // Plan of a single-module handle: inputs are copied into the arena, the module runs exactly as inside the network
 // (Builder::resblock / attn / conv), the result is copied out.
 int build_block_plan(flowse_model* m, Plan* plan, int B, int H, int W, int C1) {
-    const Module& mod = m->mods[0];
+    const Module& mod = m->wt->mods[0];
     const bool combine = mod.kind == M_COMBINE;
     const int C2 = combine ? mod.out_ch : mod.in_ch - C1;
     if (B < 1 || H < 1 || W < 1 || C1 < 4 || (C1 & 3) || C2 < 0 || (C2 & 3) || (combine && C1 != 4) ||
@@ -759,7 +759,7 @@ int build_block_plan(flowse_model* m, Plan* plan, int B, int H, int W, int C1) {
     bd.plan = plan;
     bd.B = B;
     flowse_model* M = m;
-    const int td = m->temb_dim;
+    const int td = m->wt->temb_dim;
     Tn x1 = bd.alloc(H, W, C1), x2;
     if (C2 > 0) x2 = bd.alloc(H, W, C2);
     {   // the caller's tensors are fp32; in a 16-bit storage mode they are rounded to the activation type on the way in
@@ -774,11 +774,11 @@ int build_block_plan(flowse_model* m, Plan* plan, int B, int H, int W, int C1) {
     }
     Tn out;
     if (mod.kind == M_RESBLOCK) {
-        bd.M_table_off = bd.arena.alloc((size_t)B * m->dense_rows * 4);
+        bd.M_table_off = bd.arena.alloc((size_t)B * m->wt->dense_rows * 4);
         const size_t table = bd.M_table_off;
         bd.op("dense_table", [=](hipStream_t s) {          // Dense_0(act(temb)) + Conv_0.bias (layerspp.py:262-263)
-            return launch_linear(M->bcall.temb_act, B, td, M->W(M->w_dense), M->W(M->w_dense_b), M->dense_rows, 0,
-                                 M->A(table), M->dense_rows, s);
+            return launch_linear(M->bcall.temb_act, B, td, M->W(M->wt->w_dense), M->W(M->wt->w_dense_b), M->wt->dense_rows, 0,
+                                 M->A(table), M->wt->dense_rows, s);
         });
         out = bd.resblock(mod, x1, C2 > 0 ? &x2 : nullptr);
     } else if (mod.kind == M_ATTN) {

@@ -20,7 +20,7 @@ import time
 import numpy as np
 import torch
 
-from flowmse_amd.sampling import get_white_box_solver
+from flowmse_amd.sampling import get_white_box_solver, get_white_box_solver_multi
 from flowmse_amd.util.other import pad_spec, read_wav as _read_wav
 
 
@@ -84,6 +84,34 @@ def enhance_batch(model, ys, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler"):
             for i, (y, n) in enumerate(zip(ys, norms))]
 
 
+def enhance_concurrent(model, ys, lanes, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", groups=None):
+    """Several utterances of ANY lengths as one multi-lane sampler call: up to ``lanes`` (1..4) of them are in flight on
+    the GPU at a time, on streams that share one copy of the weights (``get_white_box_solver_multi``).  Analysis and
+    synthesis run per utterance as in ``enhance_batch``.  ``groups`` (optional): lists of indices into ``ys``, each an
+    equal-padded-length batch that is sampled as ONE item; default every utterance is its own item, and then every
+    waveform equals ``enhance_waveform``'s for the same prior noise, bit for bit.  A throughput option: a single
+    utterance's latency goes up.  ys: list of float tensors [1, samples_i] on the target device.  Returns the list of
+    numpy waveforms, in the order of ``ys``."""
+    norms = [y.abs().max().item() for y in ys]
+    dm = model.data_module
+    fused = hasattr(dm, "fused_ok") and all(dm.fused_ok(y) for y in ys)
+    if fused:                      # STFT + compression + frame padding: one HIP kernel per utterance
+        specs = [dm.analyze(y / n) for y, n in zip(ys, norms)]
+    else:
+        specs = [pad_spec(torch.unsqueeze(model._forward_transform(model._stft(y / n)), 0)) for y, n in zip(ys, norms)]
+    groups = [[i] for i in range(len(ys))] if groups is None else [list(g) for g in groups]
+    Ys = [specs[g[0]] if len(g) == 1 else torch.cat([specs[i] for i in g], dim=0) for g in groups]
+    samples, _ = get_white_box_solver_multi(odesolver, model.ode, model, Ys, T_rev=T_rev, t_eps=t_eps, N=N, lanes=lanes)()
+    out = [None] * len(ys)
+    for g, sample in zip(groups, samples):
+        for j, i in enumerate(g):
+            if fused:              # decompression + iSTFT + rescale: one HIP kernel per utterance
+                out[i] = dm.synthesize(sample[j:j + 1], ys[i].size(1), norms[i]).squeeze().cpu().numpy()
+            else:
+                out[i] = (model.to_audio(sample[j, 0], ys[i].size(1)) * norms[i]).squeeze().cpu().numpy()
+    return out
+
+
 def _write_wav(path, x, sr=16000):
     """16-bit PCM WAV like the reference's ``soundfile.write(path, x_hat, 16000)`` (evaluate.py:147; libsndfile's
     default subtype for .wav is PCM_16, float samples scaled by 0x7FFF and rounded to nearest).  soundfile itself is
@@ -119,7 +147,18 @@ def _synthetic_pairs(n, seconds=2.0, sr=16000, seed=0):
     return out
 
 
-def main(argv=None):
+MAX_STREAMS = 4                  # FLOWSE_MAX_LANES of the library: one stream per lane, four hardware queues per process
+_ITEMS_PER_LANE = 4              # sampler items per lane and multi-lane call (bounds the spectrograms held on the device)
+
+
+def _streams_arg(v):
+    k = int(v)
+    if not 1 <= k <= MAX_STREAMS:
+        raise argparse.ArgumentTypeError(f"--streams must be 1..{MAX_STREAMS}, got {v}")
+    return k
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--test_dir", type=str, default=None, help="directory with test/clean and test/noisy")
     ap.add_argument("--odesolver_type", type=str, choices=("white",), default="white")
@@ -135,6 +174,18 @@ def main(argv=None):
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "bf16", "fp16"])
     ap.add_argument("--batch", type=int, default=1,
                     help="enhance up to this many utterances of equal padded length per sampler call (1 = reference behaviour)")
+    ap.add_argument("--streams", type=_streams_arg, default=1,
+                    help="sample up to this many utterances (or --batch groups) concurrently on one GPU, on streams that "
+                         "share the weights (1..4; 1 = one sampler call at a time). Same output files; more throughput "
+                         "at small batch, longer latency per utterance")
+    ap.add_argument("--seed", type=int, default=None,
+                    help="torch.manual_seed before the first prior sample, so that two runs draw the same noise and write "
+                         "the same files (default: unseeded, like the reference)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.N_mid != 0:
         raise ValueError("N_mid should be 0.")          # evaluate.py:124-125
@@ -178,7 +229,22 @@ def main(argv=None):
     frames, t0 = 0, time.time()
     from flowmse_amd.parallel import batches_by_length
     enhanced = {}
-    if args.batch > 1:                 # group by padded frame count, largest first
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
+    if args.streams > 1:               # utterances (or equal-length batches of them) dealt to concurrent lanes
+        lens = [(((p[2].shape[0] // 128 + 1) + 63) // 64) * 64 for p in pairs]
+        items = [ids for _, ids in batches_by_length(range(len(pairs)), lens, args.batch)] if args.batch > 1 \
+            else [[i] for i in range(len(pairs))]
+        per_call = args.streams * _ITEMS_PER_LANE
+        for k in range(0, len(items), per_call):
+            chunk = items[k:k + per_call]
+            flat = [i for g in chunk for i in g]
+            pos = {i: j for j, i in enumerate(flat)}
+            outs = enhance_concurrent(model, [torch.from_numpy(pairs[i][2])[None].cuda() for i in flat], args.streams,
+                                      N=args.N, T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
+                                      odesolver=args.odesolver, groups=[[pos[i] for i in g] for g in chunk])
+            enhanced.update(dict(zip(flat, outs)))
+    elif args.batch > 1:               # group by padded frame count, largest first
         lens = [(((p[2].shape[0] // 128 + 1) + 63) // 64) * 64 for p in pairs]
         for _, ids in batches_by_length(range(len(pairs)), lens, args.batch):
             outs = enhance_batch(model, [torch.from_numpy(pairs[i][2])[None].cuda() for i in ids], N=args.N,
@@ -223,6 +289,7 @@ def main(argv=None):
         f.write(f"Last evaluated point: {args.last_eval_point}\ndata: {args.test_dir}\node: FLOWMATCHING\n")
         f.write(f"sigma_min: {model.ode.sigma_min}\nsigma_max: {model.ode.sigma_max}\nN: {args.N}\n")
         f.write(f"precision: {args.precision}\n")
+        f.write(f"batch: {args.batch}\nstreams: {args.streams}\nseed: {args.seed}\n")
     print(f"enhanced {len(pairs)} utterances ({frames} frames) in {dt:.2f} s -> {target_dir}")
     return 0
 

@@ -189,6 +189,11 @@ class VFModel(nn.Module):
         """Fused N-step fixed-step loop ('euler' | 'heun' | 'rk4'), in place on x: one library call, no host sync."""
         return self.dnn.rk_sample(x, y, timesteps, stepsizes, tableau)
 
+    def rk_sample_multi_(self, xs, ys, timesteps, stepsizes, tableau, lanes=2, lane_of=None):
+        """The same loop on several items at once, on ``lanes`` streams that share one set of weights: one library call,
+        every item bit-identical to ``rk_sample_`` on it (used by sampling.get_white_box_solver_multi)."""
+        return self.dnn.rk_sample_multi(xs, ys, timesteps, stepsizes, tableau, lanes=lanes, lane_of=lane_of)
+
     def rk45_sample_(self, x, y, t0, t_bound, rtol, atol, first_step=None, max_step=float("inf"), max_nfev=100000):
         """Adaptive RK45 (scipy's step control) in place on x: one library call.  Returns ``(x, nfev, status,
         accepted_times)`` (used by sampling.get_black_box_solver)."""

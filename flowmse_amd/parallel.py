@@ -88,6 +88,29 @@ def plan_batches(indices, lengths, max_batch, promote=False):
     return out
 
 
+def plan_lanes(costs, k):
+    """Deal items to ``k`` concurrent lanes of ONE GPU (``NCSNpp.rk_sample_multi``): longest processing time first, each
+    item to the lane with the least modelled load so far.  ``costs[i]``: modelled time of item i, ``batch_cost(T, b)``
+    for a sampler call on b utterances of T padded frames.  Host only, deterministic: ties go to the earlier item and
+    the lower lane.
+
+    Returns ``(lane_of, order)``: ``lane_of[i]`` the lane of item i, ``order[l]`` the items of lane l in the order they
+    run -- their input order, so ``k = 1`` is the input sequence itself.  The greedy deal keeps the heaviest lane within
+    one item of the mean: max load <= mean load + largest item."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"plan_lanes: k must be >= 1, got {k}")
+    costs = [float(c) for c in costs]
+    loads = [0.0] * k
+    lane_of = [0] * len(costs)
+    for i in sorted(range(len(costs)), key=lambda i: (-costs[i], i)):
+        lane = min(range(k), key=lambda l: (loads[l], l))
+        lane_of[i] = lane
+        loads[lane] += costs[i]
+    order = [[i for i in range(len(costs)) if lane_of[i] == l] for l in range(k)]
+    return lane_of, order
+
+
 def _load(batches):
     return sum(batch_cost(T, len(ids)) for T, ids in batches)
 

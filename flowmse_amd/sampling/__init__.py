@@ -21,7 +21,8 @@ import torch
 
 from .odesolvers import ODEsolver, ODEsolverRegistry
 
-__all__ = ["ODEsolverRegistry", "ODEsolver", "get_white_box_solver", "get_black_box_solver", "fused_rk45", "time_grid"]
+__all__ = ["ODEsolverRegistry", "ODEsolver", "get_white_box_solver", "get_white_box_solver_multi", "get_black_box_solver",
+           "fused_rk45", "time_grid"]
 
 
 def time_grid(T_rev, t_eps, N, device="cpu"):
@@ -89,6 +90,46 @@ def get_white_box_solver(odesolver_name, ode, VF_fn, Y, Y_prior=None, T_rev=1.0,
             finally:
                 odesolver.step_start_time = None
             return xt, N
+
+    return ode_solver
+
+
+def get_white_box_solver_multi(odesolver_name, ode, VF_fn, Ys, Y_priors=None, T_rev=1.0, t_eps=0.03, N=30, zs=None,
+                               lanes=2, **kwargs):
+    """``get_white_box_solver`` for a list of independent items ``Ys[i]`` ([B_i,1,F,T_i]; batch sizes and lengths may
+    differ): returns ``ode_solver() -> ([x_i], N)`` with every ``x_i`` equal, bit for bit, to what the single solver
+    returns for item i.
+
+    When the single solver would be fused for EVERY item (a solver the library implements on a HIP-backed field that
+    offers ``rk_sample_multi_``, device tensors) the items run as ONE library call (``flowse_rk_sample_multi``) on
+    ``lanes`` streams over shared weights, dealt to the lanes by ``flowmse_amd.parallel.plan_lanes``; the priors are drawn
+    first, in list order, so the random stream is consumed as by the single solvers called in that order.  Otherwise the
+    single solver runs per item, in order: same results, no concurrency."""
+    odesolver_cls = ODEsolverRegistry.get_by_name(odesolver_name)
+    n = len(Ys)
+    Y_priors = list(Ys) if Y_priors is None else [Y if P is None else P for Y, P in zip(Ys, Y_priors)]
+    zs = [None] * n if zs is None else list(zs)
+    if len(Y_priors) != n or len(zs) != n:
+        raise ValueError("Ys, Y_priors and zs must have the same length")
+    fused = _fused_tableau(odesolver_cls) is not None and hasattr(VF_fn, "rk_sample_") \
+        and hasattr(VF_fn, "rk_sample_multi_") and n > 0 and all(Y.is_cuda for Y in Ys)
+
+    def ode_solver():
+        if not fused:
+            return [get_white_box_solver(odesolver_name, ode, VF_fn, Y, Y_prior=P, T_rev=T_rev, t_eps=t_eps, N=N, z=z,
+                                         **kwargs)()[0] for Y, P, z in zip(Ys, Y_priors, zs)], N
+        from flowmse_amd.parallel import batch_cost, plan_lanes
+        with torch.no_grad():
+            xts = []
+            for Y, P, z in zip(Ys, Y_priors, zs):
+                xt, _ = ode.prior_sampling(P.shape, P, z) if z is not None else ode.prior_sampling(P.shape, P)
+                xts.append(xt.to(P.device).contiguous())
+            timesteps, stepsizes = time_grid(T_rev, t_eps, N)
+            k = max(1, min(int(lanes), n))
+            lane_of, _ = plan_lanes([batch_cost(Y.shape[-1], Y.shape[0]) for Y in Ys], k)
+            VF_fn.rk_sample_multi_(xts, [Y.contiguous() for Y in Ys], timesteps.tolist(), stepsizes.tolist(),
+                                   _fused_tableau(odesolver_cls), lanes=k, lane_of=lane_of)
+            return xts, N
 
     return ode_solver
 
