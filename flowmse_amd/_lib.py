@@ -61,6 +61,8 @@ SIGNATURES = {
     "flowse_model_reserve": (_i, [_vp, _i, _i, _i, C.POINTER(_i64)]),
     "flowse_vf_forward": (_i, [_vp, _vp, _vp, _fp, _vp, _i, _i, _i, _i, _vp]),
     "flowse_prior_sample": (_i, [_vp, _vp, _f, _vp, _i64, _vp]),
+    "flowse_prior_sample_keyed": (_i, [_vp, _vp, C.c_uint64, _f, _vp, _i, _i, _i, _vp]),
+    "flowse_op_keyed_noise": (_i, [_vp, C.c_uint64, _vp, _i, _i, _i, _vp]),
     "flowse_euler_sample": (_i, [_vp, _vp, _vp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _vp]),
     "flowse_rk_sample": (_i, [_vp, _vp, _vp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _i, _vp]),
     "flowse_rk_sample_multi": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _i,

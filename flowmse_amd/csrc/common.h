@@ -451,5 +451,9 @@ int launch_istft_decompress(const float* spec_c64, int B, int T, int Tpad, float
                             int Lout, float scale_out, hipStream_t s);
 // out = y + sigma * z   (complex64 as float pairs)
 int launch_axpy(const float* y, const float* z, float sigma, int64_t n, float* out, hipStream_t s);
+// out = y + sigma * z (y != null) or out = z (y == null), z = the keyed Philox noise of noise.hip; [B,1,F,T] complex64,
+// T even, 16-byte aligned pointers, keys: B device words
+int launch_keyed_noise(const float* y, const uint64_t* keys, uint64_t seed, float sigma, float* out, int B, int F, int T,
+                       hipStream_t s);
 
 }  // namespace flowse

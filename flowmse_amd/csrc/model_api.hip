@@ -699,6 +699,32 @@ int flowse_axpy(const void* x, const void* k, float dt, void* out, int64_t numel
     return flowse_prior_sample(x, k, dt, out, numel_complex, stream);
 }
 
+static int keyed_args_ok(const char* who, const void* y, bool need_y, const uint64_t* keys, const void* out, int B, int F,
+                         int T) {
+    if ((need_y && !y) || !keys || !out || B <= 0 || F <= 0 || T <= 0 || (T & 1)) {
+        set_error("%s: bad argument (null pointer, B / F / T <= 0 or odd T; got B=%d F=%d T=%d)", who, B, F, T);
+        return ERR_ARG;
+    }
+    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15) {
+        set_error("%s: y and the output must be 16-byte aligned", who);
+        return ERR_ARG;
+    }
+    return OK;
+}
+
+int flowse_prior_sample_keyed(const void* y, const uint64_t* keys_dev, uint64_t seed, float sigma, void* x_out, int B, int F,
+                              int T, void* stream) {
+    if (const int rc = keyed_args_ok("flowse_prior_sample_keyed", y, true, keys_dev, x_out, B, F, T)) return rc;
+    return launch_keyed_noise(static_cast<const float*>(y), keys_dev, seed, sigma, static_cast<float*>(x_out), B, F, T,
+                              static_cast<hipStream_t>(stream));
+}
+
+int flowse_op_keyed_noise(const uint64_t* keys_dev, uint64_t seed, void* z_out_c64, int B, int F, int T, void* stream) {
+    if (const int rc = keyed_args_ok("flowse_op_keyed_noise", nullptr, false, keys_dev, z_out_c64, B, F, T)) return rc;
+    return launch_keyed_noise(nullptr, keys_dev, seed, 0.f, static_cast<float*>(z_out_c64), B, F, T,
+                              static_cast<hipStream_t>(stream));
+}
+
 int flowse_euler_sample(flowse_model* m, void* x_inout, const void* y, const float* ts, const float* dts, int N, int B,
                         int F, int T, void* stream) {
     return flowse_rk_sample(m, x_inout, y, ts, dts, N, FLOWSE_TABLEAU_EULER, B, F, T, stream);

@@ -1,0 +1,79 @@
+// Keyed prior noise: x_T = y + sigma * z with z ~ CN(0, 1) generated in registers from a counter-based stream, so the
+// noise of an utterance depends on (seed, utterance key, bin, frame) only -- not on the batch it rides in, its row, the
+// padded length, or the order of calls.  Replaces (reference): the torch.randn_like of FLOWMATCHING.prior_sampling
+// (flowmse/odes.py:93-100).  The stream is a public contract ("Keyed noise stream"):
+//
+//   Philox4x32-10 (Salmon et al., SC'11; Random123 known answers in tests/test_keyed_noise_host.py)
+//   counter = (t >> 1, f, lo32(key_b), hi32(key_b)),  Philox key = (lo32(seed), hi32(seed))
+//   words (0, 1) -> the value at the even frame t, words (2, 3) -> the value at t + 1
+//   u1 = ((w_a >> 9) + 0.5) * 2^-23 in (0, 1),  u2 = (w_b >> 8) * 2^-24 in [0, 1)      (both exact in fp32)
+//   z  = sqrtf(-logf(u1)) * (cospif(2 u2) + i sinpif(2 u2))                                (E|z|^2 = 1)
+#include "common.h"
+
+namespace flowse {
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t (&w)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
+__device__ __forceinline__ float2 complex_normal(uint32_t wa, uint32_t wb) {
+    const float u1 = ((float)(wa >> 9) + 0.5f) * 0x1p-23f;       // 23-bit integer + 0.5: exact
+    const float u2x2 = (float)(wb >> 8) * 0x1p-23f;              // 2 * u2, exact
+    const float r = sqrtf(-logf(u1));
+    return make_float2(r * cospif(u2x2), r * sinpif(u2x2));
+}
+
+// One thread per Philox call: frames (2 t2, 2 t2 + 1) of one bin of one row = one 16-byte load and store.  The float4
+// index of a thread IS its linear index (rows are [F][T] complex, T even).  ADD: out = y + sigma * z, else out = z.
+template <bool ADD>
+__global__ __launch_bounds__(256) void keyed_noise_kernel(const float4* __restrict__ y, const uint64_t* __restrict__ keys,
+                                                          uint32_t seed_lo, uint32_t seed_hi, float sigma, int F, int Th,
+                                                          int64_t n, float4* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const uint32_t t2 = (uint32_t)(i % Th);
+        const int64_t row = i / Th;
+        const uint32_t f = (uint32_t)(row % F);
+        const uint64_t key = keys[row / F];
+        uint32_t w[4];
+        philox4x32_10(t2, f, (uint32_t)key, (uint32_t)(key >> 32), seed_lo, seed_hi, w);
+        const float2 za = complex_normal(w[0], w[1]), zb = complex_normal(w[2], w[3]);
+        if (ADD) {
+            const float4 v = y[i];
+            out[i] = make_float4(v.x + __fmul_rn(za.x, sigma), v.y + __fmul_rn(za.y, sigma),
+                                 v.z + __fmul_rn(zb.x, sigma), v.w + __fmul_rn(zb.y, sigma));
+        } else {
+            out[i] = make_float4(za.x, za.y, zb.x, zb.y);
+        }
+    }
+}
+
+int launch_keyed_noise(const float* y, const uint64_t* keys, uint64_t seed, float sigma, float* out, int B, int F, int T,
+                       hipStream_t s) {
+    const int Th = T / 2;
+    const int64_t n = (int64_t)B * F * Th;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
+    if (y)
+        hipLaunchKernelGGL(keyed_noise_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s,
+                           reinterpret_cast<const float4*>(y), keys, lo, hi, sigma, F, Th, n, reinterpret_cast<float4*>(out));
+    else
+        hipLaunchKernelGGL(keyed_noise_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s,
+                           static_cast<const float4*>(nullptr), keys, lo, hi, 0.f, F, Th, n, reinterpret_cast<float4*>(out));
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+}  // namespace flowse

@@ -74,10 +74,21 @@ class FLOWMATCHING(ODE):
         """sigma(1) as the float32 number the reference evaluates for a batch of ones (odes.py:96)."""
         return float(self._std(torch.ones(1, dtype=torch.float32)))
 
-    def prior_sampling(self, shape, y, z=None):
-        """Returns ``(x_T, z)``.  ``z`` may be passed in for reproducible trajectories."""
+    def prior_sampling(self, shape, y, z=None, *, keys=None, seed=0):
+        """Returns ``(x_T, z)``.  ``z`` may be passed in for reproducible trajectories.
+
+        ``keys`` (one 64-bit utterance key per row of ``y`` [B,1,F,T], a sequence of ints or an int64 tensor holding
+        the same bits) with ``seed`` selects the keyed noise stream of ``flowmse_amd.util.noise`` instead of the
+        process-wide generator: the noise of a row then depends on (seed, key, bin, frame) only.  On a HIP tensor this
+        is one ``flowse_prior_sample_keyed`` launch that generates the noise in registers, and the returned ``z`` is
+        ``None`` -- the noise never exists as a tensor there.  On a CPU tensor it is the float64 restatement rounded to
+        complex64, and ``z`` is returned.  ``keys`` together with ``z`` raises ``ValueError``."""
         if tuple(shape) != tuple(y.shape):
             warnings.warn(f"prior_sampling: requested shape {tuple(shape)} differs from y {tuple(y.shape)}; using y's")
+        if keys is not None:
+            if z is not None:
+                raise ValueError("prior_sampling: pass either z or keys, not both")
+            return self._prior_sampling_keyed(y, keys, seed)
         z = torch.randn_like(y) if z is None else z
         if not y.is_cuda:
             return y + z * _bcast(self._std(torch.ones(y.shape[0], device=y.device))), z
@@ -88,3 +99,34 @@ class FLOWMATCHING(ODE):
             _lib.check(_lib.lib.flowse_prior_sample(_lib.ptr(y), _lib.ptr(zc), self.prior_std(), _lib.ptr(x_T),
                                                     y.numel(), _lib.current_stream()))
         return x_T, z
+
+    def _prior_sampling_keyed(self, y, keys, seed):
+        if y.dim() != 4 or y.shape[1] != 1 or y.dtype != torch.complex64:
+            raise ValueError(f"prior_sampling(keys=...): y must be complex64 [B,1,F,T], got {y.dtype} {tuple(y.shape)}")
+        B, _, F, T = y.shape
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if torch.is_tensor(keys):
+            if keys.dtype != torch.int64 or keys.numel() != B:
+                raise ValueError(f"prior_sampling: keys must be {B} int64 words, got {keys.dtype} x {keys.numel()}")
+            key_list = None if y.is_cuda else [int(k) for k in keys.reshape(-1).tolist()]
+        else:
+            key_list = [int(k) & 0xFFFFFFFFFFFFFFFF for k in keys]
+            if len(key_list) != B:
+                raise ValueError(f"prior_sampling: {len(key_list)} keys for a batch of {B}")
+        if not y.is_cuda:
+            from flowmse_amd.util.noise import keyed_noise_reference
+            z = torch.from_numpy(keyed_noise_reference([k & 0xFFFFFFFFFFFFFFFF for k in key_list], seed, F, T)).to(torch.complex64)
+            return y + z * self.prior_std(), z
+        from flowmse_amd import _lib
+        if T % 2:
+            raise ValueError(f"prior_sampling(keys=...): the keyed kernel takes an even number of frames, got T={T}")
+        if key_list is None:
+            kd = keys.to(y.device).contiguous()
+        else:                      # the 64 key bits as int64 (torch has no arithmetic-free uint64 on every build)
+            kd = torch.tensor([k - (1 << 64) if k >= (1 << 63) else k for k in key_list], dtype=torch.int64, device=y.device)
+        y = y.contiguous()
+        x_T = torch.empty_like(y)
+        with torch.cuda.device(y.device):
+            _lib.check(_lib.lib.flowse_prior_sample_keyed(_lib.ptr(y), _lib.ptr(kd), seed, self.prior_std(), _lib.ptr(x_T),
+                                                          B, F, T, _lib.current_stream()))
+        return x_T, None

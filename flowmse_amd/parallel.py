@@ -115,7 +115,7 @@ def _load(batches):
     return sum(batch_cost(T, len(ids)) for T, ids in batches)
 
 
-def plan_shards(lengths, world_size, max_batch, promote=False):
+def plan_shards(lengths, world_size, max_batch, promote=False, level=True):
     """Deal a ragged utterance set to `world_size` ranks as ready-made batches: [[(T, ids), ...] per rank].
 
     lengths: padded frame counts (multiples of the model's 64-frame granule).  (1) plan_batches() over the WHOLE set:
@@ -124,7 +124,11 @@ def plan_shards(lengths, world_size, max_batch, promote=False):
     sampler call per distinct length: at 8 ranks the 512 / 576 / 640-frame buckets ran at batch 1..6 rates).  (2) The
     batches go, most expensive first, each to the currently least-loaded rank (LPT on modelled time; deterministic).
     (3) Levelling: while moving part of a batch from the most to the least loaded rank shortens the longer of the
-    two, do so (this is what splits a lone batch over idle ranks when there are fewer batches than ranks)."""
+    two, do so (this is what splits a lone batch over idle ranks when there are fewer batches than ranks).
+
+    level=False skips step (3): the multiset of batches over all ranks is then plan_batches() of the whole set for EVERY
+    world size.  Kernel selection depends on the batch width, so this is what a run needs whose results must not depend
+    on the number of ranks (``evaluate --gpus N``), at the price of idle ranks when batches are fewer than ranks."""
     batches = plan_batches(range(len(lengths)), lengths, max_batch, promote)
     batches.sort(key=lambda b: (-batch_cost(b[0], len(b[1])), -b[0], b[1][0]))
     loads = [0.0] * world_size
@@ -133,7 +137,7 @@ def plan_shards(lengths, world_size, max_batch, promote=False):
         r = min(range(world_size), key=lambda k: (loads[k], k))
         plan[r].append((T, list(ids)))
         loads[r] += batch_cost(T, len(ids))
-    for _ in range(4 * world_size):                                # levelling moves (bounded)
+    for _ in range(4 * world_size if level else 0):                # levelling moves (bounded)
         hi = max(range(world_size), key=lambda k: (loads[k], -k))
         lo = min(range(world_size), key=lambda k: (loads[k], k))
         best = None                                                # (new makespan of the pair, batch index, count moved)
@@ -182,6 +186,19 @@ def plan_summary(plan, lengths, max_batch):
             "model_time_imbalance_max_over_mean": (max(r["model_ms"] for r in ranks) / mean_t) if mean_t else 1.0,
             "batch_fill": (run / cap) if cap else 1.0,
             "promotion_padding_frames": run - sum(r["frames"] for r in ranks)}
+
+
+def gather_rows(rows_local, group=None):
+    """Small host rows (any picklable objects, e.g. one metrics row per utterance) from every rank to rank 0:
+    ``dist.gather_object``.  Returns on rank 0 ONE flat list -- rank 0's rows, then rank 1's, ... -- and None elsewhere.
+    Without an initialised process group (or at world 1) it is the local list."""
+    rows_local = list(rows_local)
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return rows_local
+    rank = dist.get_rank(group)
+    recv = [None] * dist.get_world_size(group) if rank == 0 else None
+    dist.gather_object(rows_local, recv, dst=0, group=group)
+    return [row for part in recv for row in part] if rank == 0 else None
 
 
 def _pad_to(t, multiple):

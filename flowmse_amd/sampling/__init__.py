@@ -54,9 +54,18 @@ def _fused_tableau(odesolver_cls):
     return name
 
 
+def _prior(ode, P, z, noise_keys, noise_seed):
+    """The prior sample of one solver call: explicit ``z``, the keyed stream (``noise_keys``: one 64-bit key per row of
+    ``P``), or the process-wide generator -- each through the call ``prior_sampling`` had before keys existed."""
+    if noise_keys is not None:
+        return ode.prior_sampling(P.shape, P, z, keys=noise_keys, seed=noise_seed)[0]
+    return ode.prior_sampling(P.shape, P, z)[0] if z is not None else ode.prior_sampling(P.shape, P)[0]
+
+
 def get_white_box_solver(odesolver_name, ode, VF_fn, Y, Y_prior=None, T_rev=1.0, t_eps=0.03, N=30, z=None,
-                         **kwargs):
-    """Returns ``ode_solver() -> (x_result, N)``.  Extra keyword ``z``: explicit prior noise (reproducibility)."""
+                         noise_keys=None, noise_seed=0, **kwargs):
+    """Returns ``ode_solver() -> (x_result, N)``.  Extra keyword ``z``: explicit prior noise (reproducibility);
+    ``noise_keys`` / ``noise_seed``: the keyed noise stream instead (``FLOWMATCHING.prior_sampling``), one key per row."""
     odesolver_cls = ODEsolverRegistry.get_by_name(odesolver_name)
     odesolver = odesolver_cls(ode, VF_fn)
     fused = _fused_tableau(odesolver_cls) is not None and hasattr(VF_fn, "rk_sample_") and Y.is_cuda
@@ -65,11 +74,7 @@ def get_white_box_solver(odesolver_name, ode, VF_fn, Y, Y_prior=None, T_rev=1.0,
         with torch.no_grad():
             if Y_prior is None:
                 Y_prior = Y
-            if z is not None:
-                xt, _ = ode.prior_sampling(Y_prior.shape, Y_prior, z)
-            else:
-                xt, _ = ode.prior_sampling(Y_prior.shape, Y_prior)
-            xt = xt.to(Y_prior.device)
+            xt = _prior(ode, Y_prior, z, noise_keys, noise_seed).to(Y_prior.device)
             # host copy of the grid: the values equal torch.linspace(..., device=Y.device) of the reference
             timesteps, stepsizes = time_grid(T_rev, t_eps, N)
             if fused:
@@ -95,7 +100,7 @@ def get_white_box_solver(odesolver_name, ode, VF_fn, Y, Y_prior=None, T_rev=1.0,
 
 
 def get_white_box_solver_multi(odesolver_name, ode, VF_fn, Ys, Y_priors=None, T_rev=1.0, t_eps=0.03, N=30, zs=None,
-                               lanes=2, **kwargs):
+                               lanes=2, noise_keys=None, noise_seed=0, **kwargs):
     """``get_white_box_solver`` for a list of independent items ``Ys[i]`` ([B_i,1,F,T_i]; batch sizes and lengths may
     differ): returns ``ode_solver() -> ([x_i], N)`` with every ``x_i`` equal, bit for bit, to what the single solver
     returns for item i.
@@ -104,26 +109,28 @@ def get_white_box_solver_multi(odesolver_name, ode, VF_fn, Ys, Y_priors=None, T_
     offers ``rk_sample_multi_``, device tensors) the items run as ONE library call (``flowse_rk_sample_multi``) on
     ``lanes`` streams over shared weights, dealt to the lanes by ``flowmse_amd.parallel.plan_lanes``; the priors are drawn
     first, in list order, so the random stream is consumed as by the single solvers called in that order.  Otherwise the
-    single solver runs per item, in order: same results, no concurrency."""
+    single solver runs per item, in order: same results, no concurrency.  ``noise_keys``: one key list per item (the
+    keyed noise stream under ``noise_seed``, see ``get_white_box_solver``)."""
     odesolver_cls = ODEsolverRegistry.get_by_name(odesolver_name)
     n = len(Ys)
     Y_priors = list(Ys) if Y_priors is None else [Y if P is None else P for Y, P in zip(Ys, Y_priors)]
     zs = [None] * n if zs is None else list(zs)
-    if len(Y_priors) != n or len(zs) != n:
-        raise ValueError("Ys, Y_priors and zs must have the same length")
+    keys = [None] * n if noise_keys is None else list(noise_keys)
+    if len(Y_priors) != n or len(zs) != n or len(keys) != n:
+        raise ValueError("Ys, Y_priors, zs and noise_keys must have the same length")
     fused = _fused_tableau(odesolver_cls) is not None and hasattr(VF_fn, "rk_sample_") \
         and hasattr(VF_fn, "rk_sample_multi_") and n > 0 and all(Y.is_cuda for Y in Ys)
 
     def ode_solver():
         if not fused:
             return [get_white_box_solver(odesolver_name, ode, VF_fn, Y, Y_prior=P, T_rev=T_rev, t_eps=t_eps, N=N, z=z,
-                                         **kwargs)()[0] for Y, P, z in zip(Ys, Y_priors, zs)], N
+                                         noise_keys=k, noise_seed=noise_seed, **kwargs)()[0]
+                    for Y, P, z, k in zip(Ys, Y_priors, zs, keys)], N
         from flowmse_amd.parallel import batch_cost, plan_lanes
         with torch.no_grad():
             xts = []
-            for Y, P, z in zip(Ys, Y_priors, zs):
-                xt, _ = ode.prior_sampling(P.shape, P, z) if z is not None else ode.prior_sampling(P.shape, P)
-                xts.append(xt.to(P.device).contiguous())
+            for P, z, k in zip(Y_priors, zs, keys):
+                xts.append(_prior(ode, P, z, k, noise_seed).to(P.device).contiguous())
             timesteps, stepsizes = time_grid(T_rev, t_eps, N)
             k = max(1, min(int(lanes), n))
             lane_of, _ = plan_lanes([batch_cost(Y.shape[-1], Y.shape[0]) for Y in Ys], k)
@@ -184,7 +191,7 @@ def _rk45_fused(VF_fn, x, y, T_rev, t_eps, rtol, atol, first_step=None, max_step
 
 
 def get_black_box_solver(ode, VF_fn, y, rtol=1e-5, atol=1e-5, T_rev=1.0, t_eps=0.03, N=30, method="RK45",
-                         device="cuda", z=None, **kwargs):
+                         device="cuda", z=None, noise_keys=None, noise_seed=0, **kwargs):
     """Adaptive black-box sampler (reference: flowmse/sampling/__init__.py:64-114): scipy ``solve_ivp`` on the
     flattened complex state from T_rev down to t_eps (NOT to 0), each right-hand side evaluation being one call
     of ``VF_fn`` (host <-> device round trip per evaluation, as in the reference).  Returns ``(x, nfe)``.
@@ -194,12 +201,13 @@ def get_black_box_solver(ode, VF_fn, y, rtol=1e-5, atol=1e-5, T_rev=1.0, t_eps=0
     (``flowse_rk45_sample``) that keeps the state on the device and takes the steps scipy takes -- same nfev, same
     accepted times, same end point up to the summation order of the error norm; the only host traffic is one 8-byte
     error norm per attempted step.  Everything else (other methods, array tolerances, ``t_eval``, ``dense_output``,
-    ``events``, any other callable field) runs scipy exactly as before."""
+    ``events``, any other callable field) runs scipy exactly as before.  ``noise_keys`` / ``noise_seed``: the keyed
+    noise stream for the prior (see ``get_white_box_solver``)."""
     from scipy import integrate
 
     def ode_solver(**solver_kwargs):
         with torch.no_grad():
-            x = (ode.prior_sampling(y.shape, y, z)[0] if z is not None else ode.prior_sampling(y.shape, y)[0]).to(device)
+            x = _prior(ode, y, z, noise_keys, noise_seed).to(device)
             if fused_rk45(method, VF_fn, y, rtol, atol, solver_kwargs):
                 xd = x.to(device=y.device, dtype=torch.complex64).contiguous()
                 xd, nfev = _rk45_fused(VF_fn, xd, y.contiguous(), T_rev, t_eps, rtol, atol, **solver_kwargs)

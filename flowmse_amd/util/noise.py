@@ -1,0 +1,63 @@
+"""Keyed prior noise: the host restatement of ``csrc/noise.hip`` and the utterance keys.
+
+The stream is a public contract ("Keyed noise stream"): for the row of utterance key ``k`` under
+``seed``, bin ``f``, frame ``t``
+
+    (w0, w1, w2, w3) = Philox4x32-10(counter = (t >> 1, f, lo32(k), hi32(k)), key = (lo32(seed), hi32(seed)))
+    (w_a, w_b)       = (w0, w1) at even t, (w2, w3) at odd t
+    u1 = ((w_a >> 9) + 0.5) * 2**-23,   u2 = (w_b >> 8) * 2**-24
+    z  = sqrt(-log(u1)) * exp(2 pi i u2)                     complex standard normal, E|z|^2 = 1
+
+so the value at (f, t) depends on nothing but (seed, k, f, t): not on the batch, the row, the padded length or the
+order of calls.  The kernel evaluates the last line in fp32; this module evaluates it in float64.
+"""
+import hashlib
+import os
+
+import numpy as np
+
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_MASK32 = 0xFFFFFFFF
+_MASK64 = 0xFFFFFFFFFFFFFFFF
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 (Salmon et al., SC'11).  ``ctr``: four 32-bit words, ``key``: two; each an int or an integer numpy
+    array (arrays broadcast).  Returns the four output words as uint64 arrays holding 32-bit values (Python ints for
+    all-int input)."""
+    scalar = all(isinstance(v, (int, np.integer)) for v in tuple(ctr) + tuple(key))
+    c = [np.asarray(v, dtype=np.uint64) & np.uint64(_MASK32) for v in ctr]
+    k = [np.asarray(v, dtype=np.uint64) & np.uint64(_MASK32) for v in key]
+    m0, m1, mask, s32 = np.uint64(PHILOX_M0), np.uint64(PHILOX_M1), np.uint64(_MASK32), np.uint64(32)
+    for r in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]                          # 32 x 32 -> 64 bits: no overflow in uint64
+        c = [(p1 >> s32) ^ c[1] ^ k[0], p1 & mask, (p0 >> s32) ^ c[3] ^ k[1], p0 & mask]
+        k = [(k[0] + np.uint64(PHILOX_W0)) & mask, (k[1] + np.uint64(PHILOX_W1)) & mask]
+    return tuple(int(v) for v in c) if scalar else tuple(c)
+
+
+def keyed_noise_reference(keys, seed, F, T):
+    """The noise of the stream above in float64: complex128 array [B, 1, F, T] for the B utterance keys ``keys``."""
+    keys = [int(k) & _MASK64 for k in np.asarray(keys, dtype=np.uint64).reshape(-1).tolist()]
+    seed = int(seed) & _MASK64
+    F, T = int(F), int(T)
+    t = np.arange(T, dtype=np.uint64)[None, :]
+    f = np.arange(F, dtype=np.uint64)[:, None]
+    odd = (t & np.uint64(1)).astype(bool)
+    out = np.empty((len(keys), 1, F, T), dtype=np.complex128)
+    for b, k in enumerate(keys):
+        w = philox4x32_10((t >> np.uint64(1), f, k & _MASK32, k >> 32), (seed & _MASK32, seed >> 32))
+        wa = np.where(odd, w[2], w[0])
+        wb = np.where(odd, w[3], w[1])
+        u1 = ((wa >> np.uint64(9)).astype(np.float64) + 0.5) * 2.0 ** -23
+        u2 = (wb >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
+        r = np.sqrt(-np.log(u1))
+        out[b, 0] = r * (np.cos(2.0 * np.pi * u2) + 1j * np.sin(2.0 * np.pi * u2))
+    return out
+
+
+def utterance_key(name):
+    """64-bit key of an utterance: the 8-byte BLAKE2b digest of the file's base name, little-endian.  Depends on the
+    name only -- not on the directory, the listing, or the position in it."""
+    return int.from_bytes(hashlib.blake2b(os.path.basename(name).encode(), digest_size=8).digest(), "little")

@@ -167,6 +167,17 @@ int flowse_vf_forward(flowse_model* m, const void* x, const void* y, const float
  * x <- y + sigma * z                                            (FLOWMATCHING.prior_sampling, odes.py:93-100) */
 int flowse_prior_sample(const void* y, const void* z, float sigma, void* x_out, int64_t numel_complex,
                         void* stream);
+/* The same with z generated inside the kernel from a counter-based stream (no z tensor exists): row b of
+ * y / x_out [B,1,F,T] complex64 gets the noise of utterance key keys_dev[b] (B 64-bit words in device memory) under
+ * `seed`.  Philox4x32-10, counter (t >> 1, f, lo32(key), hi32(key)), key (lo32(seed), hi32(seed)); words (0, 1) give
+ * the value at even t, words (2, 3) at odd t; u1 = ((w_a >> 9) + 0.5) 2^-23, u2 = (w_b >> 8) 2^-24,
+ * z = sqrtf(-logf(u1)) (cospif(2 u2) + i sinpif(2 u2)), x = y + fl(z sigma) per part.  The value at (f, t) does not
+ * depend on B, the row's position or T ("Keyed noise stream").  T must be even and the pointers
+ * 16-byte aligned.  Enqueues only; no host synchronisation. */
+int flowse_prior_sample_keyed(const void* y, const uint64_t* keys_dev, uint64_t seed, float sigma, void* x_out, int B,
+                              int F, int T, void* stream);
+/* The bare noise z [B,1,F,T] complex64 of the stream above. */
+int flowse_op_keyed_noise(const uint64_t* keys_dev, uint64_t seed, void* z_out_c64, int B, int F, int T, void* stream);
 /* N Euler steps in place on x (ode_solver loop, flowmse/sampling/__init__.py:45-57, with
  * EulerODEsolver.update_fn, sampling/odesolvers.py:42-47):  for i: x <- x + VF(x, ts[i], y) * (-dts[i]).
  * ts, dts: HOST float32 arrays of length N (the caller reproduces torch.linspace and the step rule, including
