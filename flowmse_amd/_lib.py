@@ -63,6 +63,8 @@ SIGNATURES = {
     "flowse_prior_sample": (_i, [_vp, _vp, _f, _vp, _i64, _vp]),
     "flowse_prior_sample_keyed": (_i, [_vp, _vp, C.c_uint64, _f, _vp, _i, _i, _i, _vp]),
     "flowse_op_keyed_noise": (_i, [_vp, C.c_uint64, _vp, _i, _i, _i, _vp]),
+    "flowse_prior_sample_keyed_at": (_i, [_vp, _vp, _vp, C.c_uint64, _f, _vp, _i, _i, _i, _vp]),
+    "flowse_op_keyed_noise_at": (_i, [_vp, _vp, C.c_uint64, _vp, _i, _i, _i, _vp]),
     "flowse_euler_sample": (_i, [_vp, _vp, _vp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _vp]),
     "flowse_rk_sample": (_i, [_vp, _vp, _vp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _i, _i, _vp]),
     "flowse_rk_sample_multi": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _i,
@@ -73,6 +75,8 @@ SIGNATURES = {
     "flowse_axpy": (_i, [_vp, _vp, _f, _vp, _i64, _vp]),
     "flowse_stft_compress": (_i, [_fp, _i, _i, _f, _vp, _i, _i, _f, _f, _vp]),
     "flowse_istft_decompress": (_i, [_vp, _i, _i, _i, _f, _f, _fp, _i, _f, _vp]),
+    "flowse_stft_compress_chunks": (_i, [_fp, _i, _f, _vp, _i, _i, _i, _f, _f, _vp]),
+    "flowse_istft_decompress_chunks": (_i, [_vp, _i, _i, _i, _f, _f, _fp, _i, _f, _vp]),
     "flowse_profile_begin": (_i, [_vp, _i]),
     "flowse_profile_end": (_i, [_vp, C.c_char_p, _i]),
     "flowse_upfirdn2d": (_i, [_fp, _fp] + [_i] * 13 + [_fp, _i, _i, _vp]),

@@ -1,0 +1,146 @@
+"""Recordings of any length: one recording as equal, overlapping chunks of ordinary sampler rows.
+
+An opt-in mode, NOT the reference's computation for a long file.  The reference (and every other sampler entry of this
+package) treats an utterance as one ``[B,1,256,T]`` tensor: memory grows with the length, and GroupNorm statistics and
+the 16-bin attention run over all frames, a context the network -- trained on crops of 256 frames
+(flowmse/data_module.py:98,110) -- never saw on a minutes-long file.  Here the spectrogram of ONE recording is cut into
+``K`` chunks of ``Tc`` frames that start ``hop = Tc - To`` frames apart; the chunks are sampled as rows of ordinary
+``[b,1,256,Tc]`` calls, ``b <= batch``, with a workspace that depends on ``(batch, Tc)`` only; the sampled chunks are
+cross-faded over their ``To`` shared frames and ONE inverse STFT makes the waveform.  Every chunk has its own GroupNorm
+and attention context, so the result differs from the single-tensor path; it is pinned instead to the oracle
+composition -- the oracle sampler per chunk plus the same cross-fade on the host (tests/test_gpu_chunked.py).
+
+Geometry (``plan_chunks``): ``T = L // 128 + 1`` real frames; chunk ``k`` covers the recording's frames
+``[k hop, k hop + Tc)``; ``K = 1`` if ``T <= Tc`` else ``ceil((T - To) / hop)``; ``Tg = (K - 1) hop + Tc`` frames in all,
+those ``>= T`` zero as with ``pad_spec``.  The tail chunk is zero-padded, not right-aligned: the treatment a short file
+gets today, with one hop everywhere.  ``To <= Tc / 2`` guarantees that at most two chunks cover a frame.
+
+Seam rule (``blend_chunks_reference``; ``flowse_istft_decompress_chunks`` on the device): the recording's frame ``t``
+belongs to chunk ``k = min(t // hop, K - 1)`` at ``j = t - k hop``; for ``k > 0`` and ``j < To`` its value is
+``a + w (b - a)`` with ``a`` = chunk ``k - 1`` at frame ``j + hop``, ``b`` = chunk ``k`` at ``j``, ``w = (j + 0.5) / To``
+-- a linear cross-fade of the COMPRESSED complex values, before ``spec_back``.
+
+Noise: all chunks of a recording share its utterance key and address the keyed stream at their absolute frames
+(``frame0 = k hop``), so two chunks start from the same ``x_T`` on the frames they share; an explicit ``z`` or the torch
+generator gives one ``[1,1,256,Tg]`` draw that is sliced per chunk.
+
+The defaults ``Tc = 256`` (the training crop) and ``To = 32`` are chosen values, not tuned ones: no released checkpoint is
+at hand offline, so how the seams sound has not been judged.
+"""
+import numpy as np
+import torch
+
+CHUNK_FRAMES, OVERLAP_FRAMES = 256, 32
+
+
+def plan_chunks(T, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES):
+    """``(K, hop, Tg)`` for ``T`` real frames cut into chunks of ``Tc`` frames overlapping by ``To`` (module docstring).
+    ``ValueError`` unless ``T >= 1``, ``Tc`` a positive multiple of 64, ``To`` even and ``0 <= To <= Tc / 2``."""
+    T, Tc, To = int(T), int(Tc), int(To)
+    if T < 1:
+        raise ValueError(f"plan_chunks: T must be >= 1, got {T}")
+    if Tc < 64 or Tc % 64:
+        raise ValueError(f"plan_chunks: chunk_frames must be a positive multiple of 64 (the network's frame padding), got {Tc}")
+    if To % 2 or not 0 <= To <= Tc // 2:
+        raise ValueError(f"plan_chunks: overlap_frames must be even (the keyed noise stream pairs frames) and in "
+                         f"0..chunk_frames / 2 = {Tc // 2} (at most two chunks over a frame), got {To}")
+    hop = Tc - To
+    K = 1 if T <= Tc else -(-(T - To) // hop)
+    return K, hop, (K - 1) * hop + Tc
+
+
+def blend_chunks_reference(chunks, hop):
+    """The seam rule in float64: chunks ``[K,1,F,Tc]`` (numpy or torch, complex) that start ``hop`` frames apart ->
+    complex128 numpy ``[1,1,F,Tg]``.  Chunks cut from one spectrogram return it exactly (``b - a`` is an exact zero)."""
+    c = chunks.detach().cpu().numpy() if torch.is_tensor(chunks) else np.asarray(chunks)
+    c = c.astype(np.complex128)
+    K, _, F, Tc = c.shape
+    hop = int(hop)
+    To = Tc - hop
+    if not (1 <= hop <= Tc and To <= hop):
+        raise ValueError(f"blend_chunks_reference: need Tc / 2 <= hop <= Tc, got Tc={Tc} hop={hop}")
+    out = np.empty((1, 1, F, (K - 1) * hop + Tc), dtype=np.complex128)
+    for k in range(K):                                   # a later chunk owns the frames it shares with the one before
+        out[0, :, :, k * hop:k * hop + Tc] = c[k]
+    w = (np.arange(To, dtype=np.float64) + 0.5) / max(To, 1)
+    for k in range(1, K):
+        a, b = c[k - 1][:, :, hop:], c[k][:, :, :To]
+        out[0, :, :, k * hop:k * hop + To] = a + w * (b - a)
+    return out
+
+
+def _chunk_noise(z, noise_key, Y_like, Tg):
+    """The one ``[1,1,F,Tg]`` noise tensor of a recording when the noise is not keyed (explicit ``z`` or one draw from
+    the process-wide generator), else None."""
+    if noise_key is not None:
+        return None
+    F = Y_like.shape[2]
+    if z is None:
+        return torch.randn_like(torch.empty(1, 1, F, Tg, dtype=torch.complex64, device=Y_like.device))
+    if tuple(z.shape) != (1, 1, F, Tg):
+        raise ValueError(f"enhance_long: z must be the recording's noise [1,1,{F},{Tg}], got {tuple(z.shape)}")
+    return z.to(Y_like.device)
+
+
+def enhance_long(model, y, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES, batch=8, N=5, T_rev=1.0, t_eps=0.03,
+                 odesolver="euler", z=None, noise_key=None, noise_seed=0, VF_fn=None, device=None):
+    """One recording of any length, chunked (module docstring).  y: float tensor [1, samples].  Returns the enhanced
+    waveform (numpy), normalised by the recording's global ``max|y|`` like ``enhance_waveform``.
+
+    A recording whose padded frame count fits one chunk goes to ``evaluate.enhance_waveform`` unchanged.  Otherwise the
+    chunk rows of THIS recording are sampled in groups of ``batch`` (the last group narrower); rows are never pooled
+    across recordings, so a file depends on (weights, recording, seed, solver, ``batch``, ``chunk_frames``,
+    ``overlap_frames``) only.  ``z``: the recording's noise [1,1,256,Tg], sliced per chunk; ``noise_key`` /
+    ``noise_seed``: the keyed stream at absolute frames; neither: one draw of [1,1,256,Tg] from the torch generator.
+
+    With the HIP-backed model on a device tensor the chunk rows come from one ``flowse_stft_compress_chunks`` launch and
+    the waveform from one ``flowse_istft_decompress_chunks`` launch; nothing of the recording's length but its samples,
+    the chunk rows and the waveform is held.  With ``VF_fn`` or CPU tensors the same steps run as torch ops -- stft,
+    spec_fwd, index, sampler, blend (float64, rounded to complex64), spec_back, istft: the oracle composition."""
+    from flowmse_amd.evaluate import enhance_waveform
+    from flowmse_amd.sampling import get_white_box_solver
+    if int(batch) < 1:
+        raise ValueError(f"enhance_long: batch must be >= 1, got {batch}")
+    if z is not None and noise_key is not None:
+        raise ValueError("enhance_long: pass either z or noise_key, not both")
+    batch, Tc = int(batch), int(chunk_frames)
+    device = torch.device(device) if device is not None else y.device
+    if y.dim() != 2 or y.size(0) != 1:
+        raise ValueError(f"enhance_long takes one recording [1, samples], got {tuple(y.shape)}")
+    dm = model.data_module
+    L = y.size(1)
+    K, hop, Tg = plan_chunks(L // dm.hop_length + 1, Tc, overlap_frames)
+    if K == 1:
+        return enhance_waveform(model, y, N=N, T_rev=T_rev, t_eps=t_eps, odesolver=odesolver, z=z, VF_fn=VF_fn,
+                                device=device, noise_keys=None if noise_key is None else [noise_key],
+                                noise_seed=noise_seed)
+    norm_factor = y.abs().max().item()
+    y = y.to(device)
+    fused = VF_fn is None and hasattr(dm, "fused_ok") and dm.fused_ok(y)
+    if fused:                      # the chunk rows straight from the samples: one HIP kernel, no global spectrogram
+        Y = dm.analyze_chunks(y / norm_factor, Tc, hop)
+        with torch.cuda.device(device):
+            model.dnn.reserve(batch, Y.shape[2], Tc)     # the workspace of a full group, whatever K is
+    else:
+        S = torch.unsqueeze(model._forward_transform(model._stft(y / norm_factor)), 0)
+        S = torch.nn.functional.pad(S, (0, Tg - S.size(3), 0, 0))
+        Y = torch.cat([S[..., k * hop:k * hop + Tc] for k in range(K)], dim=0)
+    zg = _chunk_noise(z, noise_key, Y, Tg)
+    field = VF_fn if VF_fn is not None else model
+    rows = []
+    for k0 in range(0, K, batch):
+        k1 = min(k0 + batch, K)
+        Yg = Y[k0:k1].contiguous()
+        if zg is None:
+            kw = dict(noise_keys=[noise_key] * (k1 - k0), noise_seed=noise_seed,
+                      noise_frame0=[k * hop for k in range(k0, k1)])
+        else:
+            kw = dict(z=torch.cat([zg[..., k * hop:k * hop + Tc] for k in range(k0, k1)], dim=0).contiguous())
+        rows.append(get_white_box_solver(odesolver, model.ode, field, Y=Yg, Y_prior=Yg, T_rev=T_rev, t_eps=t_eps, N=N,
+                                         **kw)()[0])
+    sample = torch.cat(rows, dim=0)
+    if fused:                      # cross-fade + decompression + iSTFT + rescale: one HIP kernel
+        return dm.synthesize_chunks(sample, hop, L, norm_factor).squeeze().cpu().numpy()
+    spec = torch.from_numpy(blend_chunks_reference(sample, hop)).to(torch.complex64).to(sample.device)
+    x_hat = model.to_audio(spec.squeeze(), L)
+    return (x_hat * norm_factor).squeeze().cpu().numpy()

@@ -449,11 +449,18 @@ int launch_stft_compress(const float* sig, int B, int L, float scale_in, float* 
                          float exponent, hipStream_t s);
 int launch_istft_decompress(const float* spec_c64, int B, int T, int Tpad, float factor, float exponent, float* out,
                             int Lout, float scale_out, hipStream_t s);
+// the same pair for ONE recording held as K chunks [K,1,256,Tc] that start `hop` frames apart: chunk rows are slices of
+// the recording's spectrogram (frames past L / 128 + 1 zero); synthesis cross-fades the Tc - hop shared frames
+int launch_stft_compress_chunks(const float* sig, int L, float scale_in, float* out_c64, int K, int Tc, int hop,
+                                float factor, float exponent, hipStream_t s);
+int launch_istft_decompress_chunks(const float* chunks_c64, int K, int Tc, int hop, float factor, float exponent,
+                                   float* out, int Lout, float scale_out, hipStream_t s);
 // out = y + sigma * z   (complex64 as float pairs)
 int launch_axpy(const float* y, const float* z, float sigma, int64_t n, float* out, hipStream_t s);
 // out = y + sigma * z (y != null) or out = z (y == null), z = the keyed Philox noise of noise.hip; [B,1,F,T] complex64,
-// T even, 16-byte aligned pointers, keys: B device words
-int launch_keyed_noise(const float* y, const uint64_t* keys, uint64_t seed, float sigma, float* out, int B, int F, int T,
-                       hipStream_t s);
+// T even, 16-byte aligned pointers, keys: B device words; frame0 (may be null): B device words, the even absolute frame
+// each row starts at
+int launch_keyed_noise(const float* y, const uint64_t* keys, const int32_t* frame0, uint64_t seed, float sigma, float* out,
+                       int B, int F, int T, hipStream_t s);
 
 }  // namespace flowse

@@ -715,14 +715,49 @@ static int keyed_args_ok(const char* who, const void* y, bool need_y, const uint
 int flowse_prior_sample_keyed(const void* y, const uint64_t* keys_dev, uint64_t seed, float sigma, void* x_out, int B, int F,
                               int T, void* stream) {
     if (const int rc = keyed_args_ok("flowse_prior_sample_keyed", y, true, keys_dev, x_out, B, F, T)) return rc;
-    return launch_keyed_noise(static_cast<const float*>(y), keys_dev, seed, sigma, static_cast<float*>(x_out), B, F, T,
-                              static_cast<hipStream_t>(stream));
+    return launch_keyed_noise(static_cast<const float*>(y), keys_dev, nullptr, seed, sigma, static_cast<float*>(x_out), B,
+                              F, T, static_cast<hipStream_t>(stream));
 }
 
 int flowse_op_keyed_noise(const uint64_t* keys_dev, uint64_t seed, void* z_out_c64, int B, int F, int T, void* stream) {
     if (const int rc = keyed_args_ok("flowse_op_keyed_noise", nullptr, false, keys_dev, z_out_c64, B, F, T)) return rc;
-    return launch_keyed_noise(nullptr, keys_dev, seed, 0.f, static_cast<float*>(z_out_c64), B, F, T,
+    return launch_keyed_noise(nullptr, keys_dev, nullptr, seed, 0.f, static_cast<float*>(z_out_c64), B, F, T,
                               static_cast<hipStream_t>(stream));
+}
+
+// The frame offsets of the *_at calls are read back and checked here, on the host side of the call (one stream
+// synchronisation): an odd offset would pair the Philox words of a frame differently than the offset-free stream does.
+static int frame0_ok(const char* who, const int32_t* frame0_dev, int B, int T, hipStream_t s) {
+    if (!frame0_dev) {
+        set_error("%s: null frame0_dev", who);
+        return ERR_ARG;
+    }
+    std::vector<int32_t> h((size_t)B);
+    FLOWSE_HIP(hipMemcpyAsync(h.data(), frame0_dev, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    FLOWSE_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b)
+        if (h[b] < 0 || (h[b] & 1) || h[b] > INT32_MAX - T) {
+            set_error("%s: frame0[%d] = %d must be even, >= 0 and <= INT32_MAX - T", who, b, (int)h[b]);
+            return ERR_ARG;
+        }
+    return OK;
+}
+
+int flowse_prior_sample_keyed_at(const void* y, const uint64_t* keys_dev, const int32_t* frame0_dev, uint64_t seed,
+                                 float sigma, void* x_out, int B, int F, int T, void* stream) {
+    if (const int rc = keyed_args_ok("flowse_prior_sample_keyed_at", y, true, keys_dev, x_out, B, F, T)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = frame0_ok("flowse_prior_sample_keyed_at", frame0_dev, B, T, s)) return rc;
+    return launch_keyed_noise(static_cast<const float*>(y), keys_dev, frame0_dev, seed, sigma, static_cast<float*>(x_out),
+                              B, F, T, s);
+}
+
+int flowse_op_keyed_noise_at(const uint64_t* keys_dev, const int32_t* frame0_dev, uint64_t seed, void* z_out_c64, int B,
+                             int F, int T, void* stream) {
+    if (const int rc = keyed_args_ok("flowse_op_keyed_noise_at", nullptr, false, keys_dev, z_out_c64, B, F, T)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = frame0_ok("flowse_op_keyed_noise_at", frame0_dev, B, T, s)) return rc;
+    return launch_keyed_noise(nullptr, keys_dev, frame0_dev, seed, 0.f, static_cast<float*>(z_out_c64), B, F, T, s);
 }
 
 int flowse_euler_sample(flowse_model* m, void* x_inout, const void* y, const float* ts, const float* dts, int N, int B,
@@ -909,6 +944,26 @@ int flowse_istft_decompress(const void* spec_c64, int B, int T, int Tpad, float 
     }
     return launch_istft_decompress(static_cast<const float*>(spec_c64), B, T, Tpad, factor, exponent, out, Lout,
                                    scale_out, static_cast<hipStream_t>(stream));
+}
+
+int flowse_stft_compress_chunks(const float* sig, int L, float scale_in, void* out_c64, int K, int Tc, int hop, float factor,
+                                float exponent, void* stream) {
+    if (!sig || !out_c64) {
+        set_error("flowse_stft_compress_chunks: null argument");
+        return ERR_ARG;
+    }
+    return launch_stft_compress_chunks(sig, L, scale_in, static_cast<float*>(out_c64), K, Tc, hop, factor, exponent,
+                                       static_cast<hipStream_t>(stream));
+}
+
+int flowse_istft_decompress_chunks(const void* chunks_c64, int K, int Tc, int hop, float factor, float exponent, float* out,
+                                   int Lout, float scale_out, void* stream) {
+    if (!chunks_c64 || !out) {
+        set_error("flowse_istft_decompress_chunks: null argument");
+        return ERR_ARG;
+    }
+    return launch_istft_decompress_chunks(static_cast<const float*>(chunks_c64), K, Tc, hop, factor, exponent, out, Lout,
+                                          scale_out, static_cast<hipStream_t>(stream));
 }
 
 int flowse_profile_begin(flowse_model* m, int mode) {

@@ -5,6 +5,7 @@
 //
 //   Philox4x32-10 (Salmon et al., SC'11; Random123 known answers in tests/test_keyed_noise_host.py)
 //   counter = (t >> 1, f, lo32(key_b), hi32(key_b)),  Philox key = (lo32(seed), hi32(seed))
+//   t is the ABSOLUTE frame of the utterance: frame0_b + the frame's index in the row (frame0_b = 0 without offsets)
 //   words (0, 1) -> the value at the even frame t, words (2, 3) -> the value at t + 1
 //   u1 = ((w_a >> 9) + 0.5) * 2^-23 in (0, 1),  u2 = (w_b >> 8) * 2^-24 in [0, 1)      (both exact in fp32)
 //   z  = sqrtf(-logf(u1)) * (cospif(2 u2) + i sinpif(2 u2))                                (E|z|^2 = 1)
@@ -37,15 +38,18 @@ __device__ __forceinline__ float2 complex_normal(uint32_t wa, uint32_t wb) {
 
 // One thread per Philox call: frames (2 t2, 2 t2 + 1) of one bin of one row = one 16-byte load and store.  The float4
 // index of a thread IS its linear index (rows are [F][T] complex, T even).  ADD: out = y + sigma * z, else out = z.
-template <bool ADD>
+// AT: row b starts at the even absolute frame frame0[b] of its utterance (a chunk of a recording).
+template <bool ADD, bool AT>
 __global__ __launch_bounds__(256) void keyed_noise_kernel(const float4* __restrict__ y, const uint64_t* __restrict__ keys,
-                                                          uint32_t seed_lo, uint32_t seed_hi, float sigma, int F, int Th,
-                                                          int64_t n, float4* __restrict__ out) {
+                                                          const int32_t* __restrict__ frame0, uint32_t seed_lo,
+                                                          uint32_t seed_hi, float sigma, int F, int Th, int64_t n,
+                                                          float4* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const uint32_t t2 = (uint32_t)(i % Th);
+        uint32_t t2 = (uint32_t)(i % Th);
         const int64_t row = i / Th;
         const uint32_t f = (uint32_t)(row % F);
         const uint64_t key = keys[row / F];
+        if (AT) t2 += (uint32_t)frame0[row / F] >> 1;
         uint32_t w[4];
         philox4x32_10(t2, f, (uint32_t)key, (uint32_t)(key >> 32), seed_lo, seed_hi, w);
         const float2 za = complex_normal(w[0], w[1]), zb = complex_normal(w[2], w[3]);
@@ -59,19 +63,25 @@ __global__ __launch_bounds__(256) void keyed_noise_kernel(const float4* __restri
     }
 }
 
-int launch_keyed_noise(const float* y, const uint64_t* keys, uint64_t seed, float sigma, float* out, int B, int F, int T,
-                       hipStream_t s) {
+template <bool ADD, bool AT>
+static void launch_one(unsigned blocks, hipStream_t s, const float* y, const uint64_t* keys, const int32_t* frame0,
+                       uint32_t lo, uint32_t hi, float sigma, int F, int Th, int64_t n, float* out) {
+    hipLaunchKernelGGL((keyed_noise_kernel<ADD, AT>), dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(y),
+                       keys, frame0, lo, hi, sigma, F, Th, n, reinterpret_cast<float4*>(out));
+}
+
+int launch_keyed_noise(const float* y, const uint64_t* keys, const int32_t* frame0, uint64_t seed, float sigma, float* out,
+                       int B, int F, int T, hipStream_t s) {
     const int Th = T / 2;
     const int64_t n = (int64_t)B * F * Th;
     int64_t blocks = (n + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
-    if (y)
-        hipLaunchKernelGGL(keyed_noise_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s,
-                           reinterpret_cast<const float4*>(y), keys, lo, hi, sigma, F, Th, n, reinterpret_cast<float4*>(out));
-    else
-        hipLaunchKernelGGL(keyed_noise_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s,
-                           static_cast<const float4*>(nullptr), keys, lo, hi, 0.f, F, Th, n, reinterpret_cast<float4*>(out));
+    const unsigned g = (unsigned)blocks;
+    if (y && frame0) launch_one<true, true>(g, s, y, keys, frame0, lo, hi, sigma, F, Th, n, out);
+    else if (y) launch_one<true, false>(g, s, y, keys, nullptr, lo, hi, sigma, F, Th, n, out);
+    else if (frame0) launch_one<false, true>(g, s, nullptr, keys, frame0, lo, hi, 0.f, F, Th, n, out);
+    else launch_one<false, false>(g, s, nullptr, keys, nullptr, lo, hi, 0.f, F, Th, n, out);
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

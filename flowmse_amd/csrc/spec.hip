@@ -47,12 +47,17 @@ static int ensure_tables(float** out) {
 }
 
 // grid (Tpad, B), 256 threads = 256 bins.  Frames t >= T are the zero padding of pad_spec.
+// Row b of the output holds frames row_frame0 * b + [0, Tpad) of signal sig + row_sig * b: (0, L) for a batch of
+// utterances, (hop, 0) for the chunks of one recording -- the same arithmetic per frame, so a chunk row is bit for bit
+// a slice of the whole spectrogram.
 __global__ __launch_bounds__(256) void stft_compress_kernel(const float* __restrict__ sig, int L, float scale_in,
                                                             const float* __restrict__ tab, float2* __restrict__ out,
-                                                            int T, int Tpad, float factor, float exponent) {
+                                                            int T, int Tpad, float factor, float exponent,
+                                                            int row_frame0, int row_sig) {
     __shared__ float xw[NFFT], ct[NFFT], st[NFFT];
-    const int t = blockIdx.x, b = blockIdx.y, f = threadIdx.x;
-    float2* dst = out + ((int64_t)b * NBIN + f) * Tpad + t;
+    const int b = blockIdx.y, f = threadIdx.x;
+    const int t = b * row_frame0 + blockIdx.x;
+    float2* dst = out + ((int64_t)b * NBIN + f) * Tpad + blockIdx.x;
     if (t >= T) {
         *dst = make_float2(0.f, 0.f);
         return;
@@ -61,7 +66,7 @@ __global__ __launch_bounds__(256) void stft_compress_kernel(const float* __restr
         int j = t * HOP + n - PADC;                    // centre=True, reflect padding
         if (j < 0) j = -j;
         if (j >= L) j = 2 * (L - 1) - j;
-        xw[n] = sig[(int64_t)b * L + j] * scale_in * tab[n];
+        xw[n] = sig[(int64_t)b * row_sig + j] * scale_in * tab[n];
         ct[n] = tab[NFFT + n];
         st[n] = tab[2 * NFFT + n];
     }
@@ -81,11 +86,28 @@ __global__ __launch_bounds__(256) void stft_compress_kernel(const float* __restr
     *dst = make_float2(re * s, im * s);
 }
 
+// Frame t of a recording held as K chunks [K][NBIN][Tc] that start `hop` frames apart (To = Tc - hop <= hop frames of
+// overlap, so at most two chunks cover a frame): chunk k = min(t / hop, K - 1) at j = t - k hop; in the first To frames
+// of every chunk but the first, the linear cross-fade  a + w (b - a),  w = (j + 0.5) / To,  from the previous chunk's
+// tail a to this chunk's head b -- on the compressed value, before spec_back.
+__device__ __forceinline__ float2 seam_frame(const float2* __restrict__ chunks, int f, int t, int K, int Tc, int hop) {
+    int k = t / hop;
+    if (k > K - 1) k = K - 1;
+    const int j = t - k * hop, To = Tc - hop;
+    const float2 b = chunks[((int64_t)k * NBIN + f) * Tc + j];
+    if (k == 0 || j >= To) return b;
+    const float2 a = chunks[((int64_t)(k - 1) * NBIN + f) * Tc + j + hop];
+    const float w = ((float)j + 0.5f) / (float)To;
+    return make_float2(a.x + w * (b.x - a.x), a.y + w * (b.y - a.y));
+}
+
 // grid (ceil(Lout / 128), B), 256 threads: sample = tid & 127, the two halves split the bins.
+// SEAM: `spec` is the chunk stack above (B == 1, T == Tpad == Tg frames); else [B][NBIN][Tpad].
+template <bool SEAM>
 __global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __restrict__ spec, int T, int Tpad,
                                                                float factor, float exponent,
                                                                const float* __restrict__ tab, float* __restrict__ out,
-                                                               int Lout, float scale_out) {
+                                                               int Lout, float scale_out, int K, int Tc, int hop) {
     constexpr int NF = 5;                               // frames that can overlap a block of HOP samples
     __shared__ float2 Xs[NF][NBIN];
     __shared__ float ct[NFFT], st[NFFT], win[NFFT];
@@ -105,7 +127,7 @@ __global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __r
         const int t = t_lo + fr;
         float2 z = make_float2(0.f, 0.f);
         if (t < T) {
-            z = spec[((int64_t)b * NBIN + f) * Tpad + t];
+            z = SEAM ? seam_frame(spec, f, t, K, Tc, hop) : spec[((int64_t)b * NBIN + f) * Tpad + t];
             // spec_back: (|z| / factor)^(1/e) * exp(j arg z)
             z.x /= factor;
             z.y /= factor;
@@ -159,7 +181,30 @@ int launch_stft_compress(const float* sig, int B, int L, float scale_in, float* 
     int rc = ensure_tables(&tab);
     if (rc != OK) return rc;
     hipLaunchKernelGGL(stft_compress_kernel, dim3(Tpad, B), dim3(256), 0, s, sig, L, scale_in, tab,
-                       reinterpret_cast<float2*>(out_c64), T, Tpad, factor, exponent);
+                       reinterpret_cast<float2*>(out_c64), T, Tpad, factor, exponent, 0, L);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+// geometry of a chunk stack: K chunks of Tc frames, `hop` apart, at most two over any frame
+static bool chunks_ok(int K, int Tc, int hop) {
+    return K >= 1 && K <= 65535 && Tc >= 1 && hop >= 1 && hop <= Tc && 2 * (int64_t)hop >= Tc &&
+           (int64_t)(K - 1) * hop + Tc <= (1 << 23);
+}
+
+int launch_stft_compress_chunks(const float* sig, int L, float scale_in, float* out_c64, int K, int Tc, int hop,
+                                float factor, float exponent, hipStream_t s) {
+    const int T = L / HOP + 1;
+    if (L <= PADC || !chunks_ok(K, Tc, hop) || (int64_t)(K - 1) * hop + Tc < T) {
+        set_error("stft chunks: need L > %d, 1 <= hop <= Tc <= 2 hop, 1 <= K <= 65535 and (K - 1) hop + Tc >= L / %d + 1 "
+                  "(got L=%d K=%d Tc=%d hop=%d)", PADC, HOP, L, K, Tc, hop);
+        return ERR_SHAPE;
+    }
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(stft_compress_kernel, dim3(Tc, K), dim3(256), 0, s, sig, L, scale_in, tab,
+                       reinterpret_cast<float2*>(out_c64), T, Tc, factor, exponent, hop, 0);
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }
@@ -173,9 +218,27 @@ int launch_istft_decompress(const float* spec_c64, int B, int T, int Tpad, float
     float* tab = nullptr;
     int rc = ensure_tables(&tab);
     if (rc != OK) return rc;
-    hipLaunchKernelGGL(istft_decompress_kernel, dim3((Lout + HOP - 1) / HOP, B), dim3(256), 0, s,
+    hipLaunchKernelGGL(istft_decompress_kernel<false>, dim3((Lout + HOP - 1) / HOP, B), dim3(256), 0, s,
                        reinterpret_cast<const float2*>(spec_c64), T, Tpad, factor, exponent, tab, out, Lout,
-                       scale_out);
+                       scale_out, 0, 0, 0);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+int launch_istft_decompress_chunks(const float* chunks_c64, int K, int Tc, int hop, float factor, float exponent,
+                                   float* out, int Lout, float scale_out, hipStream_t s) {
+    const int64_t Tg = (int64_t)(K - 1) * hop + Tc;
+    if (!chunks_ok(K, Tc, hop) || Lout < 1 || Lout > (Tg - 1) * HOP + NFFT - PADC || factor == 0.f) {
+        set_error("istft chunks: need 1 <= hop <= Tc <= 2 hop, 1 <= K <= 65535, 1 <= Lout <= 128 (Tg - 1) + 255 and "
+                  "factor != 0 (got K=%d Tc=%d hop=%d Lout=%d)", K, Tc, hop, Lout);
+        return ERR_SHAPE;
+    }
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(istft_decompress_kernel<true>, dim3((Lout + HOP - 1) / HOP, 1), dim3(256), 0, s,
+                       reinterpret_cast<const float2*>(chunks_c64), (int)Tg, (int)Tg, factor, exponent, tab, out, Lout,
+                       scale_out, K, Tc, hop);
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

@@ -94,6 +94,39 @@ class SpecTransform:
                                                         float(scale), _lib.current_stream()))
         return out
 
+    # ---- one recording as overlapping chunks (flowmse_amd.chunked) -----------------------------------
+    def analyze_chunks(self, sig, Tc, hop, scale=1.0):
+        """The chunk rows of ONE recording in one kernel: sig float32 [1, L] on 'cuda' -> complex64 [K, 1, 256, Tc], row k
+        = frames [k hop, k hop + Tc) of ``analyze(sig)`` bit for bit (zeros past L // 128 + 1), K the chunk count of
+        ``chunked.plan_chunks(L // 128 + 1, Tc, Tc - hop)``."""
+        from flowmse_amd import _lib
+        from flowmse_amd.chunked import plan_chunks
+        sig = sig.contiguous().float()
+        if sig.dim() != 2 or sig.shape[0] != 1:
+            raise ValueError(f"analyze_chunks takes one recording [1, L], got {tuple(sig.shape)}")
+        L = sig.shape[1]
+        K, hop, _ = plan_chunks(L // self.hop_length + 1, Tc, Tc - hop)
+        out = torch.empty(K, 1, 256, Tc, dtype=torch.complex64, device=sig.device)
+        with torch.cuda.device(sig.device):
+            _lib.check(_lib.lib.flowse_stft_compress_chunks(_lib.ptr(sig), L, float(scale), _lib.ptr(out), K, Tc, hop,
+                                                            float(self.spec_factor), float(self.spec_abs_exponent),
+                                                            _lib.current_stream()))
+        return out
+
+    def synthesize_chunks(self, chunks, hop, length, scale=1.0):
+        """Cross-fade + spec_back + istft + rescale in one kernel: chunks complex64 [K, 1, 256, Tc] that start ``hop``
+        frames apart -> [1, length].  The Tc - hop shared frames are blended linearly on the compressed values
+        (``chunked.blend_chunks_reference`` states the rule); all (K - 1) hop + Tc frames take part in the overlap-add."""
+        from flowmse_amd import _lib
+        chunks = chunks.contiguous()
+        K, _, F, Tc = chunks.shape
+        out = torch.empty(1, length, dtype=torch.float32, device=chunks.device)
+        with torch.cuda.device(chunks.device):
+            _lib.check(_lib.lib.flowse_istft_decompress_chunks(_lib.ptr(chunks), K, Tc, int(hop), float(self.spec_factor),
+                                                               float(self.spec_abs_exponent), _lib.ptr(out), length,
+                                                               float(scale), _lib.current_stream()))
+        return out
+
     # ---- STFT pair ------------------------------------------------------------------------------
     def _stft_args(self, ref):
         return dict(n_fft=self.n_fft, hop_length=self.hop_length, window=self._win(ref), center=True)

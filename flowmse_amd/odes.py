@@ -74,7 +74,7 @@ class FLOWMATCHING(ODE):
         """sigma(1) as the float32 number the reference evaluates for a batch of ones (odes.py:96)."""
         return float(self._std(torch.ones(1, dtype=torch.float32)))
 
-    def prior_sampling(self, shape, y, z=None, *, keys=None, seed=0):
+    def prior_sampling(self, shape, y, z=None, *, keys=None, seed=0, frame0=None):
         """Returns ``(x_T, z)``.  ``z`` may be passed in for reproducible trajectories.
 
         ``keys`` (one 64-bit utterance key per row of ``y`` [B,1,F,T], a sequence of ints or an int64 tensor holding
@@ -82,13 +82,19 @@ class FLOWMATCHING(ODE):
         process-wide generator: the noise of a row then depends on (seed, key, bin, frame) only.  On a HIP tensor this
         is one ``flowse_prior_sample_keyed`` launch that generates the noise in registers, and the returned ``z`` is
         ``None`` -- the noise never exists as a tensor there.  On a CPU tensor it is the float64 restatement rounded to
-        complex64, and ``z`` is returned.  ``keys`` together with ``z`` raises ``ValueError``."""
+        complex64, and ``z`` is returned.  ``keys`` together with ``z`` raises ``ValueError``.
+
+        ``frame0`` (with ``keys`` only: one even frame offset >= 0 per row) addresses the stream at absolute frames: row b
+        gets the noise of frames ``frame0[b] ..`` of its key (``flowse_prior_sample_keyed_at``), so the chunks of one long
+        recording share their utterance's key and start from the same ``x_T`` wherever they overlap."""
         if tuple(shape) != tuple(y.shape):
             warnings.warn(f"prior_sampling: requested shape {tuple(shape)} differs from y {tuple(y.shape)}; using y's")
         if keys is not None:
             if z is not None:
                 raise ValueError("prior_sampling: pass either z or keys, not both")
-            return self._prior_sampling_keyed(y, keys, seed)
+            return self._prior_sampling_keyed(y, keys, seed, frame0)
+        if frame0 is not None:
+            raise ValueError("prior_sampling: frame0 addresses the keyed stream; pass keys")
         z = torch.randn_like(y) if z is None else z
         if not y.is_cuda:
             return y + z * _bcast(self._std(torch.ones(y.shape[0], device=y.device))), z
@@ -100,7 +106,7 @@ class FLOWMATCHING(ODE):
                                                     y.numel(), _lib.current_stream()))
         return x_T, z
 
-    def _prior_sampling_keyed(self, y, keys, seed):
+    def _prior_sampling_keyed(self, y, keys, seed, frame0=None):
         if y.dim() != 4 or y.shape[1] != 1 or y.dtype != torch.complex64:
             raise ValueError(f"prior_sampling(keys=...): y must be complex64 [B,1,F,T], got {y.dtype} {tuple(y.shape)}")
         B, _, F, T = y.shape
@@ -113,9 +119,13 @@ class FLOWMATCHING(ODE):
             key_list = [int(k) & 0xFFFFFFFFFFFFFFFF for k in keys]
             if len(key_list) != B:
                 raise ValueError(f"prior_sampling: {len(key_list)} keys for a batch of {B}")
+        if frame0 is not None:
+            from flowmse_amd.util.noise import check_frame0
+            frame0 = check_frame0(frame0, B)
         if not y.is_cuda:
             from flowmse_amd.util.noise import keyed_noise_reference
-            z = torch.from_numpy(keyed_noise_reference([k & 0xFFFFFFFFFFFFFFFF for k in key_list], seed, F, T)).to(torch.complex64)
+            z = torch.from_numpy(keyed_noise_reference([k & 0xFFFFFFFFFFFFFFFF for k in key_list], seed, F, T,
+                                                       frame0=frame0)).to(torch.complex64)
             return y + z * self.prior_std(), z
         from flowmse_amd import _lib
         if T % 2:
@@ -127,6 +137,12 @@ class FLOWMATCHING(ODE):
         y = y.contiguous()
         x_T = torch.empty_like(y)
         with torch.cuda.device(y.device):
-            _lib.check(_lib.lib.flowse_prior_sample_keyed(_lib.ptr(y), _lib.ptr(kd), seed, self.prior_std(), _lib.ptr(x_T),
-                                                          B, F, T, _lib.current_stream()))
+            if frame0 is None:
+                _lib.check(_lib.lib.flowse_prior_sample_keyed(_lib.ptr(y), _lib.ptr(kd), seed, self.prior_std(),
+                                                              _lib.ptr(x_T), B, F, T, _lib.current_stream()))
+            else:
+                fd = torch.tensor(frame0, dtype=torch.int32, device=y.device)
+                _lib.check(_lib.lib.flowse_prior_sample_keyed_at(_lib.ptr(y), _lib.ptr(kd), _lib.ptr(fd), seed,
+                                                                 self.prior_std(), _lib.ptr(x_T), B, F, T,
+                                                                 _lib.current_stream()))
         return x_T, None

@@ -54,18 +54,24 @@ def _fused_tableau(odesolver_cls):
     return name
 
 
-def _prior(ode, P, z, noise_keys, noise_seed):
+def _prior(ode, P, z, noise_keys, noise_seed, noise_frame0=None):
     """The prior sample of one solver call: explicit ``z``, the keyed stream (``noise_keys``: one 64-bit key per row of
-    ``P``), or the process-wide generator -- each through the call ``prior_sampling`` had before keys existed."""
+    ``P``; ``noise_frame0``: the absolute frame each row starts at), or the process-wide generator -- each through the call
+    ``prior_sampling`` had before keys (or offsets) existed."""
+    if noise_frame0 is not None:
+        if noise_keys is None:
+            raise ValueError("noise_frame0 addresses the keyed noise stream; pass noise_keys")
+        return ode.prior_sampling(P.shape, P, z, keys=noise_keys, seed=noise_seed, frame0=noise_frame0)[0]
     if noise_keys is not None:
         return ode.prior_sampling(P.shape, P, z, keys=noise_keys, seed=noise_seed)[0]
     return ode.prior_sampling(P.shape, P, z)[0] if z is not None else ode.prior_sampling(P.shape, P)[0]
 
 
 def get_white_box_solver(odesolver_name, ode, VF_fn, Y, Y_prior=None, T_rev=1.0, t_eps=0.03, N=30, z=None,
-                         noise_keys=None, noise_seed=0, **kwargs):
+                         noise_keys=None, noise_seed=0, noise_frame0=None, **kwargs):
     """Returns ``ode_solver() -> (x_result, N)``.  Extra keyword ``z``: explicit prior noise (reproducibility);
-    ``noise_keys`` / ``noise_seed``: the keyed noise stream instead (``FLOWMATCHING.prior_sampling``), one key per row."""
+    ``noise_keys`` / ``noise_seed``: the keyed noise stream instead (``FLOWMATCHING.prior_sampling``), one key per row;
+    ``noise_frame0``: with keys, the even absolute frame each row starts at in its utterance (chunks of a recording)."""
     odesolver_cls = ODEsolverRegistry.get_by_name(odesolver_name)
     odesolver = odesolver_cls(ode, VF_fn)
     fused = _fused_tableau(odesolver_cls) is not None and hasattr(VF_fn, "rk_sample_") and Y.is_cuda
@@ -74,7 +80,7 @@ def get_white_box_solver(odesolver_name, ode, VF_fn, Y, Y_prior=None, T_rev=1.0,
         with torch.no_grad():
             if Y_prior is None:
                 Y_prior = Y
-            xt = _prior(ode, Y_prior, z, noise_keys, noise_seed).to(Y_prior.device)
+            xt = _prior(ode, Y_prior, z, noise_keys, noise_seed, noise_frame0).to(Y_prior.device)
             # host copy of the grid: the values equal torch.linspace(..., device=Y.device) of the reference
             timesteps, stepsizes = time_grid(T_rev, t_eps, N)
             if fused:

@@ -9,7 +9,9 @@ The stream is a public contract ("Keyed noise stream"): for the 
     z  = sqrt(-log(u1)) * exp(2 pi i u2)                     complex standard normal, E|z|^2 = 1
 
 so the value at (f, t) depends on nothing but (seed, k, f, t): not on the batch, the row, the padded length or the
-order of calls.  The kernel evaluates the last line in fp32; this module evaluates it in float64.
+order of calls.  ``t`` is the ABSOLUTE frame of the utterance: a row that starts at frame ``frame0`` of it (a chunk of a
+long recording, ``flowmse_amd.chunked``) uses ``t = frame0 + index in the row``.  The kernel evaluates the last line in
+fp32; this module evaluates it in float64.
 """
 import hashlib
 import os
@@ -37,16 +39,30 @@ def philox4x32_10(ctr, key):
     return tuple(int(v) for v in c) if scalar else tuple(c)
 
 
-def keyed_noise_reference(keys, seed, F, T):
-    """The noise of the stream above in float64: complex128 array [B, 1, F, T] for the B utterance keys ``keys``."""
+def check_frame0(frame0, B):
+    """The per-row frame offsets of the keyed stream as a list of B ints: each even (an odd offset would pair the Philox
+    words of a frame differently than the offset-free stream does) and >= 0, else ``ValueError``."""
+    frame0 = [int(v) for v in (frame0.reshape(-1).tolist() if hasattr(frame0, "reshape") else frame0)]
+    if len(frame0) != B:
+        raise ValueError(f"frame0: {len(frame0)} offsets for {B} rows")
+    if any(v < 0 or v % 2 for v in frame0):
+        raise ValueError(f"frame0: every offset must be even and >= 0, got {frame0}")
+    return frame0
+
+
+def keyed_noise_reference(keys, seed, F, T, frame0=None):
+    """The noise of the stream above in float64: complex128 array [B, 1, F, T] for the B utterance keys ``keys``.
+    ``frame0`` (one even offset >= 0 per key): row b holds frames ``frame0[b] .. frame0[b] + T - 1`` of its key's stream."""
     keys = [int(k) & _MASK64 for k in np.asarray(keys, dtype=np.uint64).reshape(-1).tolist()]
     seed = int(seed) & _MASK64
     F, T = int(F), int(T)
-    t = np.arange(T, dtype=np.uint64)[None, :]
+    frame0 = [0] * len(keys) if frame0 is None else check_frame0(frame0, len(keys))
+    t0 = np.arange(T, dtype=np.uint64)[None, :]
     f = np.arange(F, dtype=np.uint64)[:, None]
-    odd = (t & np.uint64(1)).astype(bool)
+    odd = (t0 & np.uint64(1)).astype(bool)                     # the offsets are even: parity is the row's own
     out = np.empty((len(keys), 1, F, T), dtype=np.complex128)
     for b, k in enumerate(keys):
+        t = t0 + np.uint64(frame0[b])
         w = philox4x32_10((t >> np.uint64(1), f, k & _MASK32, k >> 32), (seed & _MASK32, seed >> 32))
         wa = np.where(odd, w[2], w[0])
         wb = np.where(odd, w[3], w[1])

@@ -178,6 +178,18 @@ int flowse_prior_sample_keyed(const void* y, const uint64_t* keys_dev, uint64_t 
                               int F, int T, void* stream);
 /* The bare noise z [B,1,F,T] complex64 of the stream above. */
 int flowse_op_keyed_noise(const uint64_t* keys_dev, uint64_t seed, void* z_out_c64, int B, int F, int T, void* stream);
+/* The same two calls for rows that do not start at frame 0 of their utterance (the chunks of a long recording,
+ * flowse_stft_compress_chunks): frame0_dev holds one int32 per row in device memory, the ABSOLUTE frame the row starts
+ * at, and counter word 0 becomes (frame0[b] + t) >> 1 -- nothing else in the stream changes, so row b equals frames
+ * frame0[b] .. frame0[b] + T - 1 of the offset-free stream of its key, bit for bit, and rows of one key that overlap
+ * get the same noise where they do.  Each offset must be even (an odd one would pair the words of a frame differently),
+ * >= 0 and <= INT32_MAX - T: the call copies the B offsets to the host and checks them BEFORE it launches, which
+ * synchronises `stream` once -- unlike the offset-free calls it is not free of host synchronisation and cannot be
+ * captured into a graph.  A bad offset returns FLOWSE_ERR_ARG and writes nothing. */
+int flowse_prior_sample_keyed_at(const void* y, const uint64_t* keys_dev, const int32_t* frame0_dev, uint64_t seed,
+                                 float sigma, void* x_out, int B, int F, int T, void* stream);
+int flowse_op_keyed_noise_at(const uint64_t* keys_dev, const int32_t* frame0_dev, uint64_t seed, void* z_out_c64, int B,
+                             int F, int T, void* stream);
 /* N Euler steps in place on x (ode_solver loop, flowmse/sampling/__init__.py:45-57, with
  * EulerODEsolver.update_fn, sampling/odesolvers.py:42-47):  for i: x <- x + VF(x, ts[i], y) * (-dts[i]).
  * ts, dts: HOST float32 arrays of length N (the caller reproduces torch.linspace and the step rule, including
@@ -276,6 +288,26 @@ int flowse_stft_compress(const float* sig, int B, int L, float scale_in, void* o
                          float exponent, void* stream);
 int flowse_istft_decompress(const void* spec_c64, int B, int T, int Tpad, float factor, float exponent, float* out,
                             int Lout, float scale_out, void* stream);
+/* ---- one recording as overlapping chunks (opt-in; NOT the reference's computation for a long file) ----------
+ * A recording of L samples has T = L / 128 + 1 frames.  It is held as K chunks of Tc frames that start `hop` frames apart:
+ * chunk k covers the recording's frames [k hop, k hop + Tc), the last To = Tc - hop of which it shares with chunk k + 1;
+ * Tg = (K - 1) hop + Tc frames in all.  Geometry accepted by both calls: 1 <= hop <= Tc <= 2 hop (at most two chunks over
+ * any frame), 1 <= K <= 65535, Tg <= 2^23; anything else returns FLOWSE_ERR_SHAPE and launches nothing.
+ * flowse_stft_compress_chunks: sig float32 [L] -> complex64 [K,1,256,Tc], the rows an ordinary [K,1,256,Tc] sampler call
+ * takes.  Frame t of chunk k is frame k hop + t of flowse_stft_compress(sig, B = 1), computed by the same kernel with the
+ * same arithmetic (bit-identical; frames >= T are zero, like pad_spec's); shared frames are computed twice -- there is no
+ * global spectrogram and no gather pass.  Needs Tg >= T (every frame of the recording lies in a chunk) and L > 255.
+ * flowse_istft_decompress_chunks: the inverse chain of flowse_istft_decompress over the Tg frames of the recording,
+ * where frame t is taken from the chunks by the seam rule: k = min(t / hop, K - 1), j = t - k hop; for k > 0 and j < To
+ * the linear cross-fade a + w (b - a) of a = chunk k-1 at frame j + hop and b = chunk k at frame j with
+ * w = (j + 0.5) / To, evaluated in fp32 on the COMPRESSED complex value (before spec_back); otherwise chunk k at frame j.
+ * All Tg frames take part in the overlap-add, as all Tpad frames do in flowse_istft_decompress.  Chunks cut from one
+ * spectrogram give that spectrogram's waveform bit for bit (b - a is an exact zero there).  out: float32 [Lout],
+ * 1 <= Lout <= 128 (Tg - 1) + 255. */
+int flowse_stft_compress_chunks(const float* sig, int L, float scale_in, void* out_c64, int K, int Tc, int hop, float factor,
+                                float exponent, void* stream);
+int flowse_istft_decompress_chunks(const void* chunks_c64, int K, int Tc, int hop, float factor, float exponent, float* out,
+                                   int Lout, float scale_out, void* stream);
 
 /* ---- in-library kernel timing (used by bench.py for the live roofline figure) -------------------------
  * Between _begin and _end every selected launch of this handle is bracketed by HIP events on the launch
