@@ -77,6 +77,9 @@ SIGNATURES = {
     "flowse_istft_decompress": (_i, [_vp, _i, _i, _i, _f, _f, _fp, _i, _f, _vp]),
     "flowse_stft_compress_chunks": (_i, [_fp, _i, _f, _vp, _i, _i, _i, _f, _f, _vp]),
     "flowse_istft_decompress_chunks": (_i, [_vp, _i, _i, _i, _f, _f, _fp, _i, _f, _vp]),
+    "flowse_resample_num_taps": (_i, [_i, _i]),
+    "flowse_resample_taps": (_i, [_i, _i, C.POINTER(_d), _i]),
+    "flowse_resample_poly": (_i, [_fp, _i, _i, _i, _i, _fp, _i, _vp]),
     "flowse_profile_begin": (_i, [_vp, _i]),
     "flowse_profile_end": (_i, [_vp, C.c_char_p, _i]),
     "flowse_upfirdn2d": (_i, [_fp, _fp] + [_i] * 13 + [_fp, _i, _i, _vp]),

@@ -83,9 +83,10 @@ def _chunk_noise(z, noise_key, Y_like, Tg):
 
 
 def enhance_long(model, y, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES, batch=8, N=5, T_rev=1.0, t_eps=0.03,
-                 odesolver="euler", z=None, noise_key=None, noise_seed=0, VF_fn=None, device=None):
+                 odesolver="euler", z=None, noise_key=None, noise_seed=0, VF_fn=None, device=None, as_tensor=False):
     """One recording of any length, chunked (module docstring).  y: float tensor [1, samples].  Returns the enhanced
-    waveform (numpy), normalised by the recording's global ``max|y|`` like ``enhance_waveform``.
+    waveform (numpy), normalised by the recording's global ``max|y|`` like ``enhance_waveform``; with ``as_tensor`` the
+    same values as a 1-D tensor left on the compute device (for a step that follows there, ``flowmse_amd.resample``).
 
     A recording whose padded frame count fits one chunk goes to ``evaluate.enhance_waveform`` unchanged.  Otherwise the
     chunk rows of THIS recording are sampled in groups of ``batch`` (the last group narrower); rows are never pooled
@@ -113,7 +114,7 @@ def enhance_long(model, y, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRA
     if K == 1:
         return enhance_waveform(model, y, N=N, T_rev=T_rev, t_eps=t_eps, odesolver=odesolver, z=z, VF_fn=VF_fn,
                                 device=device, noise_keys=None if noise_key is None else [noise_key],
-                                noise_seed=noise_seed)
+                                noise_seed=noise_seed, as_tensor=as_tensor)
     norm_factor = y.abs().max().item()
     y = y.to(device)
     fused = VF_fn is None and hasattr(dm, "fused_ok") and dm.fused_ok(y)
@@ -140,7 +141,8 @@ def enhance_long(model, y, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRA
                                          **kw)()[0])
     sample = torch.cat(rows, dim=0)
     if fused:                      # cross-fade + decompression + iSTFT + rescale: one HIP kernel
-        return dm.synthesize_chunks(sample, hop, L, norm_factor).squeeze().cpu().numpy()
-    spec = torch.from_numpy(blend_chunks_reference(sample, hop)).to(torch.complex64).to(sample.device)
-    x_hat = model.to_audio(spec.squeeze(), L)
-    return (x_hat * norm_factor).squeeze().cpu().numpy()
+        x_hat = dm.synthesize_chunks(sample, hop, L, norm_factor).reshape(-1)
+    else:
+        spec = torch.from_numpy(blend_chunks_reference(sample, hop)).to(torch.complex64).to(sample.device)
+        x_hat = (model.to_audio(spec.squeeze(), L) * norm_factor).reshape(-1)
+    return x_hat if as_tensor else x_hat.cpu().numpy()

@@ -48,8 +48,9 @@ def mean_std(data):
 
 
 def enhance_waveform(model, y, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", z=None, VF_fn=None, device=None,
-                     noise_keys=None, noise_seed=0):
-    """One utterance, evaluate.py:107-136.  y: float tensor [1, samples].  Returns the enhanced waveform (numpy).
+                     noise_keys=None, noise_seed=0, as_tensor=False):
+    """One utterance, evaluate.py:107-136.  y: float tensor [1, samples].  Returns the enhanced waveform (numpy; with
+    ``as_tensor`` the same values as a 1-D tensor left on the compute device).
     ``noise_keys`` ([key], see ``flowmse_amd.util.noise.utterance_key``) / ``noise_seed``: keyed prior noise."""
     device = device or y.device
     T_orig = y.size(1)
@@ -67,9 +68,10 @@ def enhance_waveform(model, y, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", z=
                                    noise_seed=noise_seed)
     sample, _ = sampler()
     if fused:                      # decompression + iSTFT + rescale as one HIP kernel
-        return dm.synthesize(sample, T_orig, norm_factor).squeeze().cpu().numpy()
-    x_hat = model.to_audio(sample.squeeze(), T_orig)
-    return (x_hat * norm_factor).squeeze().cpu().numpy()
+        x_hat = dm.synthesize(sample, T_orig, norm_factor).reshape(-1)
+    else:
+        x_hat = (model.to_audio(sample.squeeze(), T_orig) * norm_factor).reshape(-1)
+    return x_hat if as_tensor else x_hat.cpu().numpy()
 
 
 def enhance_batch(model, ys, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", noise_keys=None, noise_seed=0):

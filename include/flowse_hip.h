@@ -309,6 +309,36 @@ int flowse_stft_compress_chunks(const float* sig, int L, float scale_in, void* o
 int flowse_istft_decompress_chunks(const void* chunks_c64, int K, int Tc, int hop, float factor, float exponent, float* out,
                                    int Lout, float scale_out, void* stream);
 
+/* ---- sample-rate conversion ahead of the STFT and after the iSTFT (opt-in; the reference reads 16 kHz files only) ----
+ * Rational-ratio polyphase FIR resampling, zero phase, defined as what scipy.signal.resample_poly(x, up, down) computes
+ * with its defaults (window ("kaiser", 5.0), padtype "constant"):
+ *   g = gcd(up, down), up /= g, down /= g, R = max(up, down), half = 10 R
+ *   h[k]  = up * firwin(2 half + 1, 1 / R, window = ("kaiser", 5.0))[k],  k = 0 .. 2 half
+ *   L_out = ceil(L up / down)
+ *   out[n] = sum over m in [0, L) with |n down - m up| <= half of  x[m] h[half + n down - m up]
+ * Every entry takes a reduced or an unreduced pair (sr_out, sr_in will do) and reduces it itself.  Ratios with R > 1024
+ * after reduction return FLOWSE_ERR_SHAPE; 8 / 11.025 / 12 / 22.05 / 24 / 32 / 44.1 / 48 / 88.2 / 96 / 176.4 / 192 kHz
+ * against 16 kHz are within it, both ways (largest table: 20481 taps).
+ * Host only, no GPU call, usable without a device:
+ *   flowse_resample_num_taps: 2 half + 1, or -FLOWSE_ERR_ARG (a rate < 1) / -FLOWSE_ERR_SHAPE (R > 1024).
+ *   flowse_resample_taps: h[0 .. 2 half] in double into `taps` (a HOST buffer of `cap` doubles): the windowed sinc with the
+ *   Kaiser window's I0 by its power series, normalised to unit gain at DC as firwin does, times up (within 1e-12 of
+ *   scipy's).  cap < 2 half + 1 or a null buffer -> FLOWSE_ERR_ARG.
+ * flowse_resample_poly: B rows of L float32 samples (device, [B][L]), each on its own, into rows of L_out samples
+ * (device, [B][L_out]); L_out != ceil(L up / down) or B > 65535 -> FLOWSE_ERR_SHAPE, a null pointer or B, L < 1 ->
+ * FLOWSE_ERR_ARG, all checked before anything is launched.  One launch: with P = ceil((2 half + 1) / up) and the table
+ * H[p][j] = fp32(h[p + j up]) (zero past 2 half), c = half + n down, p = c mod up, q = c div up,
+ *   out[n] = fmaf chain over j = 0 .. P-1 of H[p][j] x[q - j],  x zero outside [0, L),
+ * c and q in 64 bits (n down passes 2^31 five minutes into a 44.1 kHz recording).  up == down is a device copy.  The table
+ * of a reduced ratio is built once per process and device and uploaded on the stream of the first call that needs it (that
+ * call allocates; later calls on other streams wait for the upload by event).  Enqueues only, no host synchronisation --
+ * but for the first call of a ratio on a device: it designs the taps on the host, allocates, and copies the table from
+ * pageable memory, which the runtime may wait for, and it records an event, so make it outside stream capture (one short
+ * call per ratio warms the cache).  Every later call for that ratio may be captured. */
+int flowse_resample_num_taps(int up, int down);
+int flowse_resample_taps(int up, int down, double* taps, int cap);
+int flowse_resample_poly(const float* sig, int B, int L, int up, int down, float* out, int L_out, void* stream);
+
 /* ---- in-library kernel timing (used by bench.py for the live roofline figure) -------------------------
  * Between _begin and _end every selected launch of this handle is bracketed by HIP events on the launch
  * stream (and the handle launches eagerly instead of replaying its hipGraph).  mode 0: only launches of the dominant
