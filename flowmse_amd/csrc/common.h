@@ -340,6 +340,11 @@ int conv_fused_stats_blocks(int B, int H, int W, int Cin, int Cout, int taps);
 // with_reduce = false: a split-K launch only writes the partial slices (the caller runs launch_splitk_reduce)
 int launch_conv(const ConvArgs& a, hipStream_t s, bool with_reduce = true);
 int launch_splitk_reduce(const ConvArgs& a, hipStream_t s);
+// What the calling thread's last convolution launch ran: every conv launcher records its kernel family -- the small-image
+// launchers the instance -- next to the launch itself (a host-side store: nothing of it is captured into a graph).
+// The parts are concatenated; flowse_op_last_conv_route returns the string.
+void conv_note_route(const char* a, const char* b = "", const char* c = "");
+const char* conv_last_route();
 // Reduction of a split-K conv fused with the GroupNorm that consumes its output (Conv_0 -> GroupNorm_1 of a ResnetBlock,
 // layerspp.py:262-265; the group structure G = min(Cout / 4, 32) is known when the plan is built).  One block per (group,
 // sample) sums the slices of its H*W x Cout/G elements, adds bias / per-sample bias, and -- holding the whole group --

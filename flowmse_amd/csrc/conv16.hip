@@ -471,6 +471,7 @@ int launch_flat16(const ConvArgs& a, hipStream_t s) {
         if (a.out_dt == DT_F32) FLOWSE_L16(false, float) else FLOWSE_L16(false, bf16_t)
     }
 #undef FLOWSE_L16
+    conv_note_route(ks > 1 ? "flat16_splitk" : "flat16");
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }
@@ -586,6 +587,7 @@ static int launch_halo_bf16(const ConvArgs& a, hipStream_t s) {
         else
             hipLaunchKernelGGL((conv3x3_halo_bf16_kernel<1, false, F16, T16, T16>), dim3(grid), dim3(256), lds, s, a);
     }
+    conv_note_route(TERMS == 3 ? "halo_bf16x3" : "halo16");
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

@@ -963,6 +963,7 @@ int launch_pc16(const ConvArgs& a, hipStream_t s) {
         if (gn == 2) FLOWSE_LPC(2, false) else if (gn == 1) FLOWSE_LPC(1, false) else FLOWSE_LPC(0, false)
     }
 #undef FLOWSE_LPC
+    conv_note_route("pc16");
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

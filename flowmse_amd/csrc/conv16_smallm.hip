@@ -244,6 +244,7 @@ int launch_smallm16b(const ConvArgs& a, hipStream_t s) {
         const size_t lds = (size_t)8 * 32 * (32 * NT2 + 4) * sizeof(float);                                  \
         if (const int rc = allow_lds<&conv_smallm16b_kernel<NT2, F16, OT>>(lds)) return rc;                  \
         hipLaunchKernelGGL((conv_smallm16b_kernel<NT2, F16, OT>), dim3(mtiles * (a.Cout / (32 * NT2))), dim3(512), lds, s, a); \
+        conv_note_route("smallm16b<" #NT2 ", ", F16 ? "f16, " : "bf16, ", sizeof(OT) == 4 ? "out32>" : "out16>"); \
     }
     const bool of32 = a.out_dt == DT_F32;
     if (a.wq_f16) {

@@ -235,6 +235,7 @@ int launch_1x1_stream(const ConvArgs& a, hipStream_t s) {
     const int64_t M = (int64_t)a.B * a.H * a.W;
     const int mblocks = (int)((M + C1_WAVES * C1_PX - 1) / (C1_WAVES * C1_PX));
     hipLaunchKernelGGL(conv1x1_stream_kernel, dim3(mblocks * (a.Cout >> 7)), dim3(64 * C1_WAVES), 0, s, a);
+    conv_note_route("1x1_stream");
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

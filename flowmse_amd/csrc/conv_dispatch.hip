@@ -13,6 +13,8 @@
 //   conv_reduce.hip   second pass of split-K launches (+ fused GroupNorm statistics / GroupNorm)
 //   conv16.hip        16-bit operand / storage modes
 // Replaces (reference): ddpm_conv3x3 / ddpm_conv1x1 (flowmse/backbones/ncsnpp_utils/layers.py:100-124), NIN (:546-555).
+#include <cstdio>
+
 #include "conv_common.h"
 
 namespace flowse {
@@ -140,6 +142,10 @@ bool conv_supports_w2d(int B, int H, int W, int C1, int C2, int Cout, int taps) 
     const int64_t b64 = ((int64_t)B * H * W / 256) * (Cout / 64);
     return conv_w2d_shape_ok(B, H, W, C1, C2, Cout, taps) && b64 >= g_w2d_min_blocks;
 }
+
+static thread_local char g_route[48] = "";
+void conv_note_route(const char* a, const char* b, const char* c) { snprintf(g_route, sizeof g_route, "%s%s%s", a, b, c); }
+const char* conv_last_route() { return g_route; }
 
 int launch_conv(const ConvArgs& a, hipStream_t s, bool with_reduce) {
     if ((a.C1 & 3) || (a.C2 & 3) || (a.Cout & 3) || (a.bias2 && (a.bias2_stride & 3)) || (a.taps != 1 && a.taps != 9) ||

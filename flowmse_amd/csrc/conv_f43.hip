@@ -659,6 +659,7 @@ int launch_f43(const ConvArgs& a, hipStream_t s) {
         if (gn == 2) FLOWSE_LF43(2, false, 1) else if (gn == 1) FLOWSE_LF43(1, false, 1) else FLOWSE_LF43(0, false, 1)
     }
 #undef FLOWSE_LF43
+    conv_note_route(a.partial ? "f43_splitk" : "f43");
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

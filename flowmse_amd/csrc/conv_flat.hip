@@ -355,6 +355,7 @@ static int launch_cfg(const ConvArgs& a, hipStream_t s) {
     } else {
         hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, TM, TN>), dim3(grid, a.ksplit), dim3(64 * WM * WN), lds, s, a);
     }
+    conv_note_route(a.ksplit > 1 ? "flat_splitk" : "flat");
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

@@ -213,6 +213,7 @@ static int launch_halo(const ConvArgs& a, hipStream_t s) {
         hipLaunchKernelGGL((conv3x3_halo_kernel<WM, WN, TM, TN, 1>), dim3(grid), dim3(64 * WM * WN), lds, s, a);
     else
         hipLaunchKernelGGL((conv3x3_halo_kernel<WM, WN, TM, TN, 0>), dim3(grid), dim3(64 * WM * WN), lds, s, a);
+    conv_note_route("halo");
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }
@@ -508,6 +509,7 @@ int launch_head4(const ConvArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL((conv3x3_head4_16_kernel<GNF, f16_t>), dim3(grid), dim3(256), lds16, s, a);
         if (gn == 2) { FLOWSE_H16(2) } else if (gn == 1) { FLOWSE_H16(1) } else { FLOWSE_H16(0) }
 #undef FLOWSE_H16
+        conv_note_route("head4_16");
         FLOWSE_LAUNCH_CHECK();
         return OK;
     }
@@ -518,6 +520,7 @@ int launch_head4(const ConvArgs& a, hipStream_t s) {
     } else {
         FLOWSE_DT_SWITCH(a.in_dt, ST, hipLaunchKernelGGL((conv3x3_head4_kernel<0, ST>), dim3(grid), dim3(256), lds, s, a));
     }
+    conv_note_route("head4");
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }
@@ -763,6 +766,7 @@ bool conv_cin4_uses_mfma(int B, int H, int W, int Cout, int taps) {
 }
 
 int launch_conv_cin4(const ConvArgs& a, hipStream_t s) {
+    conv_note_route("cin4");
     const int Q = a.Cout / 4;
     if (a.C1 == 4 && a.C2 == 0 && a.ksplit <= 1 && !a.gn.mean && conv_cin4_uses_mfma(a.B, a.H, a.W, a.Cout, a.taps)) {
         const size_t lds = ((size_t)128 * (128 + 4) + 256 * 8) * sizeof(float);

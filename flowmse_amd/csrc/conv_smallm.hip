@@ -461,14 +461,17 @@ int launch_smallm(const ConvArgs& a, hipStream_t s) {
             return ERR_ARG;
         }
         hipLaunchKernelGGL(conv_smallm16_kernel, dim3((unsigned)(((M + 15) / 16) * (a.Cout / 16))), dim3(512), 0, s, a);
+        conv_note_route("smallm_tile16");
     } else if (wide) {
         const size_t lds = (size_t)8 * SM_BM * (64 + 4) * sizeof(float);
         if (const int rc = allow_lds<&conv_smallm_kernel<2>>(lds)) return rc;
         hipLaunchKernelGGL((conv_smallm_kernel<2>), dim3(mtiles * (a.Cout / 64)), dim3(512), lds, s, a);
+        conv_note_route("smallm<2>");
     } else {
         const size_t lds = (size_t)8 * SM_BM * (32 + 4) * sizeof(float);
         if (const int rc = allow_lds<&conv_smallm_kernel<1>>(lds)) return rc;
         hipLaunchKernelGGL((conv_smallm_kernel<1>), dim3(mtiles * (a.Cout / 32)), dim3(512), lds, s, a);
+        conv_note_route("smallm<1>");
     }
     FLOWSE_LAUNCH_CHECK();
     return OK;

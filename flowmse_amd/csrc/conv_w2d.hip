@@ -691,6 +691,7 @@ int launch_w2d(const ConvArgs& a, hipStream_t s) {
         if (gn == 2) FLOWSE_LW2D(2, 1) else if (gn == 1) FLOWSE_LW2D(1, 1) else FLOWSE_LW2D(0, 1)
     }
 #undef FLOWSE_LW2D
+    conv_note_route("w2d");
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

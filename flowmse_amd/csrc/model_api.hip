@@ -1210,10 +1210,12 @@ int flowse_op_conv3x3_f43(const float* in1, int C1, const float* in2, int C2, co
 // 16-bit storage per-op entry: fp32 NHWC tensors at the boundary, rounded to bf16 (dt 1) / half (dt 2) inside, conv on
 // the 16-bit matrix cores (LDS-halo kernel when it applies, else the flat kernel), result widened back.  Optional fused
 // GroupNorm(+SiLU) on the input (halo shapes only) from caller-supplied per-(sample, channel) mean / scale and beta.
-int flowse_op_conv2d_16(const float* in1, int C1, const float* in2, int C2, const float* w, const float* bias,
-                        const float* res, const float* gn_mean, const float* gn_scale, const float* gn_beta, int silu,
-                        float* out, int B, int H, int W, int Cout, int taps, float scale, int dt, void* scratch,
-                        int64_t scratch_bytes, void* stream) {
+// (bias2 / out_f32: the additions of flowse_op_conv2d_16_ex; out_f32 = `res` and `out` are fp32 tensors the conv reads and
+// writes directly, out_dt = DT_F32, as the model does for the few convs that leave the 16-bit domain)
+static int op_conv2d_16(const float* in1, int C1, const float* in2, int C2, const float* w, const float* bias,
+                        const float* bias2, int bias2_stride, const float* res, const float* gn_mean, const float* gn_scale,
+                        const float* gn_beta, int silu, float* out, int out_f32, int B, int H, int W, int Cout, int taps,
+                        float scale, int dt, void* scratch, int64_t scratch_bytes, void* stream) {
     if (!in1 || !w || !out || !scratch || (dt != DT_BF16 && dt != DT_F16) || (taps != 1 && taps != 9)) {
         set_error("flowse_op_conv2d_16: bad argument");
         return ERR_ARG;
@@ -1221,7 +1223,8 @@ int flowse_op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
     if (!in2) C2 = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t M = (int64_t)B * H * W, C = C1 + C2;
-    const bool halo = conv16_uses_halo(B, H, W, C1, C2, Cout, taps);
+    // (the LDS-halo kernels store the operands' type only: an fp32-output launch of their shapes runs the flat kernel)
+    const bool halo = !out_f32 && conv16_uses_halo(B, H, W, C1, C2, Cout, taps);
     // the progressive-output heads (C -> 4, ncsnpp.py:345-366): 16-bit input, fp32 residual (the pyramid) and fp32 output, as
     // in the model -- conv3x3_head4_16_kernel
     const bool head = Cout == 4 && taps == 9 && !in2 && conv_supports_head4(B, H, W, C1, 0, Cout, taps);
@@ -1246,8 +1249,9 @@ int flowse_op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
     void* wq = take(2 * nw);
     const bool frag = (taps == 9 && conv16_uses_pc(B, H, W, C1, C2, Cout, taps)) || conv16_smallm_ok(B, H, W, C1, C2, Cout, taps);
     void* wfrag = frag ? take(2 * nw) : nullptr;
-    void* r16 = res ? take(2 * M * Cout) : nullptr;
-    void* o16 = take(2 * M * Cout);
+    const bool direct = head || out_f32;                   // fp32 res / out, used in place
+    void* r16 = res && !direct ? take(2 * M * Cout) : nullptr;
+    void* o16 = direct ? nullptr : take(2 * M * Cout);
     float* part = ks > 1 ? reinterpret_cast<float*>(take(4 * (int64_t)ks * M * Cout)) : nullptr;
     if ((size_t)(p - static_cast<char*>(scratch)) > (size_t)scratch_bytes) {
         set_error("flowse_op_conv2d_16: scratch too small");
@@ -1257,11 +1261,11 @@ int flowse_op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
     if (rc == OK && C2) rc = launch_convert(in2, DT_F32, a2, dt, M * C2, s);
     if (rc == OK) rc = launch_convert(w, DT_F32, wq, dt, nw, s);
     if (rc == OK && frag) rc = launch_pc16_weights(wq, Cout, (int)C, wfrag, s, taps);
-    if (rc == OK && res) rc = launch_convert(res, DT_F32, r16, dt, M * Cout, s);
+    if (rc == OK && r16) rc = launch_convert(res, DT_F32, r16, dt, M * Cout, s);
     if (rc != OK) return rc;
     ConvArgs c;
     c.in1 = static_cast<const float*>(a1); c.in2 = static_cast<const float*>(a2); c.C1 = C1; c.C2 = C2;
-    c.w = w; c.bias = bias; c.bias2 = nullptr; c.bias2_stride = 0;
+    c.w = w; c.bias = bias; c.bias2 = bias2; c.bias2_stride = bias2 ? bias2_stride : 0;
     c.res = static_cast<const float*>(r16); c.out = static_cast<float*>(o16);
     c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.taps = taps; c.scale = scale;
     c.ksplit = ks; c.partial = part;
@@ -1272,15 +1276,38 @@ int flowse_op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
         c.gn = GnParams{gn_mean, gn_scale, gn_beta};
         c.gn_silu = silu;
     }
-    if (head) {
+    if (direct) {
         c.res = res;
         c.out = out;
         c.out_dt = DT_F32;
     }
     rc = launch_conv(c, s);
-    if (rc != OK || head) return rc;
+    if (rc != OK || direct) return rc;
     return launch_convert(o16, dt, out, DT_F32, M * Cout, s);
 }
+
+int flowse_op_conv2d_16(const float* in1, int C1, const float* in2, int C2, const float* w, const float* bias,
+                        const float* res, const float* gn_mean, const float* gn_scale, const float* gn_beta, int silu,
+                        float* out, int B, int H, int W, int Cout, int taps, float scale, int dt, void* scratch,
+                        int64_t scratch_bytes, void* stream) {
+    return op_conv2d_16(in1, C1, in2, C2, w, bias, nullptr, 0, res, gn_mean, gn_scale, gn_beta, silu, out, 0, B, H, W, Cout,
+                        taps, scale, dt, scratch, scratch_bytes, stream);
+}
+
+int flowse_op_conv2d_16_ex(const float* in1, int C1, const float* in2, int C2, const float* w, const float* bias,
+                           const float* bias2, int bias2_stride, const float* res, const float* gn_mean,
+                           const float* gn_scale, const float* gn_beta, int silu, float* out, int out_f32, int B, int H,
+                           int W, int Cout, int taps, float scale, int dt, void* scratch, int64_t scratch_bytes,
+                           void* stream) {
+    if (bias2 && (bias2_stride < Cout || (bias2_stride & 3))) {
+        set_error("flowse_op_conv2d_16_ex: bias2_stride must be a multiple of 4 and at least Cout");
+        return ERR_ARG;
+    }
+    return op_conv2d_16(in1, C1, in2, C2, w, bias, bias2, bias2_stride, res, gn_mean, gn_scale, gn_beta, silu, out,
+                        out_f32 != 0, B, H, W, Cout, taps, scale, dt, scratch, scratch_bytes, stream);
+}
+
+const char* flowse_op_last_conv_route(void) { return conv_last_route(); }
 
 // Tail of ResnetBlockBigGANpp in 16-bit storage as ONE launch of the producer / consumer kernel:
 //   out = (conv3x3(act(GroupNorm(h)); w1) + b1 + conv1x1(cat[x1, x2]; w2) + b2) * scale       (layerspp.py:265-274)

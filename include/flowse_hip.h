@@ -387,6 +387,24 @@ int flowse_op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
                         const float* res, const float* gn_mean, const float* gn_scale, const float* gn_beta, int silu,
                         float* out, int B, int H, int W, int Cout, int taps, float scale, int dt, void* scratch,
                         int64_t scratch_bytes, void* stream);
+/* flowse_op_conv2d_16 plus the two epilogue inputs the model's 16-bit modes also use: a per-sample bias table `bias2`
+ * (element (b, co) at bias2[b * bias2_stride + co], fp32, may be NULL; stride a multiple of 4, >= Cout) and, with
+ * out_f32 != 0, fp32 output: `res` and `out` are then read and written by the convolution as fp32 tensors (out_dt = fp32,
+ * no conversion at the boundary, no second rounding) -- the form of the few convs that leave the 16-bit domain.  Shapes of
+ * the LDS-halo kernels, which store the operands' type only, run the flat kernel when out_f32 is set. */
+int flowse_op_conv2d_16_ex(const float* in1, int C1, const float* in2, int C2, const float* w, const float* bias,
+                           const float* bias2, int bias2_stride, const float* res, const float* gn_mean,
+                           const float* gn_scale, const float* gn_beta, int silu, float* out, int out_f32, int B, int H,
+                           int W, int Cout, int taps, float scale, int dt, void* scratch, int64_t scratch_bytes,
+                           void* stream);
+/* Which kernel the calling thread's last convolution launch ran (any entry point that launches one: the per-op entries
+ * above and below, a forward pass while it is being recorded): the kernel family -- "flat", "flat_splitk", "halo", "f43",
+ * "f43_splitk", "w2d", "1x1_stream", "head4", "head4_16", "cin4", "flat16", "flat16_splitk", "halo16", "halo_bf16x3",
+ * "pc16" -- or, for the small-image kernels (at most 2048 pixels), the instance: "smallm<1>", "smallm<2>", "smallm_tile16",
+ * "smallm16b<NT2, bf16|f16, out16|out32>" with NT2 = 1 or 2.  Written by the launcher next to the launch, never derived
+ * from the shape a second time; a host-side, thread-local record ("" before the first launch): replaying a captured
+ * graph does not change it.  The pointer stays valid for the thread's lifetime; the text changes with the next launch. */
+const char* flowse_op_last_conv_route(void);
 /* Tail of ResnetBlockBigGANpp (layerspp.py:265-274) in 16-bit storage as ONE launch of the producer / consumer kernel:
  *   out = (conv3x3(act(GroupNorm(h)); w1) + b1 + conv1x1(cat[x1, x2]; w2) + b2) * scale
  * The 1x1 shortcut Conv_2(x) runs as extra K steps of Conv_1's launch (the form the 16-bit model modes use wherever

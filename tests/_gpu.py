@@ -46,6 +46,37 @@ def conv2d(x1, w, bias=None, x2=None, bias2=None, res=None, scale=1.0, padding=N
     return nchw(out)
 
 
+def last_route():
+    """which kernel the last convolution launch of this thread ran (flowse_op_last_conv_route)"""
+    return L.flowse_op_last_conv_route().decode()
+
+
+def conv2d_16(x1, w, dt, bias=None, x2=None, bias2=None, res=None, scale=1.0, out_f32=False, gn=None):
+    """The 16-bit storage op entry with per-sample bias and optional fp32 output (flowse_op_conv2d_16_ex; dt 1 = bf16,
+    2 = half): fp32 NCHW cpu tensors in, rounded to dt inside; fp32 NCHW cpu out.  gn: (mean, scale, beta) or None."""
+    Cout, Cin, k, _ = w.shape
+    taps = k * k
+    a1 = nhwc(x1)
+    a2 = nhwc(x2) if x2 is not None else None
+    B, H, W, C1 = a1.shape
+    C2 = a2.shape[3] if a2 is not None else 0
+    wp = w.permute(0, 2, 3, 1).reshape(Cout, taps, Cin).contiguous().cuda()
+    bb = bias.contiguous().cuda() if bias is not None else None
+    b2 = bias2.contiguous().cuda() if bias2 is not None else None
+    rr = nhwc(res) if res is not None else None
+    mean, scl, beta = (t.contiguous().cuda() for t in gn) if gn is not None else (None, None, None)
+    out = torch.empty(B, H, W, Cout, device="cuda")
+    M = B * H * W
+    nbytes = 2 * (M * Cin + 2 * Cout * taps * Cin + 2 * M * Cout) + 4 * 64 * M * Cout + 4096
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    _lib.check(L.flowse_op_conv2d_16_ex(_lib.ptr(a1), C1, _lib.ptr(a2), C2, _lib.ptr(wp), _lib.ptr(bb), _lib.ptr(b2),
+                                        b2.shape[1] if b2 is not None else 0, _lib.ptr(rr), _lib.ptr(mean), _lib.ptr(scl),
+                                        _lib.ptr(beta), 1, _lib.ptr(out), int(out_f32), B, H, W, Cout, taps, float(scale), dt,
+                                        _lib.ptr(scratch), scratch.numel(), stream()))
+    torch.cuda.synchronize()
+    return nchw(out)
+
+
 def group_norm(x1, gamma, beta, x2=None, silu=True, eps=1e-6):
     a1 = nhwc(x1)
     a2 = nhwc(x2) if x2 is not None else None

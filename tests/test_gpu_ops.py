@@ -533,23 +533,33 @@ def _conv16(x, w, dt, bias=None, x2=None, res=None, gn=None, scale=1.0):
 
 
 @pytest.mark.parametrize("dt,bound", [(1, 4e-3), (2, 5e-4)])
-@pytest.mark.parametrize("case", ["halo", "halo_gn_concat", "halo_32ch", "flat_small_splitk", "flat_1x1_concat", "flat_w8",
-                                  "pc", "pc_gn_concat", "pc_gn_256out", "pc_ragged_items", "pc_64items", "head4_gn", "head4_plain"])
+@pytest.mark.parametrize("case", ["halo", "halo_gn_concat", "halo_32ch", "smallm_16x16", "flat_1x1_concat", "smallm_8x8",
+                                  "flat_3x3_splitk", "pc", "pc_gn_concat", "pc_gn_256out", "pc_ragged_items", "pc_64items",
+                                  "head4_gn", "head4_plain"])
 def test_conv2d_16bit_storage(case, dt, bound):
     """pc*: >= 64 (16 x 16 pixel tile, 128-channel block) items -> the persistent producer / consumer kernel
     (conv3x3_pc16_kernel); pc_64items: its smallest launch (64 blocks of one tile); pc_ragged_items: an item count that is no
     multiple of the 256 blocks (blocks with 1 and 2 tiles, tiles of several samples and both channel blocks in one block's
     stream).  head4*: the progressive-output heads C -> 4 (conv3x3_head4_16_kernel: 16-bit operands on v_mfma_f32_4x4x4, fp32
     residual and output).  halo*: image heights that are multiples of 8 but not of 16 -> the per-tap kernel (conv3x3_halo_bf16_kernel),
-    which no power-of-two image reaches in the storage modes any more."""
+    which no power-of-two image reaches in the storage modes any more.  smallm*: at most 2048 pixels -> the in-block split-K
+    kernel (conv_smallm16b_kernel<1, ., 16-bit out>; its own bounds: test_gpu_smallm.py).  flat*: the flat kernel
+    (conv_flat16_kernel) with its K slices and the reduction launch -- flat_3x3_splitk: one utterance at 64 x 64, too large
+    for the small-image kernel and too few items for the LDS-halo kernels.  Every case asserts the kernel that ran."""
     g = torch.Generator().manual_seed(3)
     shapes = {"halo": (6, 128, 0, 128, 24, 128, 3), "halo_gn_concat": (6, 128, 128, 128, 24, 128, 3),
-              "halo_32ch": (6, 32, 0, 128, 24, 128, 3), "flat_small_splitk": (2, 256, 0, 256, 16, 16, 3),
+              "halo_32ch": (6, 32, 0, 128, 24, 128, 3), "smallm_16x16": (2, 256, 0, 256, 16, 16, 3),
+              "flat_3x3_splitk": (1, 256, 0, 256, 64, 64, 3),
               "pc_64items": (2, 128, 0, 128, 64, 128, 3),
-              "flat_1x1_concat": (2, 256, 128, 128, 32, 64, 1), "flat_w8": (3, 256, 0, 256, 8, 8, 3),
+              "flat_1x1_concat": (2, 256, 128, 128, 32, 64, 1), "smallm_8x8": (3, 256, 0, 256, 8, 8, 3),
               "pc": (1, 128, 0, 128, 256, 256, 3), "pc_gn_concat": (4, 64, 32, 128, 128, 128, 3),
               "pc_gn_256out": (2, 64, 0, 256, 128, 128, 3), "pc_ragged_items": (3, 32, 0, 256, 112, 128, 3),
               "head4_gn": (4, 128, 0, 4, 64, 64, 3), "head4_plain": (4, 64, 0, 4, 64, 64, 3)}
+    dtn = {1: "bf16", 2: "f16"}[dt]
+    routes = {"halo": "halo16", "halo_gn_concat": "halo16", "halo_32ch": "halo16", "smallm_16x16": f"smallm16b<1, {dtn}, out16>",
+              "smallm_8x8": f"smallm16b<1, {dtn}, out16>", "flat_1x1_concat": "flat16_splitk", "flat_3x3_splitk": "flat16_splitk",
+              "pc": "pc16", "pc_gn_concat": "pc16", "pc_gn_256out": "pc16", "pc_ragged_items": "pc16", "pc_64items": "pc16",
+              "head4_gn": "head4_16", "head4_plain": "head4_16"}
     B, C1, C2, Cout, H, W, k = shapes[case]
     C = C1 + C2
     x = torch.randn(B, C, H, W, generator=g)
@@ -570,8 +580,10 @@ def test_conv2d_16bit_storage(case, dt, bound):
         _lib.check(_lib.lib.flowse_op_pc16_channel_blocks(blocks))
         try:
             got = _conv16(x[:, :C1].contiguous(), w, dt, bias, x[:, C1:].contiguous() if C2 else None, res, gn, 0.7071)
+            route = _lib.lib.flowse_op_last_conv_route().decode()
         finally:
             _lib.check(_lib.lib.flowse_op_pc16_channel_blocks(-1))
+        assert route == routes[case], (case, route)
         err = float((got - ref).norm() / ref.norm())
         print(f"conv2d_16 {case} dt={dt} blocks={blocks}: rel-L2 vs fp32 torch {err:.3e}")
         assert err < bound
