@@ -56,16 +56,36 @@ struct W2Tile {
 };
 
 // ---- output stage.  out = A4^T [m] A2 needs all 24 components of a (unit, channel); they live in eight waves.
-// Destination wave D = (j, g) finishes the 32 channels of tile j for unit row g (4 image rows x 16 pixels): accumulator
-// registers r = 4g .. 4g+3 of every source.  Sources pre-reduce vertically inside their half --
+// The products are TRANSPOSED (weight fragment = A operand, pixel fragment = B operand; for v_mfma_f32_32x32x2_f32 both
+// fragment layouts are lane = index + 32 k, so nothing upstream of the MFMA changes): lane l of a source holds UNIT
+// l & 31 = (ur, uc) and accumulator register r holds channel 8 (r >> 2) + 4 (l >> 5) + (r & 3) -- the four registers of
+// group q = r >> 2 are the channel quad cq = 2 q + kh of one unit, which is what a 16-byte NHWC store wants.
+// Destination wave D = (j, g) finishes the 32 channels of tile j for unit row g (4 image rows x 16 pixels); its lane
+// lambda = (uc = lambda >> 3, cq = lambda & 7) finishes unit (g, uc), channels 4 cq .. 4 cq + 3.  Sources pre-reduce
+// vertically inside their half --
 //     CH 0: (m0 + m1 + m2, m1 - m2, m1 + m2)          CH 1: (m3 + m4, m3 - m4, m5)
-// -- and hand each destination three float4 (the four registers of its unit row).  Two rounds through ONE 96 KB region
-// [dest 8][h 4][3][lane 64][4] (the CH 0 sources, then the CH 1 sources: 2 x 96 KB would not fit beside the next tile's
-// prefetched halo); a destination folds the four h of a round in a fixed order (x0 = (h0 + h1) + h2, x1 = (h1 - h2) - h3:
-// bit-reproducible) and finishes
+// -- and write, per channel tile and register group, three float4 to destination (j, ur) -- lane-dependent -- at lane
+// lambda = 8 uc + 2 q + kh.  Two rounds through ONE 96 KB region [dest 8][h 4][3][position 64][4] (the CH 0 sources, then
+// the CH 1 sources: 2 x 96 KB would not fit beside the next tile's prefetched halo); a destination folds the four h of a
+// round in a fixed order (x0 = (h0 + h1) + h2, x1 = (h1 - h2) - h3: bit-reproducible) and finishes
 //     o0 = A + D      o1 = B + 2 E      o2 = C + 4 D      o3 = B + 8 E + F          (A..F = the six partials, per column)
-// Then, wave-private: transposition of its 64 pixels x 32 channels through its own 12 KB slice, bias / per-sample bias /
-// residual / scale, 16-byte stores, GroupNorm partial statistics per (4 x 16 pixel strip, channel).
+// = rows 0..3 of its unit, columns x = 0, 1, as float4 over its four channels: bias / per-sample bias / residual / scale,
+// eight 16-byte stores (each store instruction = 8 pixels x 128 bytes: full lines), GroupNorm partial statistics per
+// (4 x 16 pixel strip, channel) -- no transposition, no wave-private slice.
+//
+// Position of lane lambda inside a [64][4] slot block of destination row g:  p = lambda ^ uc ^ 8 (g & 1), i.e.
+//     bits 0-2 = cq ^ uc,   bit 3 = (uc ^ g) & 1,   bits 4-5 = uc >> 1.
+// 12 KB per destination and 1 KB per slot are 0 mod 64 banks, so only p counts (16 bytes = 4 banks: p mod 16 of a 64-bank
+// row, p mod 8 of a 32-bank row).
+//   ds_write_b128 (eight groups of 8 consecutive lanes, 32 banks): a group is one ur, one kh, uc = 0..7, and q is the
+//     same for the whole instruction: p mod 8 = cq ^ uc takes all eight values.  Counted in four groups of 16 consecutive
+//     lanes over 64 banks instead (ur = 2 k, 2 k + 1): bit 3 = (uc ^ ur) & 1 separates the two unit rows for every uc -- 16
+//     distinct values as well.
+//   ds_read_b128 (four groups of 16 lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, + 32; 64 banks): g is the wave's.  A
+//     group holds, of every uc of its half, either the low or the high four cq: uc, uc ^ 1 contribute complementary
+//     halves; p mod 16 = 8 ((uc ^ g) & 1) + (cq ^ uc) -- the two uc of equal parity (uc, uc ^ 2) share bit 3 and carry
+//     opposite cq halves, XORed with values that differ in bit 1 only: disjoint; 16 distinct values.  (Sixteen CONSECUTIVE
+//     lanes = (uc & 1, cq) are distinct too.)  tests/test_w2d_layout_host.py enumerates all of it.
 // NJ = 1 (32-channel blocks, see the kernel): only waves 0-3 are destinations; the others give and keep the barriers.
 template <int CH, int NJ>
 __device__ __forceinline__ void w2d_out(f32x16 (&acc)[3][NJ], float* X, int b, int y0, int x0, int n0) {
@@ -82,59 +102,61 @@ __device__ __forceinline__ void w2d_out(f32x16 (&acc)[3][NJ], float* X, int b, i
     const int jD = wave >> 2, gD = wave & 3;             // this wave as a destination
     const bool dest = jD < NJ;
     const int li = lane & 31, kh = lane >> 5;
+    const int ur = li >> 3, uc = li & 7;                 // this lane as a source: its unit
     const int W = a.W, Cout = a.Cout;
     const int ch0 = n0 + jD * 32;
-    const int pl = lane >> 3, cq = lane & 7;             // row pass: pixel lane, channel quad
+    const int ucD = lane >> 3, cq = lane & 7;            // this lane as a destination: unit column, channel quad
     const bool has_res = a.res != nullptr;
-    const int64_t pix0 = ((int64_t)b * a.H + y0 + 4 * gD) * W + x0;
+    const int64_t pix0 = ((int64_t)b * a.H + y0 + 4 * gD) * W + x0 + 2 * ucD;
     const float* resb = a.res + pix0 * Cout + ch0 + cq * 4;
     float* outb = a.out + pix0 * Cout + ch0 + cq * 4;
-    int roff[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int pp = i * 8 + pl;                       // pixel of the 4 x 16 strip, row-major
-        roff[i] = ((pp >> 4) * W + (pp & 15)) * Cout;
-    }
+    // pixel i = 2 row + x of the unit: a uniform offset
+    auto poff = [&](int i) { return ((i >> 1) * W + (i & 1)) * Cout; };
     // residual quads are requested first: in flight during the whole exchange
     float4 rres[8];
     if (has_res && dest) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) rres[i] = *reinterpret_cast<const float4*>(resb + roff[i]);
+        for (int i = 0; i < 8; ++i) rres[i] = *reinterpret_cast<const float4*>(resb + poff(i));
     }
-    float* Xd = X + wave * W2_XDEST;
+    // source: slot block (h, partial 0) of destination (0, ur), position of register group 0; group q: position ^ 2 q
+    const int gpos = (uc * 8 + (kh ^ uc)) ^ ((ur & 1) << 3);
+    float* Xs = X + ur * W2_XDEST + (hq * 3) * 256;
+    const float* Xd = X + wave * W2_XDEST + 4 * ((lane ^ ucD) ^ ((gD & 1) << 3));
     auto give = [&]() {
 #pragma unroll
-        for (int D = 0; D < 4 * NJ; ++D) {
-            const int jd = D >> 2, gd = D & 3;
-            float4 v0, v1, v2;
-            float* e0 = &v0.x; float* e1 = &v1.x; float* e2 = &v2.x;
+        for (int jd = 0; jd < NJ; ++jd) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int r = 4 * gd + e;
-                const float s12 = acc[1][jd][r] + acc[2][jd][r];
-                if (CH == 0) {
-                    e0[e] = acc[0][jd][r] + s12;
-                    e1[e] = acc[1][jd][r] - acc[2][jd][r];
-                    e2[e] = s12;
-                } else {                                 // acc[0] = m5, acc[1] = m3, acc[2] = m4
-                    e0[e] = s12;
-                    e1[e] = acc[1][jd][r] - acc[2][jd][r];
-                    e2[e] = acc[0][jd][r];
+            for (int q = 0; q < 4; ++q) {
+                float4 v0, v1, v2;
+                float* e0 = &v0.x; float* e1 = &v1.x; float* e2 = &v2.x;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = 4 * q + e;
+                    const float s12 = acc[1][jd][r] + acc[2][jd][r];
+                    if (CH == 0) {
+                        e0[e] = acc[0][jd][r] + s12;
+                        e1[e] = acc[1][jd][r] - acc[2][jd][r];
+                        e2[e] = s12;
+                    } else {                             // acc[0] = m5, acc[1] = m3, acc[2] = m4
+                        e0[e] = s12;
+                        e1[e] = acc[1][jd][r] - acc[2][jd][r];
+                        e2[e] = acc[0][jd][r];
+                    }
                 }
+                float* dst = Xs + jd * 4 * W2_XDEST + 4 * (gpos ^ (2 * q));
+                *reinterpret_cast<float4*>(dst) = v0;
+                *reinterpret_cast<float4*>(dst + 256) = v1;
+                *reinterpret_cast<float4*>(dst + 512) = v2;
             }
-            float* dst = X + D * W2_XDEST + (hq * 3) * 256 + lane * 4;
-            *reinterpret_cast<float4*>(dst) = v0;
-            *reinterpret_cast<float4*>(dst + 256) = v1;
-            *reinterpret_cast<float4*>(dst + 512) = v2;
         }
     };
-    // S[x][c][e]: column x, partial c, register e of this wave's unit row
+    // S[x][c][e]: column x, partial c, channel e of this lane's quad
     auto take = [&](float (&S)[2][3][4]) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float4 t = *reinterpret_cast<const float4*>(Xd + (s * 3 + c) * 256 + lane * 4);
+                const float4 t = *reinterpret_cast<const float4*>(Xd + (s * 3 + c) * 256);
                 const float* q = &t.x;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -160,41 +182,37 @@ __device__ __forceinline__ void w2d_out(f32x16 (&acc)[3][NJ], float* X, int b, i
     if (a.bias) bq = *reinterpret_cast<const float4*>(a.bias + ch0 + cq * 4);
     if (a.bias2) bq2 = *reinterpret_cast<const float4*>(a.bias2 + (int64_t)b * a.bias2_stride + ch0 + cq * 4);
     take(SB);
-    // ---- transpose through this wave's own slice (nobody else reads it), finish, store, statistics
-    float* T = Xd;                                       // [64 pixels][32 channels]
-    __builtin_amdgcn_wave_barrier();                     // LDS is in-order per wave: take()'s reads precede these writes
+    // ---- finish the unit's 4 rows x 2 columns x 4 channels, store, statistics
+    float o[4][2][4];
 #pragma unroll
     for (int x = 0; x < 2; ++x)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float A = SA[x][0][e], Bv = SA[x][1][e], Cv = SA[x][2][e];
             const float D = SB[x][0][e], E = SB[x][1][e], Fv = SB[x][2][e];
-            const float o0 = A + D, o1 = fmaf(2.f, E, Bv), o2 = fmaf(4.f, D, Cv), o3 = fmaf(8.f, E, Bv) + Fv;
-            const int col = 2 * (e + 4 * kh) + x;        // unit column uc = e + 4 kh
-            T[(0 * 16 + col) * 32 + li] = o0;
-            T[(1 * 16 + col) * 32 + li] = o1;
-            T[(2 * 16 + col) * 32 + li] = o2;
-            T[(3 * 16 + col) * 32 + li] = o3;
+            o[0][x][e] = A + D;
+            o[1][x][e] = fmaf(2.f, E, Bv);
+            o[2][x][e] = fmaf(4.f, D, Cv);
+            o[3][x][e] = fmaf(8.f, E, Bv) + Fv;
         }
-    __builtin_amdgcn_wave_barrier();
     bq.x += bq2.x; bq.y += bq2.y; bq.z += bq2.z; bq.w += bq2.w;
     const float scale = a.scale;
     float4 piv = make_float4(0.f, 0.f, 0.f, 0.f), s1 = piv, s2 = piv;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const int pp = i * 8 + pl;
-        float4 v = *reinterpret_cast<const float4*>(T + pp * 32 + cq * 4);
+        float4 v = make_float4(o[i >> 1][i & 1][0], o[i >> 1][i & 1][1], o[i >> 1][i & 1][2], o[i >> 1][i & 1][3]);
         v.x += bq.x; v.y += bq.y; v.z += bq.z; v.w += bq.w;
         if (has_res) { v.x += rres[i].x; v.y += rres[i].y; v.z += rres[i].z; v.w += rres[i].w; }
         v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
-        *reinterpret_cast<float4*>(outb + roff[i]) = v;
+        *reinterpret_cast<float4*>(outb + poff(i)) = v;
         if (i == 0) piv = v;
         const float dx = v.x - piv.x, dy = v.y - piv.y, dz = v.z - piv.z, dw = v.w - piv.w;
         s1.x += dx; s1.y += dy; s1.z += dz; s1.w += dw;
         s2.x = fmaf(dx, dx, s2.x); s2.y = fmaf(dy, dy, s2.y); s2.z = fmaf(dz, dz, s2.z); s2.w = fmaf(dw, dw, s2.w);
     }
     if (!a.stats) return;
-    // 8 values per lane and channel -> the 8 pixel lanes of a channel quad (equal-count Chan merges) -> 64 pixels
+    // 8 values per lane and channel (the unit's 4 x 2 pixels) -> the 8 unit columns of a channel quad (equal-count Chan
+    // merges) -> 64 pixels
     float mean[4] = {piv.x + s1.x * 0.125f, piv.y + s1.y * 0.125f, piv.z + s1.z * 0.125f, piv.w + s1.w * 0.125f};
     float m2[4] = {fmaxf(s2.x - s1.x * s1.x * 0.125f, 0.f), fmaxf(s2.y - s1.y * s1.y * 0.125f, 0.f),
                    fmaxf(s2.z - s1.z * s1.z * 0.125f, 0.f), fmaxf(s2.w - s1.w * s1.w * 0.125f, 0.f)};
@@ -210,7 +228,7 @@ __device__ __forceinline__ void w2d_out(f32x16 (&acc)[3][NJ], float* X, int b, i
         }
         cnt *= 2.f;
     }
-    if (pl == 0) {
+    if (ucD == 0) {
         // statistics blocks of this kernel: 4 x 16 pixel strips, row-major over the sample (stats_nblk = H W / 64)
         const int strip = ((y0 >> 2) + gD) * (W >> 4) + (x0 >> 4);
         float* dst = a.stats + (((int64_t)b * a.stats_nblk + strip) * Cout + ch0 + cq * 4) * 2;
@@ -429,7 +447,7 @@ __device__ __forceinline__ void conv3x3_w2d_body(const ConvArgs& a, float* smem,
     // component 1, one staged GroupNorm quad (SX) behind component 2.
 #define W2_MF(V, c, K)                                                                                               \
     _Pragma("unroll") for (int j = 0; j < NJ; ++j)                                                                   \
-        acc[c][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[((c) == 0 && CH == 1) ? 4 : (c)].K, bF[c][j].K, acc[c][j], 0, 0, 0); \
+        acc[c][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bF[c][j].K, V[((c) == 0 && CH == 1) ? 4 : (c)].K, acc[c][j], 0, 0, 0); \
     W2_FENCE
 #define W2_BL(C, NJB, WB) _Pragma("unroll") for (int j = 0; j < NJ; ++j) W2_BLOAD(C, j, NJB, WB, bF)
     // twelve (component, k-step) pairs of NJ MFMAs, one filler group behind each

@@ -1178,7 +1178,9 @@ static int op_conv3x3_winograd(const float* in1, int C1, const float* in2, int C
         c.gn = GnParams{mean, scl, beta};
         c.gn_silu = silu;
     }
-    return launch_conv(c, s);
+    // the 2-D entry names its kernel: every shape conv_w2d_shape_ok admits runs it (launch_conv's policy would hand images of
+    // up to 2048 pixels to another kernel, or refuse their fused GroupNorm input)
+    return two_d ? launch_w2d(c, s) : launch_conv(c, s);
 }
 
 int64_t flowse_op_conv3x3_f43_scratch_floats(int B, int H, int W, int C, int Cout) {
