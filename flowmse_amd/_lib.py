@@ -80,6 +80,11 @@ SIGNATURES = {
     "flowse_resample_num_taps": (_i, [_i, _i]),
     "flowse_resample_taps": (_i, [_i, _i, C.POINTER(_d), _i]),
     "flowse_resample_poly": (_i, [_fp, _i, _i, _i, _i, _fp, _i, _vp]),
+    "flowse_estoi_num_taps": (_i, []),
+    "flowse_estoi_taps": (_i, [C.POINTER(_d), _i]),
+    "flowse_metrics_workspace_bytes": (_i64, [_i]),
+    "flowse_estoi": (_i, [_fp, _fp, _i, _vp, _i64, _vp, _vp]),
+    "flowse_energy_ratios": (_i, [_fp, _fp, _fp, _i, _vp, _i64, _vp, _vp]),
     "flowse_profile_begin": (_i, [_vp, _i]),
     "flowse_profile_end": (_i, [_vp, C.c_char_p, _i]),
     "flowse_upfirdn2d": (_i, [_fp, _fp] + [_i] * 13 + [_fp, _i, _i, _vp]),

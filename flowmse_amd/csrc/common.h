@@ -15,6 +15,8 @@ enum { OK = 0, ERR_ARG = 1, ERR_HIP = 2, ERR_STATE = 3, ERR_SHAPE = 4 };
 
 void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
+// modified Bessel function I0 by its power series (resample.hip): the Kaiser windows of the resampler and of the ESTOI taps
+double bessel_i0(double x);
 
 #define FLOWSE_HIP(call)                                                        \
     do {                                                                        \

@@ -61,8 +61,9 @@ static int make_ratio(const char* who, int up, int down, Ratio* r) {
     return OK;
 }
 
-// modified Bessel function I0 by its power series sum_k ((x / 2)^k / k!)^2 (x = 5 at most here: 25 terms reach 1e-17)
-static double bessel_i0(double x) {
+// modified Bessel function I0 by its power series sum_k ((x / 2)^k / k!)^2 (x = 5 here, 5.65 in metrics.hip: 25 to 30 terms
+// reach 1e-17); declared in common.h
+double bessel_i0(double x) {
     const double q = 0.25 * x * x;
     double term = 1.0, sum = 1.0;
     for (int k = 1; k < 200; ++k) {

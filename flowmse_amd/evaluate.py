@@ -7,7 +7,9 @@ Same arguments and outputs (``files/*.wav``, ``_results.csv``, ``_avg_results.tx
 utterance it follows evaluate.py:101-136: load wav -> normalise by max|y| -> STFT -> magnitude compression
 (spec_fwd) -> pad frames to a multiple of 64 -> white-box Euler sampler -> spec_back -> iSTFT -> rescale.
 Wave I/O uses scipy (torchaudio / soundfile are optional), PESQ / ESTOI are reported when the ``pesq`` / ``pystoi``
-packages are importable, SI-SDR / SI-SIR / SI-SAR always (utils.py:10-35).  ``--synthetic`` runs with synthetic
+packages are importable, SI-SDR / SI-SIR / SI-SAR always (utils.py:10-35); ``--metrics device`` takes ESTOI and the three
+energy ratios from the library instead (``flowmse_amd.metrics``: float64 on the GPU, no optional package, one read-back
+per sampler call), PESQ stays a host import.  ``--synthetic`` runs with synthetic
 weights and synthetic noisy/clean pairs (no checkpoint or dataset needed) as an end-to-end smoke demo.
 
 ``--noise keyed`` draws the prior noise from the keyed stream of ``flowmse_amd.util.noise`` (addressed by seed, file name,
@@ -74,12 +76,14 @@ def enhance_waveform(model, y, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", z=
     return x_hat if as_tensor else x_hat.cpu().numpy()
 
 
-def enhance_batch(model, ys, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", noise_keys=None, noise_seed=0):
+def enhance_batch(model, ys, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", noise_keys=None, noise_seed=0, as_tensor=False):
     """Several utterances whose padded frame counts agree, as ONE sampler call (the reference enhances one file at
     a time, evaluate.py:97; trajectories are independent, so batching changes nothing but throughput).
-    ys: list of float tensors [1, samples_i] on the target device.  Returns a list of numpy waveforms.
+    ys: list of float tensors [1, samples_i] on the target device.  Returns a list of numpy waveforms (with ``as_tensor``
+    the same values as 1-D tensors left on the device).
     ``noise_keys`` (one key per utterance) / ``noise_seed``: keyed prior noise, which follows the utterance and not its
     row or batch."""
+    host = (lambda t: t.reshape(-1)) if as_tensor else (lambda t: t.squeeze().cpu().numpy())
     norms = [y.abs().max().item() for y in ys]
     dm = model.data_module
     fused = hasattr(dm, "fused_ok") and all(dm.fused_ok(y) for y in ys)
@@ -91,22 +95,21 @@ def enhance_batch(model, ys, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", nois
     sample, _ = get_white_box_solver(odesolver, model.ode, model, Y=Y, Y_prior=Y, T_rev=T_rev, t_eps=t_eps, N=N,
                                      noise_keys=noise_keys, noise_seed=noise_seed)()
     if fused:                      # decompression + iSTFT + rescale: one HIP kernel per utterance
-        return [dm.synthesize(sample[i:i + 1], y.size(1), n).squeeze().cpu().numpy()
-                for i, (y, n) in enumerate(zip(ys, norms))]
-    return [(model.to_audio(sample[i, 0], y.size(1)) * n).squeeze().cpu().numpy()
-            for i, (y, n) in enumerate(zip(ys, norms))]
+        return [host(dm.synthesize(sample[i:i + 1], y.size(1), n)) for i, (y, n) in enumerate(zip(ys, norms))]
+    return [host(model.to_audio(sample[i, 0], y.size(1)) * n) for i, (y, n) in enumerate(zip(ys, norms))]
 
 
 def enhance_concurrent(model, ys, lanes, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", groups=None, noise_keys=None,
-                       noise_seed=0):
+                       noise_seed=0, as_tensor=False):
     """Several utterances of ANY lengths as one multi-lane sampler call: up to ``lanes`` (1..4) of them are in flight on
     the GPU at a time, on streams that share one copy of the weights (``get_white_box_solver_multi``).  Analysis and
     synthesis run per utterance as in ``enhance_batch``.  ``groups`` (optional): lists of indices into ``ys``, each an
     equal-padded-length batch that is sampled as ONE item; default every utterance is its own item, and then every
     waveform equals ``enhance_waveform``'s for the same prior noise, bit for bit.  A throughput option: a single
     utterance's latency goes up.  ys: list of float tensors [1, samples_i] on the target device.  Returns the list of
-    numpy waveforms, in the order of ``ys``.  ``noise_keys`` (one key per utterance, in the order of ``ys``) /
-    ``noise_seed``: keyed prior noise."""
+    numpy waveforms (with ``as_tensor``: 1-D device tensors), in the order of ``ys``.  ``noise_keys`` (one key per
+    utterance, in the order of ``ys``) / ``noise_seed``: keyed prior noise."""
+    host = (lambda t: t.reshape(-1)) if as_tensor else (lambda t: t.squeeze().cpu().numpy())
     norms = [y.abs().max().item() for y in ys]
     dm = model.data_module
     fused = hasattr(dm, "fused_ok") and all(dm.fused_ok(y) for y in ys)
@@ -123,9 +126,9 @@ def enhance_concurrent(model, ys, lanes, N=5, T_rev=1.0, t_eps=0.03, odesolver="
     for g, sample in zip(groups, samples):
         for j, i in enumerate(g):
             if fused:              # decompression + iSTFT + rescale: one HIP kernel per utterance
-                out[i] = dm.synthesize(sample[j:j + 1], ys[i].size(1), norms[i]).squeeze().cpu().numpy()
+                out[i] = host(dm.synthesize(sample[j:j + 1], ys[i].size(1), norms[i]))
             else:
-                out[i] = (model.to_audio(sample[j, 0], ys[i].size(1)) * norms[i]).squeeze().cpu().numpy()
+                out[i] = host(model.to_audio(sample[j, 0], ys[i].size(1)) * norms[i])
     return out
 
 
@@ -221,6 +224,10 @@ def build_parser():
                          "behaviour). keyed: a counter-based stream addressed by (seed, file name, bin, frame), so an "
                          "utterance's files do not depend on --gpus, --streams, the processing order or what else is in "
                          "the directory. Default: torch with --gpus 1, keyed with --gpus > 1")
+    ap.add_argument("--metrics", choices=("host", "device"), default="host",
+                    help="host: ESTOI from pystoi where importable (nan otherwise), the energy ratios in numpy. device: ESTOI "
+                         "and SI-SDR / SI-SIR / SI-SAR in float64 on the GPU (flowmse_amd.metrics), read back once per "
+                         "sampler call; PESQ stays on the host either way")
     ap.add_argument("--gpus", type=int, default=1,
                     help="shard the test set over this many GPUs of this node, one process each (keyed noise only)")
     return ap
@@ -301,6 +308,29 @@ def _metrics(pesq, stoi, x, y, x_hat, sr=16000):
     return (p, e) + tuple(energy_ratios(x_hat, x, y - x))
 
 
+def _metrics_device(pesq, triples, sr=16000):
+    """The rows of ``_metrics`` for the utterances of ONE sampler call with ``--metrics device``: ``triples`` is a list of
+    (clean x: numpy, noisy y: numpy or device tensor, enhanced x_hat: 1-D device tensor).  ESTOI and the energy ratios of
+    all of them are queued on the device and read back once; PESQ as in ``_metrics``.  Returns the rows and the enhanced
+    waveforms as numpy arrays."""
+    from flowmse_amd.metrics import metrics_device
+    dev = triples[0][2].device
+    table = torch.empty(len(triples), 4, dtype=torch.float64, device=dev)
+    for row, (x, y, x_hat) in zip(table, triples):
+        metrics_device(x, y.reshape(-1) if isinstance(y, torch.Tensor) else y, x_hat, out=row, sr=sr)
+    table = table.cpu().numpy()                                    # the one read-back
+    rows, waves = [], []
+    for vals, (x, _, x_hat) in zip(table, triples):
+        w = x_hat.cpu().numpy()
+        try:
+            p = pesq(sr, x, w, "wb") if pesq else float("nan")
+        except Exception:
+            p = float("nan")
+        rows.append((p,) + tuple(float(v) for v in vals))
+        waves.append(w)
+    return rows, waves
+
+
 def _write_reports(target_dir, data, args, model, epoch, noise_seed):
     with open(os.path.join(target_dir, "_results.csv"), "w", newline="") as f:
         w = csv.writer(f)
@@ -321,6 +351,8 @@ def _write_reports(target_dir, data, args, model, epoch, noise_seed):
         f.write(f"precision: {args.precision}\n")
         f.write(f"batch: {args.batch}\nstreams: {args.streams}\nseed: {args.seed}\n")
         f.write(f"noise: {args.noise}\nnoise seed: {noise_seed}\ngpus: {args.gpus}\n")
+        if getattr(args, "metrics", "host") == "device":           # a host run's file is unchanged
+            f.write("metrics: device\n")
 
 
 _COLUMNS = ("filename", "pesq", "estoi", "si_sdr", "si_sir", "si_sar")
@@ -420,6 +452,7 @@ def _main_keyed(args, ap):
     # the batches of the WHOLE set, dealt to the ranks unsplit: batch composition does not depend on the world size
     batches = [ids for _, ids in plan_shards([_padded_frames(n) for n in n_samples], world, args.batch, level=False)[rank]]
     per_call = args.streams * _ITEMS_PER_LANE if args.streams > 1 else 1
+    on_device = args.metrics == "device"
     rows, t0 = [], time.time()
     for k in range(0, len(batches), per_call):
         chunk = batches[k:k + per_call]
@@ -430,13 +463,17 @@ def _main_keyed(args, ap):
         if args.streams > 1:
             pos = {i: j for j, i in enumerate(flat)}
             outs = enhance_concurrent(model, ys, args.streams, groups=[[pos[i] for i in g] for g in chunk],
-                                      noise_keys=keys, **kw)
+                                      noise_keys=keys, as_tensor=on_device, **kw)
         else:
-            outs = enhance_batch(model, ys, noise_keys=keys, **kw)
-        for i, x_hat in zip(flat, outs):
-            x, y = waves[i]
+            outs = enhance_batch(model, ys, noise_keys=keys, as_tensor=on_device, **kw)
+        if on_device:
+            metric_rows, outs = _metrics_device(pesq, [(waves[i][0], yd, x_hat) for i, yd, x_hat in zip(flat, ys, outs)])
+        else:
+            metric_rows = [_metrics(pesq, stoi, waves[i][0], waves[i][1], x_hat) for i, x_hat in zip(flat, outs)]
+        for i, x_hat, m in zip(flat, outs, metric_rows):
+            y = waves[i][1]
             _write_wav(target_dir + "files/" + names[i], x_hat, 16000)
-            rows.append((i, names[i]) + _metrics(pesq, stoi, x, y, x_hat) + (y.shape[0] // 128 + 1,))
+            rows.append((i, names[i]) + m + (y.shape[0] // 128 + 1,))
     rows = gather_rows(rows)
     dt = time.time() - t0
     if rank == 0:
@@ -481,6 +518,15 @@ def main(argv=None):
     frames, t0 = 0, time.time()
     from flowmse_amd.parallel import batches_by_length
     enhanced = {}
+    on_device = args.metrics == "device"
+    metric_rows = {}                   # --metrics device: idx -> row, filled after each sampler call
+
+    def keep(ids, ys, outs):
+        if on_device:
+            rows, outs = _metrics_device(pesq, [(pairs[i][1], y, o) for i, y, o in zip(ids, ys, outs)], sr)
+            metric_rows.update(dict(zip(ids, rows)))
+        enhanced.update(dict(zip(ids, outs)))
+
     if args.seed is not None:
         torch.manual_seed(args.seed)
     if args.streams > 1:               # utterances (or equal-length batches of them) dealt to concurrent lanes
@@ -492,27 +538,30 @@ def main(argv=None):
             chunk = items[k:k + per_call]
             flat = [i for g in chunk for i in g]
             pos = {i: j for j, i in enumerate(flat)}
-            outs = enhance_concurrent(model, [torch.from_numpy(pairs[i][2])[None].cuda() for i in flat], args.streams,
+            ys = [torch.from_numpy(pairs[i][2])[None].cuda() for i in flat]
+            outs = enhance_concurrent(model, ys, args.streams,
                                       N=args.N, T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
-                                      odesolver=args.odesolver, groups=[[pos[i] for i in g] for g in chunk])
-            enhanced.update(dict(zip(flat, outs)))
+                                      odesolver=args.odesolver, groups=[[pos[i] for i in g] for g in chunk],
+                                      as_tensor=on_device)
+            keep(flat, ys, outs)
     elif args.batch > 1:               # group by padded frame count, largest first
         lens = [_padded_frames(p[2].shape[0]) for p in pairs]
         for _, ids in batches_by_length(range(len(pairs)), lens, args.batch):
-            outs = enhance_batch(model, [torch.from_numpy(pairs[i][2])[None].cuda() for i in ids], N=args.N,
+            ys = [torch.from_numpy(pairs[i][2])[None].cuda() for i in ids]
+            outs = enhance_batch(model, ys, N=args.N,
                                  T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
-                                 odesolver=args.odesolver)
-            enhanced.update(dict(zip(ids, outs)))
+                                 odesolver=args.odesolver, as_tensor=on_device)
+            keep(ids, ys, outs)
     for idx, (name, x, y) in enumerate(pairs):
-        if idx in enhanced:
-            x_hat = enhanced[idx]
-        else:
-            x_hat = enhance_waveform(model, torch.from_numpy(y)[None].cuda(), N=args.N,
-                                     T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
-                                     odesolver=args.odesolver)
+        if idx not in enhanced:
+            yd = torch.from_numpy(y)[None].cuda()
+            keep([idx], [yd], [enhance_waveform(model, yd, N=args.N,
+                                                T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
+                                                odesolver=args.odesolver, as_tensor=on_device)])
+        x_hat = enhanced.pop(idx)
         frames += y.shape[0] // 128 + 1
         _write_wav(target_dir + "files/" + name, x_hat, sr)
-        for c, v in zip(_COLUMNS, (name,) + _metrics(pesq, stoi, x, y, x_hat, sr)):
+        for c, v in zip(_COLUMNS, (name,) + (metric_rows[idx] if on_device else _metrics(pesq, stoi, x, y, x_hat, sr))):
             data[c].append(v)
     dt = time.time() - t0
 

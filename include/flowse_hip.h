@@ -339,6 +339,46 @@ int flowse_resample_num_taps(int up, int down);
 int flowse_resample_taps(int up, int down, double* taps, int cap);
 int flowse_resample_poly(const float* sig, int B, int L, int up, int down, float* out, int L_out, void* stream);
 
+/* ---- evaluation metrics on the device: ESTOI and SI-SDR / SI-SIR / SI-SAR (opt-in: evaluate --metrics device) ----
+ * ESTOI is DEFINED here, step by step after pystoi.stoi(x, y, 16000, extended=True) (pystoi 0.3 / 0.4); the package is
+ * not available where this library is built and tested, so equality with it has NOT been checked -- the float64
+ * restatement flowmse_amd.metrics.estoi_reference is what the kernels are held to.  All arithmetic float64; inputs are
+ * float32 waveforms at 16 kHz of equal length L (clean x, processed y); EPS = 2^-52.
+ *   1. 10 kHz: fc = 1/16, t = -290 .. 290, h[t] = kaiser(581, 0.1102 (60 - 8.7))[t] 2 5 fc sinc(2 fc t), h /= sum h;
+ *      x10 = scipy.signal.resample_poly(x, 5, 8, window = h): x10[n] = sum_m x[m] 5 h[290 + 8 n - 5 m], L10 = ceil(5 L / 8).
+ *   2. w = hanning(258)[1:-1]; first-pass frames start at 128 i < L10 - 256 (f0 = ceil((L10 - 256) / 128) of them);
+ *      e[i] = 20 log10(|w x10[128 i : 128 i + 256]| + EPS) on the CLEAN signal; frame i is kept iff max(e) - 40 - e[i] < 0;
+ *      both signals are rebuilt by overlap-adding their K kept windowed frames at hop 128.
+ *   3. The rebuilt signals are framed the same way (K - 1 frames, w again), 512-point DFT, 15 third-octave bands with bin
+ *      ranges [7,9) [9,11) [11,14) [14,17) [17,22) [22,27) [27,34) [34,43) [43,55) [55,69) [69,87) [87,109) [109,138)
+ *      [138,174) [174,219): X_tob[b][j] = sqrt(sum over the band of |X[k][j]|^2).
+ *   4. K - 1 < 30 or L10 <= 256: the result is 1e-5.
+ *   5. Segments m = 30 .. K - 1 take columns [m - 30, m) of both band matrices (15 x 30); each is normalised: row mean
+ *      over time subtracted, rows divided by (|row| + EPS), column mean over bands subtracted, columns divided by
+ *      (|col| + EPS); d = sum(x_n y_n) / 30 / (number of segments).
+ * The kept count K is decided on the device: later grids are sized for f0 frames, and blocks past K leave.  No
+ * floating-point atomics: the same input gives the same bits.
+ * Energy ratios (reference utils.py:26-35) in float64 with n = noisy - clean, two passes: <est,s>, <s,s>, <est,n>, <n,n>
+ * give a_s and a_n; then |est - a_s s|^2, |a_n n|^2, |est - a_s s - a_n n|^2 element by element; out3 = SI-SDR, SI-SIR,
+ * SI-SAR in dB.
+ *   flowse_estoi_num_taps: 581.  flowse_estoi_taps: h of step 1 (sum 1; the resampler applies 5 h) in double into a HOST
+ *   buffer of `cap` doubles; host only, no device needed; cap < 581 or a null buffer -> FLOWSE_ERR_ARG.
+ *   flowse_metrics_workspace_bytes: bytes of device workspace either call needs for length L (one workspace serves both,
+ *   and any shorter L); -FLOWSE_ERR_ARG for L < 1 or L > 2^24.
+ *   flowse_estoi / flowse_energy_ratios: signals, workspace and out (1 / 3 doubles) are DEVICE memory owned by the caller.
+ *   L < 1, L > 2^24, a null pointer or workspace_bytes below flowse_metrics_workspace_bytes(L) -> FLOWSE_ERR_ARG with a
+ *   message, nothing launched.  The calls enqueue on `stream`, allocate nothing and never synchronise -- but for the first
+ *   flowse_estoi on a device, which builds the tap / window / twiddle table on the host, allocates it and copies it from
+ *   pageable memory (the runtime may wait for that) and records an event: make that call outside stream capture.  Calls
+ *   that share a workspace must be ordered by the caller (one stream, or events). */
+int flowse_estoi_num_taps(void);
+int flowse_estoi_taps(double* taps, int cap);
+int64_t flowse_metrics_workspace_bytes(int L);
+int flowse_estoi(const float* clean, const float* proc, int L, void* workspace, int64_t workspace_bytes, double* out,
+                 void* stream);
+int flowse_energy_ratios(const float* est, const float* clean, const float* noisy, int L, void* workspace,
+                         int64_t workspace_bytes, double* out3, void* stream);
+
 /* ---- in-library kernel timing (used by bench.py for the live roofline figure) -------------------------
  * Between _begin and _end every selected launch of this handle is bracketed by HIP events on the launch
  * stream (and the handle launches eagerly instead of replaying its hipGraph).  mode 0: only launches of the dominant
