@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("FLOWSE_LIB_PATH") or os.path.join(_HERE, "libflowse_h
 FLOWSE_MAX_LEVELS = 8
 FLOWSE_MAX_ATTN = 4
 FLOWSE_MAX_LANES = 4
+FLOWSE_MAX_SPEC_ROWS = 64
 FLOWSE_BYTES_WEIGHTS, FLOWSE_BYTES_OWNED = 0, 1
 
 
@@ -29,6 +30,10 @@ class flowse_config(C.Structure):
     _fields_ = [("nf", C.c_int32), ("num_levels", C.c_int32), ("ch_mult", C.c_int32 * FLOWSE_MAX_LEVELS),
                 ("num_res_blocks", C.c_int32), ("num_attn", C.c_int32),
                 ("attn_resolutions", C.c_int32 * FLOWSE_MAX_ATTN), ("image_size", C.c_int32)]
+
+
+class flowse_spec_row(C.Structure):
+    _fields_ = [("sig", C.c_void_p), ("L", C.c_int32), ("frame0", C.c_int32), ("scale_in", C.c_float)]
 
 
 if not os.path.exists(LIB_PATH):
@@ -77,6 +82,8 @@ SIGNATURES = {
     "flowse_istft_decompress": (_i, [_vp, _i, _i, _i, _f, _f, _fp, _i, _f, _vp]),
     "flowse_stft_compress_chunks": (_i, [_fp, _i, _f, _vp, _i, _i, _i, _f, _f, _vp]),
     "flowse_istft_decompress_chunks": (_i, [_vp, _i, _i, _i, _f, _f, _fp, _i, _f, _vp]),
+    "flowse_stft_compress_rows": (_i, [C.POINTER(flowse_spec_row), _i, _i, _vp, _f, _f, _vp]),
+    "flowse_istft_decompress_stacks": (_i, [_vp, _i, _i, _i, _i, _f, _f, _fp, _i, _f, _vp]),
     "flowse_resample_num_taps": (_i, [_i, _i]),
     "flowse_resample_taps": (_i, [_i, _i, C.POINTER(_d), _i]),
     "flowse_resample_poly": (_i, [_fp, _i, _i, _i, _i, _fp, _i, _vp]),

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct flowse_spec_row;   // include/flowse_hip.h
+
 namespace flowse {
 
 // status codes of the C ABI (include/flowse_hip.h)
@@ -464,6 +466,12 @@ int launch_stft_compress_chunks(const float* sig, int L, float scale_in, float* 
                                 float factor, float exponent, hipStream_t s);
 int launch_istft_decompress_chunks(const float* chunks_c64, int K, int Tc, int hop, float factor, float exponent,
                                    float* out, int Lout, float scale_out, hipStream_t s);
+// the chunk synthesis for S stacks of one geometry in one launch: [S][K][256][Tc] -> [S][Lout]
+int launch_istft_decompress_stacks(const float* chunks_c64, int S, int K, int Tc, int hop, float factor, float exponent,
+                                   float* out, int Lout, float scale_out, hipStream_t s);
+// the R rows [R,1,256,Tw] of one sampler call from up to FLOWSE_MAX_SPEC_ROWS signals; `rows`: HOST table
+int launch_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, float* out_c64, float factor, float exponent,
+                              hipStream_t s);
 // out = y + sigma * z   (complex64 as float pairs)
 int launch_axpy(const float* y, const float* z, float sigma, int64_t n, float* out, hipStream_t s);
 // out = y + sigma * z (y != null) or out = z (y == null), z = the keyed Philox noise of noise.hip; [B,1,F,T] complex64,

@@ -966,6 +966,26 @@ int flowse_istft_decompress_chunks(const void* chunks_c64, int K, int Tc, int ho
                                           scale_out, static_cast<hipStream_t>(stream));
 }
 
+int flowse_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, void* out_c64, float factor, float exponent,
+                              void* stream) {
+    if (!rows || !out_c64) {
+        set_error("flowse_stft_compress_rows: null argument");
+        return ERR_ARG;
+    }
+    return launch_stft_compress_rows(rows, R, Tw, static_cast<float*>(out_c64), factor, exponent,
+                                     static_cast<hipStream_t>(stream));
+}
+
+int flowse_istft_decompress_stacks(const void* chunks_c64, int S, int K, int Tc, int hop, float factor, float exponent,
+                                   float* out, int Lout, float scale_out, void* stream) {
+    if (!chunks_c64 || !out) {
+        set_error("flowse_istft_decompress_stacks: null argument");
+        return ERR_ARG;
+    }
+    return launch_istft_decompress_stacks(static_cast<const float*>(chunks_c64), S, K, Tc, hop, factor, exponent, out, Lout,
+                                          scale_out, static_cast<hipStream_t>(stream));
+}
+
 int flowse_profile_begin(flowse_model* m, int mode) {
     if (!m || (mode != 0 && mode != 1)) {
         set_error("flowse_profile_begin: bad argument");

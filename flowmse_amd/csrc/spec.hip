@@ -11,6 +11,7 @@
 #include <mutex>
 #include <vector>
 
+#include "../../include/flowse_hip.h"
 #include "common.h"
 
 namespace flowse {
@@ -46,27 +47,23 @@ static int ensure_tables(float** out) {
     return OK;
 }
 
-// grid (Tpad, B), 256 threads = 256 bins.  Frames t >= T are the zero padding of pad_spec.
-// Row b of the output holds frames row_frame0 * b + [0, Tpad) of signal sig + row_sig * b: (0, L) for a batch of
-// utterances, (hop, 0) for the chunks of one recording -- the same arithmetic per frame, so a chunk row is bit for bit
-// a slice of the whole spectrogram.
-__global__ __launch_bounds__(256) void stft_compress_kernel(const float* __restrict__ sig, int L, float scale_in,
-                                                            const float* __restrict__ tab, float2* __restrict__ out,
-                                                            int T, int Tpad, float factor, float exponent,
-                                                            int row_frame0, int row_sig) {
+// One frame by one block of 256 threads = 256 bins: frame t of `sig` (L samples, T = L / 128 + 1 frames) to *dst; frames
+// t >= T are the zero padding of pad_spec.  Every STFT kernel below is this function, so a frame's value depends on
+// (samples, scale_in, t) only -- not on the kernel, the row or the batch that asked for it.  Sample indices in 64 bits.
+__device__ __forceinline__ void stft_frame(const float* __restrict__ sig, int L, float scale_in,
+                                           const float* __restrict__ tab, float2* __restrict__ dst, int t, int T,
+                                           float factor, float exponent) {
     __shared__ float xw[NFFT], ct[NFFT], st[NFFT];
-    const int b = blockIdx.y, f = threadIdx.x;
-    const int t = b * row_frame0 + blockIdx.x;
-    float2* dst = out + ((int64_t)b * NBIN + f) * Tpad + blockIdx.x;
+    const int f = threadIdx.x;
     if (t >= T) {
         *dst = make_float2(0.f, 0.f);
         return;
     }
     for (int n = threadIdx.x; n < NFFT; n += 256) {
-        int j = t * HOP + n - PADC;                    // centre=True, reflect padding
+        int64_t j = (int64_t)t * HOP + n - PADC;       // centre=True, reflect padding
         if (j < 0) j = -j;
-        if (j >= L) j = 2 * (L - 1) - j;
-        xw[n] = sig[(int64_t)b * row_sig + j] * scale_in * tab[n];
+        if (j >= L) j = 2 * ((int64_t)L - 1) - j;
+        xw[n] = sig[j] * scale_in * tab[n];
         ct[n] = tab[NFFT + n];
         st[n] = tab[2 * NFFT + n];
     }
@@ -86,6 +83,36 @@ __global__ __launch_bounds__(256) void stft_compress_kernel(const float* __restr
     *dst = make_float2(re * s, im * s);
 }
 
+// grid (Tpad, B), 256 threads = 256 bins.  Row b of the output holds frames row_frame0 * b + [0, Tpad) of signal
+// sig + row_sig * b: (row_frame0, row_sig) = (0, L) for a batch of utterances, (hop, 0) for the chunks of one recording.
+__global__ __launch_bounds__(256) void stft_compress_kernel(const float* __restrict__ sig, int L, float scale_in,
+                                                            const float* __restrict__ tab, float2* __restrict__ out,
+                                                            int T, int Tpad, float factor, float exponent,
+                                                            int row_frame0, int row_sig) {
+    const int b = blockIdx.y;
+    stft_frame(sig + (int64_t)b * row_sig, L, scale_in, tab, out + ((int64_t)b * NBIN + threadIdx.x) * Tpad + blockIdx.x,
+               b * row_frame0 + blockIdx.x, T, factor, exponent);
+}
+
+// The rows of ONE sampler call from up to FLOWSE_MAX_SPEC_ROWS different signals: grid (Tw, R), row r = frames
+// [frame0_r, frame0_r + Tw) of signal r under its own scale.  The table travels in the kernel's argument block (by value:
+// no allocation, no upload, nothing for the host to keep alive) and is indexed by the block's row only.
+struct SpecRowTable {
+    flowse_spec_row row[FLOWSE_MAX_SPEC_ROWS];
+};
+static_assert(sizeof(flowse_spec_row) == 24 && sizeof(SpecRowTable) <= 2048, "the table must fit the argument block");
+
+__global__ __launch_bounds__(256) void stft_compress_rows_kernel(const SpecRowTable rows, const float* __restrict__ tab,
+                                                                 float2* __restrict__ out, int Tw, float factor,
+                                                                 float exponent) {
+    const int r = blockIdx.y;
+    const float* sig = rows.row[r].sig;
+    const int L = rows.row[r].L, frame0 = rows.row[r].frame0;
+    const float scale_in = rows.row[r].scale_in;
+    stft_frame(sig, L, scale_in, tab, out + ((int64_t)r * NBIN + threadIdx.x) * Tw + blockIdx.x, frame0 + blockIdx.x,
+               L / HOP + 1, factor, exponent);
+}
+
 // Frame t of a recording held as K chunks [K][NBIN][Tc] that start `hop` frames apart (To = Tc - hop <= hop frames of
 // overlap, so at most two chunks cover a frame): chunk k = min(t / hop, K - 1) at j = t - k hop; in the first To frames
 // of every chunk but the first, the linear cross-fade  a + w (b - a),  w = (j + 0.5) / To,  from the previous chunk's
@@ -102,7 +129,8 @@ __device__ __forceinline__ float2 seam_frame(const float2* __restrict__ chunks, 
 }
 
 // grid (ceil(Lout / 128), B), 256 threads: sample = tid & 127, the two halves split the bins.
-// SEAM: `spec` is the chunk stack above (B == 1, T == Tpad == Tg frames); else [B][NBIN][Tpad].
+// SEAM: `spec` is B chunk stacks as above, one after the other ([B][K][NBIN][Tc]; T == Tpad == Tg frames each; B == 1 for
+// the chunks of one recording); else [B][NBIN][Tpad].
 template <bool SEAM>
 __global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __restrict__ spec, int T, int Tpad,
                                                                float factor, float exponent,
@@ -127,7 +155,8 @@ __global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __r
         const int t = t_lo + fr;
         float2 z = make_float2(0.f, 0.f);
         if (t < T) {
-            z = SEAM ? seam_frame(spec, f, t, K, Tc, hop) : spec[((int64_t)b * NBIN + f) * Tpad + t];
+            z = SEAM ? seam_frame(spec + (int64_t)b * K * NBIN * Tc, f, t, K, Tc, hop)
+                     : spec[((int64_t)b * NBIN + f) * Tpad + t];
             // spec_back: (|z| / factor)^(1/e) * exp(j arg z)
             z.x /= factor;
             z.y /= factor;
@@ -225,20 +254,60 @@ int launch_istft_decompress(const float* spec_c64, int B, int T, int Tpad, float
     return OK;
 }
 
-int launch_istft_decompress_chunks(const float* chunks_c64, int K, int Tc, int hop, float factor, float exponent,
-                                   float* out, int Lout, float scale_out, hipStream_t s) {
+// S chunk stacks of one geometry, [S][K][NBIN][Tc] -> [S][Lout]; `who` names the entry in the error text
+static int launch_istft_stacks(const char* who, const float* chunks_c64, int S, int K, int Tc, int hop, float factor,
+                               float exponent, float* out, int Lout, float scale_out, hipStream_t s) {
     const int64_t Tg = (int64_t)(K - 1) * hop + Tc;
-    if (!chunks_ok(K, Tc, hop) || Lout < 1 || Lout > (Tg - 1) * HOP + NFFT - PADC || factor == 0.f) {
-        set_error("istft chunks: need 1 <= hop <= Tc <= 2 hop, 1 <= K <= 65535, 1 <= Lout <= 128 (Tg - 1) + 255 and "
-                  "factor != 0 (got K=%d Tc=%d hop=%d Lout=%d)", K, Tc, hop, Lout);
+    if (S < 1 || S > 65535 || !chunks_ok(K, Tc, hop) || Lout < 1 || Lout > (Tg - 1) * HOP + NFFT - PADC || factor == 0.f) {
+        set_error("istft %s: need 1 <= hop <= Tc <= 2 hop, 1 <= K <= 65535, 1 <= S <= 65535, 1 <= Lout <= 128 (Tg - 1) + 255 "
+                  "and factor != 0 (got S=%d K=%d Tc=%d hop=%d Lout=%d)", who, S, K, Tc, hop, Lout);
         return ERR_SHAPE;
     }
     float* tab = nullptr;
     int rc = ensure_tables(&tab);
     if (rc != OK) return rc;
-    hipLaunchKernelGGL(istft_decompress_kernel<true>, dim3((Lout + HOP - 1) / HOP, 1), dim3(256), 0, s,
+    hipLaunchKernelGGL(istft_decompress_kernel<true>, dim3((Lout + HOP - 1) / HOP, S), dim3(256), 0, s,
                        reinterpret_cast<const float2*>(chunks_c64), (int)Tg, (int)Tg, factor, exponent, tab, out, Lout,
                        scale_out, K, Tc, hop);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+int launch_istft_decompress_chunks(const float* chunks_c64, int K, int Tc, int hop, float factor, float exponent,
+                                   float* out, int Lout, float scale_out, hipStream_t s) {
+    return launch_istft_stacks("chunks", chunks_c64, 1, K, Tc, hop, factor, exponent, out, Lout, scale_out, s);
+}
+
+int launch_istft_decompress_stacks(const float* chunks_c64, int S, int K, int Tc, int hop, float factor, float exponent,
+                                   float* out, int Lout, float scale_out, hipStream_t s) {
+    return launch_istft_stacks("stacks", chunks_c64, S, K, Tc, hop, factor, exponent, out, Lout, scale_out, s);
+}
+
+int launch_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, float* out_c64, float factor, float exponent,
+                              hipStream_t s) {
+    if (R < 1 || R > FLOWSE_MAX_SPEC_ROWS || Tw < 1 || Tw > (1 << 23)) {
+        set_error("stft rows: need 1 <= R <= %d and 1 <= Tw <= 2^23 (got R=%d Tw=%d)", FLOWSE_MAX_SPEC_ROWS, R, Tw);
+        return ERR_SHAPE;
+    }
+    SpecRowTable t;
+    for (int r = 0; r < FLOWSE_MAX_SPEC_ROWS; ++r) {
+        t.row[r] = rows[r < R ? r : 0];                // the slots past R are never read; keep them defined
+        if (r >= R) continue;
+        if (!rows[r].sig || rows[r].frame0 < 0) {
+            set_error("stft rows: row %d has a null signal or frame0 < 0 (frame0=%d)", r, rows[r].frame0);
+            return ERR_ARG;
+        }
+        if (rows[r].L <= PADC || (int64_t)rows[r].frame0 + Tw > (1 << 23)) {
+            set_error("stft rows: need L > %d and frame0 + Tw <= 2^23 (row %d: L=%d frame0=%d Tw=%d)", PADC, r, rows[r].L,
+                      rows[r].frame0, Tw);
+            return ERR_SHAPE;
+        }
+    }
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(stft_compress_rows_kernel, dim3(Tw, R), dim3(256), 0, s, t, tab, reinterpret_cast<float2*>(out_c64),
+                       Tw, factor, exponent);
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

@@ -127,6 +127,45 @@ class SpecTransform:
                                                                float(scale), _lib.current_stream()))
         return out
 
+    # ---- rows and stacks from many recordings (flowmse_amd.pooled) ------------------------------------
+    def analyze_rows(self, rows, Tw):
+        """The input rows of ONE sampler call from several signals in one kernel: ``rows`` is a list of
+        ``(sig, frame0, scale)`` with ``sig`` a 1-D float32 'cuda' tensor (two rows may share one) -> complex64
+        [R, 1, 256, Tw], row r = frames [frame0, frame0 + Tw) of ``analyze(sig[None], scale)`` bit for bit (zeros past
+        L // 128 + 1).  1 <= R <= 64 (``FLOWSE_MAX_SPEC_ROWS``: the table travels in the kernel's argument block)."""
+        from flowmse_amd import _lib
+        R = len(rows)
+        if not 1 <= R <= _lib.FLOWSE_MAX_SPEC_ROWS:
+            raise ValueError(f"analyze_rows takes 1..{_lib.FLOWSE_MAX_SPEC_ROWS} rows, got {R}")
+        device = rows[0][0].device
+        table = (_lib.flowse_spec_row * R)()
+        for d, (sig, frame0, scale) in zip(table, rows):
+            if sig.dim() != 1 or sig.dtype != torch.float32 or not sig.is_contiguous() or sig.device != device:
+                raise ValueError(f"analyze_rows: every signal is a contiguous 1-D float32 tensor on {device}, got "
+                                 f"{sig.dtype} {tuple(sig.shape)} on {sig.device}")
+            d.sig, d.L, d.frame0, d.scale_in = sig.data_ptr(), sig.numel(), int(frame0), float(scale)
+        out = torch.empty(R, 1, 256, int(Tw), dtype=torch.complex64, device=device)
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib.flowse_stft_compress_rows(table, R, int(Tw), _lib.ptr(out), float(self.spec_factor),
+                                                          float(self.spec_abs_exponent), _lib.current_stream()))
+        return out
+
+    def synthesize_stacks(self, chunks, S, hop, length, scale=1.0):
+        """``synthesize_chunks`` for S chunk stacks of one geometry in one kernel: chunks complex64 [S * K, 1, 256, Tc],
+        rows ordered (stack, chunk) -> [S, length], row s bit for bit ``synthesize_chunks`` of stack s."""
+        from flowmse_amd import _lib
+        chunks = chunks.contiguous()
+        S = int(S)
+        rows, _, F, Tc = chunks.shape
+        if S < 1 or rows % S:
+            raise ValueError(f"synthesize_stacks: {rows} chunk rows do not make {S} equal stacks")
+        out = torch.empty(S, length, dtype=torch.float32, device=chunks.device)
+        with torch.cuda.device(chunks.device):
+            _lib.check(_lib.lib.flowse_istft_decompress_stacks(_lib.ptr(chunks), S, rows // S, Tc, int(hop),
+                                                               float(self.spec_factor), float(self.spec_abs_exponent),
+                                                               _lib.ptr(out), length, float(scale), _lib.current_stream()))
+        return out
+
     # ---- STFT pair ------------------------------------------------------------------------------
     def _stft_args(self, ref):
         return dict(n_fft=self.n_fft, hop_length=self.hop_length, window=self._win(ref), center=True)

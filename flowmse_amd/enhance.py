@@ -3,7 +3,7 @@
 
     python -m flowmse_amd.enhance --input WAV_OR_DIR --output DIR --ckpt MODEL.ckpt [--N 5] [--batch 8]
                                   [--chunk_frames 256] [--overlap_frames 32] [--noise keyed|torch] [--seed S]
-                                  [--resample [--output_rate 16000|input]]
+                                  [--resample [--output_rate 16000|input]] [--pool [--channels first|all]]
 
 Unlike ``flowmse_amd.evaluate`` it needs no clean files and reports no metrics.  Every recording goes through
 ``flowmse_amd.chunked.enhance_long``: one that fits a single chunk is enhanced exactly as ``evaluate`` would; a longer
@@ -26,6 +26,15 @@ absolute 16 kHz frame).  ``--output_rate 16000`` (default) writes the enhanced s
 ``--output_rate input`` resamples it back on the device to the file's own rate, trimmed to the input's sample count.  Such a
 file carries NOTHING above 8 kHz: the network never saw that band, and the way back only interpolates.
 ``--synthetic_rate HZ`` generates the synthetic signals at another rate, to exercise all this without a checkpoint.
+
+Pooling.  Without ``--pool`` a sampler call holds rows of ONE recording, so a folder of short clips runs at batch width 1.
+``--pool`` (``flowmse_amd.pooled``) cuts the rows of all files -- one per (file, channel, chunk) -- into calls of exactly
+``--batch`` rows; a file's bytes still depend on the file, its name, the seed and the settings only, not on the folder.  At
+``--batch 1`` a mono file gets the bytes it gets without the flag; at wider batches it agrees to fp32 tolerance.  Keyed noise
+only.  ``--channels all`` (needs ``--pool``) enhances every channel of a multi-channel file independently, normalised by one
+factor per file, and writes a file with the input's channel count; ``--channels first`` (default) reads channel 0, as ever.
+``--synthetic_channels 1,2,...`` gives the synthetic signals that many channels (channel c > 0: an independent signal at
+half the level of channel 0).
 """
 import argparse
 import glob
@@ -37,11 +46,22 @@ import torch
 
 from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, enhance_long, plan_chunks
 from flowmse_amd.evaluate import _load_model, _seconds_arg, _synthetic_pairs, _write_wav
-from flowmse_amd.resample import rational, resample
+from flowmse_amd.pooled import MAX_BATCH, enhance_pooled
+from flowmse_amd.resample import out_len, rational, resample
 from flowmse_amd.util.noise import utterance_key
-from flowmse_amd.util.other import read_wav
+from flowmse_amd.util.other import read_wav, read_wav_channels
 
 SAMPLE_RATE = 16000
+
+
+def _channels_arg(v):
+    try:
+        chans = [int(x) for x in v.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--synthetic_channels takes a comma list of channel counts, got {v!r}")
+    if not chans or min(chans) < 1:
+        raise argparse.ArgumentTypeError(f"--synthetic_channels takes counts >= 1, got {v!r}")
+    return chans
 
 
 def build_parser():
@@ -59,9 +79,9 @@ def build_parser():
     ap.add_argument("--last_eval_point", type=float, default=0.03)
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "bf16", "fp16"])
     ap.add_argument("--batch", type=int, default=8,
-                    help="chunk rows of ONE recording per sampler call (rows are never pooled across recordings). Batch "
-                         "widths select different kernels: across --batch values a file agrees to fp32 tolerance (about "
-                         "1e-5 relative), not byte for byte")
+                    help="chunk rows of ONE recording per sampler call (rows are pooled across recordings only with --pool, "
+                         f"which makes every call exactly this wide and takes at most {MAX_BATCH}). Batch widths select different kernels: across --batch "
+                         "values a file agrees to fp32 tolerance (about 1e-5 relative), not byte for byte")
     ap.add_argument("--chunk_frames", type=int, default=CHUNK_FRAMES,
                     help="frames per chunk, a multiple of 64 (default 256, the training crop)")
     ap.add_argument("--overlap_frames", type=int, default=OVERLAP_FRAMES,
@@ -81,6 +101,15 @@ def build_parser():
                          "nothing above 8 kHz (the network never saw that band)")
     ap.add_argument("--synthetic_rate", type=int, default=SAMPLE_RATE, metavar="HZ",
                     help="sample rate of the --synthetic signals (default 16000); any other value needs --resample")
+    ap.add_argument("--pool", action="store_true",
+                    help="fill every sampler call with --batch rows taken across recordings and channels "
+                         "(flowmse_amd.pooled); needs --noise keyed. A file's bytes do not depend on the rest of the folder")
+    ap.add_argument("--channels", choices=("first", "all"), default="first",
+                    help="first: enhance channel 0 of a multi-channel file (default). all: needs --pool; enhance every "
+                         "channel independently and write a file with the input's channel count")
+    ap.add_argument("--synthetic_channels", type=_channels_arg, default=[1],
+                    help="channel counts of the --synthetic signals, a comma list cycled over them (default 1); channel "
+                         "c > 0 is an independent signal at half the level of channel 0")
     return ap
 
 
@@ -99,6 +128,12 @@ def parse_args(argv=None, ap=None):
         plan_chunks(1, args.chunk_frames, args.overlap_frames)
     except ValueError as e:
         ap.error(str(e))
+    if args.channels == "all" and not args.pool:
+        ap.error("--channels all needs --pool")
+    if args.pool and args.noise != "keyed":
+        ap.error("--pool --noise torch: pooling needs --noise keyed (the generator's draw order would depend on the folder)")
+    if args.pool and args.batch > MAX_BATCH:
+        ap.error(f"--pool takes --batch up to {MAX_BATCH}, got {args.batch}")
     if args.output_rate != "16000" and not args.resample:
         ap.error("--output_rate input needs --resample")
     if args.synthetic_rate != SAMPLE_RATE and not args.resample:
@@ -139,6 +174,63 @@ def refuse_other_rates(files):
         raise SystemExit("not 16 kHz (resample first): " + ", ".join(f"{n} ({sr} Hz)" for n, sr in bad))
 
 
+def wav_shape(path):
+    """(samples per channel, channels) of a wav file, which the ``--pool`` plan needs before any file is loaded.  From the
+    header where scipy can map the samples; a sample format it cannot map (24-bit, say) is read in full here, so a
+    pooled run reads such a file twice."""
+    from scipy.io import wavfile
+    try:
+        data = wavfile.read(path, mmap=True)[1]
+    except ValueError:                                             # a sample format scipy cannot map
+        data = wavfile.read(path)[1]
+    return int(data.shape[0]), (1 if data.ndim == 1 else int(data.shape[1]))
+
+
+def synthetic_signals(n, seconds, channels, sr):
+    """``[(name, float32 [C, samples])]``: channel 0 is the noisy signal of ``evaluate._synthetic_pairs``; channel c > 0 an
+    independent tone-plus-noise signal at half that level.  ``channels``: counts cycled over the signals."""
+    import numpy as np
+    out = []
+    for i, (name, _, noisy) in enumerate(_synthetic_pairs(n, seconds=seconds, sr=sr)):
+        rows = [noisy]
+        t = np.arange(noisy.shape[0]) / sr
+        for c in range(1, channels[i % len(channels)]):
+            g = np.random.default_rng([1, i, c])
+            tone = 0.3 * np.sin(2 * np.pi * (230 + 60 * i + 45 * c) * t) * (0.5 + 0.5 * np.sin(2 * np.pi * 3 * t + c))
+            rows.append((0.5 * (tone + 0.05 * g.standard_normal(t.shape))).astype(np.float32))
+        out.append((name, np.stack(rows)))
+    return out
+
+
+def run_pooled(model, args, names, rates, shapes, read, seed):
+    """The ``--pool`` run: ``read(i)`` -> float32 [C, samples] on the host at ``rates[i]`` Hz, ``shapes[i]`` its (samples,
+    channels).  Every file is moved to the device, brought to 16 kHz there (all channels in one launch), enhanced by
+    ``enhance_pooled`` and written as it completes (``--output_rate input``: resampled back and trimmed first).  Returns
+    the real 16 kHz frames enhanced, channels counted."""
+    every = args.channels == "all"
+    items = []
+    for name, sr, (n, C) in zip(names, rates, shapes):
+        up, down = rational(sr, SAMPLE_RATE)
+        items.append((name, C if every else 1, out_len(n, up, down)))
+
+    def load(i):
+        y = read(i)
+        return resample((y if every else y[:1]).cuda(), rates[i], SAMPLE_RATE)
+
+    def write(i, x_hat):
+        sr = SAMPLE_RATE
+        if args.output_rate == "input" and rates[i] != SAMPLE_RATE:
+            sr = rates[i]
+            x_hat = resample(x_hat, SAMPLE_RATE, sr)[:, :shapes[i][0]]
+        x = x_hat.cpu().numpy()
+        _write_wav(os.path.join(args.output, names[i]), x[0] if x.shape[0] == 1 else x.T, sr)
+
+    enhance_pooled(model, load, items, write, batch=args.batch, chunk_frames=args.chunk_frames,
+                   overlap_frames=args.overlap_frames, N=args.N, T_rev=args.reverse_starting_point,
+                   t_eps=args.last_eval_point, odesolver=args.odesolver, noise_seed=seed)
+    return sum(C * (L // 128 + 1) for _, C, L in items)
+
+
 def resampling_rates(files):
     """The sample rate of every file under ``--resample``.  Exits, naming the files and both rates, if one cannot be
     brought to 16 kHz by a ratio the resampler supports (``flowmse_amd.resample.rational``)."""
@@ -176,6 +268,8 @@ def write_settings(out_dir, args, model, epoch, noise_seed, resampled=()):
         f.write(f"precision: {args.precision}\nbatch: {args.batch}\n")
         f.write(f"chunk_frames: {args.chunk_frames}\noverlap_frames: {args.overlap_frames}\n")
         f.write(f"resample: {args.resample}\noutput_rate: {args.output_rate}\n")
+        if args.pool:                                              # without the flag the file is what it always was
+            f.write(f"pool: {args.pool}\nchannels: {args.channels}\n")
         for name, sr in resampled:
             f.write(f"resampled {name}: {sr} Hz\n")
         f.write(f"seed: {args.seed}\nnoise: {args.noise}\nnoise seed: {noise_seed}\n")
@@ -185,12 +279,16 @@ def main(argv=None):
     ap = build_parser()
     args = parse_args(argv, ap)
     if args.synthetic:
-        pairs = _synthetic_pairs(args.synthetic, seconds=args.synthetic_seconds, sr=args.synthetic_rate)
-        names = [p[0] for p in pairs]
-        rates = [args.synthetic_rate] * len(pairs)
+        signals = synthetic_signals(args.synthetic, args.synthetic_seconds, args.synthetic_channels, args.synthetic_rate)
+        names = [p[0] for p in signals]
+        rates = [args.synthetic_rate] * len(signals)
+        shapes = [(p[1].shape[1], p[1].shape[0]) for p in signals]
+
+        def read(i):
+            return torch.from_numpy(signals[i][1])
 
         def load(i):
-            return torch.from_numpy(pairs[i][2])[None]
+            return read(i)[:1]
     else:
         files = list_inputs(args.input)
         if args.resample:
@@ -199,9 +297,13 @@ def main(argv=None):
             refuse_other_rates(files)
             rates = [SAMPLE_RATE] * len(files)
         names = [os.path.basename(f) for f in files]
+        shapes = [wav_shape(f) for f in files] if args.pool else None
 
         def load(i):
             return read_wav(files[i])[0]
+
+        def read(i):
+            return read_wav_channels(files[i])[0]
 
     model, epoch = _load_model(types.SimpleNamespace(synthetic=args.synthetic, ckpt=args.ckpt, test_dir=args.input,
                                                      precision=args.precision), ap)
@@ -213,14 +315,18 @@ def main(argv=None):
     elif args.seed is not None:
         torch.manual_seed(args.seed)
     frames, t0 = 0, time.time()
-    for i, name in enumerate(names):
-        y = load(i).cuda()
-        x_hat, sr_out, n_frames = enhance_recording(
-            model, y, rates[i], args.output_rate, chunk_frames=args.chunk_frames, overlap_frames=args.overlap_frames,
-            batch=args.batch, N=args.N, T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
-            odesolver=args.odesolver, noise_key=utterance_key(name) if keyed else None, noise_seed=seed if keyed else 0)
-        _write_wav(os.path.join(args.output, name), x_hat, sr_out)
-        frames += n_frames
+    if args.pool:
+        frames = run_pooled(model, args, names, rates, shapes, read, seed)
+    else:
+        for i, name in enumerate(names):
+            y = load(i).cuda()
+            x_hat, sr_out, n_frames = enhance_recording(
+                model, y, rates[i], args.output_rate, chunk_frames=args.chunk_frames, overlap_frames=args.overlap_frames,
+                batch=args.batch, N=args.N, T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
+                odesolver=args.odesolver, noise_key=utterance_key(name) if keyed else None,
+                noise_seed=seed if keyed else 0)
+            _write_wav(os.path.join(args.output, name), x_hat, sr_out)
+            frames += n_frames
     write_settings(args.output, args, model, epoch, seed,
                    [(n, sr) for n, sr in zip(names, rates) if sr != SAMPLE_RATE])
     print(f"enhanced {len(names)} recordings ({frames} frames) in {time.time() - t0:.2f} s -> {args.output}"

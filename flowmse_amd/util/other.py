@@ -27,3 +27,16 @@ def read_wav(path):
     if data.ndim > 1:
         data = data[:, 0]
     return torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32))[None], sr
+
+
+def read_wav_channels(path):
+    """float32 tensor [channels, samples] and the sample rate: ``read_wav`` that keeps every channel (for a mono file the
+    two agree bit for bit)."""
+    import numpy as np
+    from scipy.io import wavfile
+    sr, data = wavfile.read(path)
+    if data.dtype.kind == "i":
+        data = data.astype(np.float32) / float(np.iinfo(data.dtype).max + 1)
+    if data.ndim == 1:
+        data = data[:, None]
+    return torch.from_numpy(np.ascontiguousarray(data.T, dtype=np.float32)), sr

@@ -309,6 +309,30 @@ int flowse_stft_compress_chunks(const float* sig, int L, float scale_in, void* o
 int flowse_istft_decompress_chunks(const void* chunks_c64, int K, int Tc, int hop, float factor, float exponent, float* out,
                                    int Lout, float scale_out, void* stream);
 
+/* ---- rows and stacks from many recordings (opt-in: flowmse_amd.pooled, `enhance --pool`) ----------------------
+ * The two chunk calls above for sampler calls whose rows come from SEVERAL recordings (or channels of one file).
+ * flowse_stft_compress_rows: the R input rows [R,1,256,Tw] of ONE sampler call in one launch.  `rows` is a HOST table of R
+ * descriptors; row r holds frames [frame0, frame0 + Tw) of flowse_stft_compress(sig_r, B = 1, L_r, scale_in_r), computed by
+ * the same per-frame code as the calls above (bit-identical to the matching row of flowse_stft_compress_chunks; frames
+ * >= L_r / 128 + 1 are zero).  Two rows may name the same signal.  The table is copied into the kernel's argument block
+ * (FLOWSE_MAX_SPEC_ROWS x 24 bytes): the call does not allocate, upload or synchronise, and the caller may reuse the table
+ * as soon as it returns.  R outside 1..FLOWSE_MAX_SPEC_ROWS, L_r <= 255, Tw < 1, frame0 + Tw > 2^23 -> FLOWSE_ERR_SHAPE;
+ * a null table, output or sig_r, frame0 < 0 -> FLOWSE_ERR_ARG; nothing is launched and the output is left untouched.
+ * flowse_istft_decompress_stacks: flowse_istft_decompress_chunks for S stacks of equal geometry in one launch:
+ * chunks_c64 [S*K,1,256,Tc], rows ordered (stack, chunk) -> out float32 [S][Lout], row s bit-identical to
+ * flowse_istft_decompress_chunks on stack s.  1 <= S <= 65535; the other checks are those of the chunk call. */
+#define FLOWSE_MAX_SPEC_ROWS 64
+typedef struct flowse_spec_row {
+    const float* sig;                          /* device, float32 [L] */
+    int32_t L;                                 /* samples, > 255 */
+    int32_t frame0;                            /* first frame of the row, >= 0 */
+    float scale_in;                            /* the signal is multiplied by this (1 / its file's peak) */
+} flowse_spec_row;
+int flowse_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, void* out_c64, float factor, float exponent,
+                              void* stream);
+int flowse_istft_decompress_stacks(const void* chunks_c64, int S, int K, int Tc, int hop, float factor, float exponent,
+                                   float* out, int Lout, float scale_out, void* stream);
+
 /* ---- sample-rate conversion ahead of the STFT and after the iSTFT (opt-in; the reference reads 16 kHz files only) ----
  * Rational-ratio polyphase FIR resampling, zero phase, defined as what scipy.signal.resample_poly(x, up, down) computes
  * with its defaults (window ("kaiser", 5.0), padtype "constant"):
