@@ -51,9 +51,10 @@ def last_route():
     return L.flowse_op_last_conv_route().decode()
 
 
-def conv2d_16(x1, w, dt, bias=None, x2=None, bias2=None, res=None, scale=1.0, out_f32=False, gn=None):
+def conv2d_16(x1, w, dt, bias=None, x2=None, bias2=None, res=None, scale=1.0, out_f32=False, gn=None, silu=True):
     """The 16-bit storage op entry with per-sample bias and optional fp32 output (flowse_op_conv2d_16_ex; dt 1 = bf16,
-    2 = half): fp32 NCHW cpu tensors in, rounded to dt inside; fp32 NCHW cpu out.  gn: (mean, scale, beta) or None."""
+    2 = half): fp32 NCHW cpu tensors in, rounded to dt inside; fp32 NCHW cpu out.  gn: (mean [B, C], scale [B, C],
+    beta [C]) or None; silu: SiLU behind the fused GroupNorm."""
     Cout, Cin, k, _ = w.shape
     taps = k * k
     a1 = nhwc(x1)
@@ -67,12 +68,41 @@ def conv2d_16(x1, w, dt, bias=None, x2=None, bias2=None, res=None, scale=1.0, ou
     mean, scl, beta = (t.contiguous().cuda() for t in gn) if gn is not None else (None, None, None)
     out = torch.empty(B, H, W, Cout, device="cuda")
     M = B * H * W
-    nbytes = 2 * (M * Cin + 2 * Cout * taps * Cin + 2 * M * Cout) + 4 * 64 * M * Cout + 4096
+    ksmax = max(1, (Cin // 32 * taps + 1) // 4)            # K slices: at most half the two-step stages (conv16_ksplit)
+    nbytes = 2 * (M * Cin + 2 * Cout * taps * Cin + 2 * M * Cout) + 4 * ksmax * M * Cout + 4096
     scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     _lib.check(L.flowse_op_conv2d_16_ex(_lib.ptr(a1), C1, _lib.ptr(a2), C2, _lib.ptr(wp), _lib.ptr(bb), _lib.ptr(b2),
                                         b2.shape[1] if b2 is not None else 0, _lib.ptr(rr), _lib.ptr(mean), _lib.ptr(scl),
-                                        _lib.ptr(beta), 1, _lib.ptr(out), int(out_f32), B, H, W, Cout, taps, float(scale), dt,
+                                        _lib.ptr(beta), int(silu), _lib.ptr(out), int(out_f32), B, H, W, Cout, taps, float(scale), dt,
                                         _lib.ptr(scratch), scratch.numel(), stream()))
+    torch.cuda.synchronize()
+    return nchw(out)
+
+
+def resblock_tail_16(h, w1, dt, b1, x1, w2, b2, x2=None, gn=None, silu=True, scale=1.0):
+    """Tail of a residual block in 16-bit storage as one launch (flowse_op_resblock_tail_16; dt 1 = bf16, 2 = half):
+    (conv3x3(act(GN(h)); w1) + b1 + conv1x1(cat[x1, x2]; w2) + b2) * scale.  fp32 NCHW cpu tensors in, rounded to dt inside;
+    fp32 NCHW cpu out.  w1 [Cout, C, 3, 3], w2 [Cout, X1 + X2, 1, 1]; gn: (mean [B, C], scale [B, C], beta [C]) or None."""
+    Cout, Cc = w1.shape[:2]
+    hd, a1 = nhwc(h), nhwc(x1)
+    a2 = nhwc(x2) if x2 is not None else None
+    B, H, W, X1 = a1.shape
+    X2 = a2.shape[3] if a2 is not None else 0
+    w1p = w1.permute(0, 2, 3, 1).reshape(Cout, 9, Cc).contiguous().cuda()
+    w2p = w2.reshape(Cout, 1, X1 + X2).contiguous().cuda()
+    b1d = b1.contiguous().cuda() if b1 is not None else None
+    b2d = b2.contiguous().cuda() if b2 is not None else None
+    mean, scl, beta = (t.contiguous().cuda() for t in gn) if gn is not None else (None, None, None)
+    out = torch.empty(B, H, W, Cout, device="cuda")
+    M = B * H * W
+    up = lambda b: (b + 255) & ~255                       # the entry's own `need`
+    nw1, nw2 = (Cout * 9 * Cc + 3) & ~3, (Cout * (X1 + X2) + 3) & ~3
+    need = up(2 * M * Cc) + up(2 * M * X1) + up(2 * M * X2) + 2 * up(2 * nw1) + 2 * up(2 * nw2) + up(2 * M * Cout)
+    scratch = torch.empty(need, dtype=torch.uint8, device="cuda")
+    _lib.check(L.flowse_op_resblock_tail_16(_lib.ptr(hd), Cc, _lib.ptr(mean), _lib.ptr(scl), _lib.ptr(beta), int(silu),
+                                            _lib.ptr(w1p), _lib.ptr(b1d), _lib.ptr(a1), X1, _lib.ptr(a2), X2, _lib.ptr(w2p),
+                                            _lib.ptr(b2d), _lib.ptr(out), B, H, W, Cout, float(scale), dt, _lib.ptr(scratch),
+                                            scratch.numel(), stream()))
     torch.cuda.synchronize()
     return nchw(out)
 
