@@ -40,11 +40,49 @@ struct GnFuse {
     bool done = false;
 };
 
+// One conv of the plan (Builder::conv).  conv_req() fills what every conv has; a call site names what else differs from
+// the defaults.
+struct ConvReq {
+    std::string label;
+    const Tn* a = nullptr;              // input
+    const Tn* b2 = nullptr;             // second part of a concat input
+    int64_t w = -1, bias = -1;          // packed offsets of weight / bias
+    int dense_row0 = -1;                // offset of the block's Dense_0 bias within a sample's row of the table
+    int Cout = 0, taps = 0;
+    const Tn* res = nullptr;            // residual: out = (conv + res) * scale
+    float scale = 1.f;
+    bool out_is_res = false;            // in place on `res`
+    bool cin4 = false;                  // the 4-channel input kernels
+    const GnBuf* gin = nullptr;         // GroupNorm (+ SiLU) of the input on load
+    bool gin_silu = false;
+    int64_t wq_off = -1;                // offset of the reduced-precision weight copy
+    int out_dt = -1;                    // < 0: Builder::alloc's choice
+    SkPartial* defer = nullptr;         // leave the split-K slices to another conv's reduction, if this conv runs split
+    const SkPartial* extra = nullptr;   // slices of a deferred conv to sum in this conv's reduction
+    GnFuse* gnf = nullptr;              // finish the consuming GroupNorm in the reduction, if this conv runs split
+    const ScFold* fold = nullptr;       // 1x1 shortcut as extra K steps of this launch
+    bool no_stats = false;              // nobody normalises the output
+    int64_t bias_sc = -1;               // a second per-channel bias from the weight blob
+};
+static ConvReq conv_req(const char* label, const Tn& a, int64_t w, int Cout, int taps) {
+    ConvReq q;
+    q.label = label;
+    q.a = &a;
+    q.w = w;
+    q.Cout = Cout;
+    q.taps = taps;
+    return q;
+}
+
+// label suffix: the image size an op runs at
+static std::string at(int H, int W) { return "@" + std::to_string(H) + "x" + std::to_string(W); }
+
 struct Builder {
     flowse_model* m;
     Plan* plan;
     Arena arena;
     int B;
+    Builder(flowse_model* m_, Plan* plan_, int B_) : m(m_), plan(plan_), B(B_) {}
 
     // dt < 0: the model's activation type for wide tensors, fp32 for the 4-channel ones (input pack, pyramids)
     Tn alloc(int H, int W, int C, int dt = -1) {
@@ -74,47 +112,61 @@ struct Builder {
         plan->dominant.push_back(dominant ? 1 : 0);
     }
 
-    // statistics (fused partials of the producing conv when present, else a gn_stats pass per tensor) +
-    // finalize; returns per-(b,c) mean / scale buffers (caller releases)
-    GnBuf gn(const Tn& a, const Tn* b2, int64_t w_gamma, int64_t w_beta) {
-        flowse_model* M = m;
-        const int C1 = a.C, C2 = b2 ? b2->C : 0, C = C1 + C2, HW = a.H * a.W, Bn = B;
-        const int G = std::min(C / 4, 32);
-        size_t poff[2] = {0, 0};
-        int pnblk[2] = {0, 0};
+    // Where the statistics partials of a GroupNorm's one or two source tensors are: the producing conv's fused ones when
+    // present, else a temporary buffer that a gn_stats launch (emitted here) fills.  The temporaries are allocated here,
+    // source 0 then source 1, and released by release_temp() once the consuming op is emitted.
+    struct StatSrc {
+        size_t off[2] = {0, 0};
+        int nblk[2] = {0, 0};
         bool temp[2] = {false, false};
+    };
+    StatSrc stat_sources(const Tn& a, const Tn* b2) {
+        flowse_model* M = m;
+        const int HW = a.H * a.W, Bn = B;
+        StatSrc st;
         const Tn* src[2] = {&a, b2};
         for (int k = 0; k < 2; ++k) {
             if (!src[k]) continue;
             if (src[k]->st_nblk > 0) {
-                poff[k] = src[k]->st_off;
-                pnblk[k] = src[k]->st_nblk;
+                st.off[k] = src[k]->st_off;
+                st.nblk[k] = src[k]->st_nblk;
                 continue;
             }
             const int Ck = src[k]->C;
             const int nblk = gn_partial_blocks(HW, Ck);
-            poff[k] = arena.alloc((size_t)Bn * nblk * Ck * 2 * sizeof(float));
-            pnblk[k] = nblk;
-            temp[k] = true;
-            const size_t t_off = src[k]->off, p_off = poff[k];
+            st.off[k] = arena.alloc((size_t)Bn * nblk * Ck * 2 * sizeof(float));
+            st.nblk[k] = nblk;
+            st.temp[k] = true;
+            const size_t t_off = src[k]->off, p_off = st.off[k];
             const int sdt = src[k]->dt;
-            op("gn_stats@" + std::to_string(src[k]->H) + "x" + std::to_string(src[k]->W), [=](hipStream_t s) {
+            op("gn_stats" + at(src[k]->H, src[k]->W), [=](hipStream_t s) {
                 return launch_gn_stats(M->A(t_off), Ck, nullptr, 0, Bn, HW, M->A(p_off), nblk, s, sdt);
             }, 3.0 * Bn * HW * Ck, (double)dt_size(sdt) * Bn * HW * Ck);
         }
+        return st;
+    }
+    void release_temp(const StatSrc& st) {
+        for (int k = 0; k < 2; ++k)
+            if (st.temp[k]) arena.release(st.off[k]);
+    }
+    // statistics + finalize; returns per-(b,c) mean / scale buffers (caller releases)
+    GnBuf gn(const Tn& a, const Tn* b2, int64_t w_gamma, int64_t w_beta) {
+        flowse_model* M = m;
+        const int C1 = a.C, C2 = b2 ? b2->C : 0, C = C1 + C2, HW = a.H * a.W, Bn = B;
+        const int G = std::min(C / 4, 32);
+        const StatSrc st = stat_sources(a, b2);
         GnBuf g;
         g.mean = arena.alloc((size_t)Bn * C * sizeof(float));
         g.scale = arena.alloc((size_t)Bn * C * sizeof(float));
         g.beta = w_beta;
-        const size_t gm = g.mean, gs = g.scale, p0 = poff[0], p1 = poff[1];
-        const int n0 = pnblk[0], n1 = pnblk[1];
+        const size_t gm = g.mean, gs = g.scale, p0 = st.off[0], p1 = st.off[1];
+        const int n0 = st.nblk[0], n1 = st.nblk[1];
         const bool has2 = b2 != nullptr;
-        op("gn_finalize@" + std::to_string(a.H) + "x" + std::to_string(a.W), [=](hipStream_t s) {
+        op("gn_finalize" + at(a.H, a.W), [=](hipStream_t s) {
             return launch_gn_finalize(M->A(p0), n0, C1, has2 ? M->A(p1) : nullptr, n1, C2, Bn, HW, G, M->W(w_gamma),
                                       1e-6f, M->A(gm), M->A(gs), s);
         });
-        for (int k = 0; k < 2; ++k)
-            if (temp[k]) arena.release(poff[k]);
+        release_temp(st);
         return g;
     }
     // GroupNorm (+ SiLU) materialised into a new tensor.  Small images: statistics finalize and the apply pass are ONE
@@ -132,38 +184,17 @@ struct Builder {
             return o;
         }
         flowse_model* M = m;
-        size_t poff[2] = {0, 0};
-        int pnblk[2] = {0, 0};
-        bool temp[2] = {false, false};
-        const Tn* src[2] = {&a, b2};
-        for (int k = 0; k < 2; ++k) {
-            if (!src[k]) continue;
-            if (src[k]->st_nblk > 0) {
-                poff[k] = src[k]->st_off;
-                pnblk[k] = src[k]->st_nblk;
-                continue;
-            }
-            const int Ck = src[k]->C;
-            const int nblk = gn_partial_blocks(HW, Ck);
-            poff[k] = arena.alloc((size_t)Bn * nblk * Ck * 2 * sizeof(float));
-            pnblk[k] = nblk;
-            temp[k] = true;
-            const size_t t_off = src[k]->off, p_off = poff[k];
-            op("gn_stats@" + std::to_string(src[k]->H) + "x" + std::to_string(src[k]->W), [=](hipStream_t s) {
-                return launch_gn_stats(M->A(t_off), Ck, nullptr, 0, Bn, HW, M->A(p_off), nblk, s, idt);
-            }, 3.0 * Bn * HW * Ck, (double)dt_size(idt) * Bn * HW * Ck);
-        }
+        const StatSrc st = stat_sources(a, b2);
         Tn o = alloc(a.H, a.W, C, odt);
-        const size_t a_off = a.off, b_off = b2 ? b2->off : 0, o_off = o.off, p0 = poff[0], p1 = poff[1];
-        const int n0 = pnblk[0], n1 = pnblk[1];
+        const size_t a_off = a.off, b_off = b2 ? b2->off : 0, o_off = o.off, p0 = st.off[0], p1 = st.off[1];
+        const int n0 = st.nblk[0], n1 = st.nblk[1];
         const bool has2 = b2 != nullptr;
-        op("gn_norm@" + std::to_string(a.H) + "x" + std::to_string(a.W), [=](hipStream_t s) {
+        op("gn_norm" + at(a.H, a.W), [=](hipStream_t s) {
             return launch_gn_finalize_apply(M->A(a_off), M->A(p0), n0, C1, has2 ? M->A(b_off) : nullptr,
                                             has2 ? M->A(p1) : nullptr, n1, C2, Bn, HW, G, M->W(w_gamma), M->W(w_beta),
                                             1e-6f, silu ? 1 : 0, M->A(o_off), s, idt, odt);
         }, 8.0 * Bn * HW * C, (double)(dt_size(idt) + dt_size(odt)) * Bn * HW * C);
-        for (int k = 0; k < 2; ++k)
-            if (temp[k]) arena.release(poff[k]);
+        release_temp(st);
         return o;
     }
     void gn_release(const GnBuf& g) {
@@ -177,49 +208,62 @@ struct Builder {
         Tn o = alloc(a.H, a.W, C1 + C2, odt);
         const size_t a_off = a.off, b_off = b2 ? b2->off : 0, o_off = o.off;
         const bool has2 = b2 != nullptr;
-        op("gn_apply@" + std::to_string(a.H) + "x" + std::to_string(a.W), [=](hipStream_t s) {
+        op("gn_apply" + at(a.H, a.W), [=](hipStream_t s) {
             GnParams p{M->A(g.mean), M->A(g.scale), M->W(g.beta)};
             return launch_gn_apply(M->A(a_off), C1, has2 ? M->A(b_off) : nullptr, C2, Bn, HW, p, silu ? 1 : 0,
                                    M->A(o_off), s, idt, odt);
         }, 8.0 * Bn * HW * (C1 + C2), (double)(dt_size(idt) + dt_size(odt)) * Bn * HW * (C1 + C2));
         return o;
     }
-    // conv: out (new tensor unless `inplace_res`), res optional
-    Tn conv(const std::string& label, const Tn& a, const Tn* b2, int64_t w, int64_t bias, int dense_row0, int Cout,
-            int taps, const Tn* res, float scale, bool out_is_res = false, bool cin4 = false,
-            const GnBuf* gin = nullptr, bool gin_silu = false, int64_t wq_off = -1, int out_dt = -1,
-            SkPartial* defer = nullptr, const SkPartial* extra = nullptr, GnFuse* gnf = nullptr,
-            const ScFold* fold = nullptr, bool no_stats = false, int64_t bias_sc = -1) {
+    // Split of a conv's reduction dimension over blocks (1: unsplit) -- the one place the plan asks.  (C1, C2): the parts of
+    // a concat input, as the kernel predicates take them.
+    int ksplit(int dt, int H, int W, int C1, int C2, int Cout, int taps) const {
+        if (dt == DT_F32) return conv_ksplit(B, H, W, C1 + C2, Cout, taps);
+        return (conv_supports_head4(B, H, W, C1, C2, Cout, taps) || conv16_uses_halo(B, H, W, C1, C2, Cout, taps))
+                   ? 1 : conv16_ksplit(B, H, W, C1 + C2, Cout, taps);
+    }
+    // true when a conv of this shape runs split over K with the separate (two-pass) reduction launch
+    bool sk_two_pass(int dt, int H, int W, int Cin, int Cout, int taps) const {
+        return ksplit(dt, H, W, Cin, 0, Cout, taps) > 1;
+    }
+    // conv: out (new tensor unless `out_is_res`), res optional
+    Tn conv(const ConvReq& q) {
         flowse_model* M = m;
+        // locals: the launch closures below copy what they use -- they outlive the request and the Builder
+        const std::string& label = q.label;
+        const Tn& a = *q.a;
+        const Tn *b2 = q.b2, *res = q.res;
+        const int64_t w = q.w, bias = q.bias, wq_off = q.wq_off, bias_sc = q.bias_sc;
+        const int dense_row0 = q.dense_row0, Cout = q.Cout, taps = q.taps, out_dt = q.out_dt;
+        const float scale = q.scale;
+        const bool out_is_res = q.out_is_res, cin4 = q.cin4, gin_silu = q.gin_silu, no_stats = q.no_stats;
+        const GnBuf* gin = q.gin;
+        const SkPartial* extra = q.extra;
+        const ScFold* fold = q.fold;
+        SkPartial* defer = q.defer;                      // requests: dropped below for a conv that cannot honour them
+        GnFuse* gnf = q.gnf;
         const int C1 = a.C, C2 = b2 ? b2->C : 0, H = a.H, Wd = a.W, Bn = B;
         if (bias_sc >= 0 && dense_row0 >= 0) {           // both ride on ConvArgs::bias2
             set_error("internal: a second per-channel bias and a Dense row on one conv (%s)", label.c_str());
             failed = true;
         }
-        {   // a deferred reduction leaves no output tensor: decide before anything is allocated
-            const bool in16_ = a.dt != DT_F32;
-            const int ks_ = cin4 ? 1 : in16_ ? ((conv_supports_head4(Bn, H, Wd, C1, C2, Cout, taps) || conv16_uses_halo(Bn, H, Wd, C1, C2, Cout, taps))
-                                                    ? 1 : conv16_ksplit(Bn, H, Wd, C1 + C2, Cout, taps))
-                                             : conv_ksplit(Bn, H, Wd, C1 + C2, Cout, taps);
-            if (defer && !(ks_ > 1 && !res && dense_row0 < 0)) defer = nullptr;
-            if ((extra || gnf) && !(ks_ > 1)) {
-                if (extra && extra->valid) {
-                    set_error("internal: merged reduction requested for an unsplit conv (%s)", label.c_str());
-                    failed = true;
-                }
-                gnf = nullptr;
+        const int ks = cin4 ? 1 : ksplit(a.dt, H, Wd, C1, C2, Cout, taps);
+        // a deferred reduction leaves no output tensor: decide before anything is allocated
+        if (defer && !(ks > 1 && !res && dense_row0 < 0)) defer = nullptr;
+        if ((extra || gnf) && !(ks > 1)) {
+            if (extra && extra->valid) {
+                set_error("internal: merged reduction requested for an unsplit conv (%s)", label.c_str());
+                failed = true;
             }
-            if (gnf && (res || !conv_reduce_gn_ok(Bn, H * Wd, Cout))) gnf = nullptr;
+            gnf = nullptr;
         }
+        if (gnf && (res || !conv_reduce_gn_ok(Bn, H * Wd, Cout))) gnf = nullptr;
         Tn o;
         if (!defer) o = out_is_res ? *res : alloc(a.H, a.W, Cout, out_dt);
         const size_t a_off = a.off, b_off = b2 ? b2->off : 0, o_off = o.off, r_off = res ? res->off : 0;
         const bool has2 = b2 != nullptr, hasres = res != nullptr;
         const int idt = a.dt, odt = o.dt;
         const bool in16 = idt != DT_F32;                 // 16-bit storage: the 16-bit matrix-core kernels take it
-        const int ks = cin4 ? 1 : in16 ? (conv_supports_head4(Bn, H, Wd, C1, C2, Cout, taps) || conv16_uses_halo(Bn, H, Wd, C1, C2, Cout, taps)
-                                              ? 1 : conv16_ksplit(Bn, H, Wd, C1 + C2, Cout, taps))
-                                       : conv_ksplit(Bn, H, Wd, C1 + C2, Cout, taps);
         int st_nblk = (cin4 || out_is_res || Cout < 16) ? 0
                       : in16 ? (conv16_uses_halo(Bn, H, Wd, C1, C2, Cout, taps) ? H * Wd / 128
                                                                                  : conv16_stats_blocks(Bn, H, Wd, C1 + C2, Cout, taps))
@@ -277,7 +321,7 @@ struct Builder {
             set_error("internal: shortcut fold requested for a conv that cannot take it (%s)", label.c_str());
             failed = true;
         }
-        const std::string full_label = label + "@" + std::to_string(H) + "x" + std::to_string(Wd) + ":" +
+        const std::string full_label = label + at(H, Wd) + ":" +
                                        std::to_string(C1 + C2) + (has_fold ? "+" + std::to_string(FC1 + FC2) : std::string()) +
                                        ">" + std::to_string(Cout);
         auto make_args = [=]() {
@@ -366,14 +410,14 @@ struct Builder {
                 g.beta = wb;
             }
             const size_t gm = g.mean, gs = g.scale;
-            op("splitk_reduce_gn@" + std::to_string(H) + "x" + std::to_string(Wd), [=](hipStream_t s) {
+            op("splitk_reduce_gn" + at(H, Wd), [=](hipStream_t s) {
                 return launch_splitk_reduce_gn(make_args(), M->W(wg), M->W(wb), 1e-6f, gsilu ? 1 : 0, gapply ? 1 : 0,
                                                gapply ? nullptr : M->A(gm), gapply ? nullptr : M->A(gs), s);
             }, 8.0 * Bn * H * Wd * Cout, part_bytes + out_bytes);
             gnf->g = g;
             gnf->done = true;
         } else if (ks > 1)
-            op("splitk_reduce@" + std::to_string(H) + "x" + std::to_string(Wd), [=](hipStream_t s) { return launch_splitk_reduce(make_args(), s); }, 0.0,
+            op("splitk_reduce" + at(H, Wd), [=](hipStream_t s) { return launch_splitk_reduce(make_args(), s); }, 0.0,
                part_bytes * (has_extra ? 1.0 + (double)xp.ks / ks : 1.0) + out_bytes);
         if (ks > 1) arena.release(part_off);
         return o;
@@ -392,7 +436,7 @@ struct Builder {
         const bool hasg = g != nullptr, hasadd = add != nullptr, hasraw = raw_out != nullptr;
         GnBuf gb = hasg ? *g : GnBuf();
         const double outs = hasraw ? 2.0 : 1.0;
-        op(std::string(up ? "fir_up@" : "fir_down@") + std::to_string(H) + "x" + std::to_string(Wd), [=](hipStream_t s) {
+        op((up ? "fir_up" : "fir_down") + at(H, Wd), [=](hipStream_t s) {
             GnParams p{nullptr, nullptr, nullptr};
             if (hasg) p = GnParams{M->A(gb.mean), M->A(gb.scale), M->W(gb.beta)};
             if (up)
@@ -412,7 +456,7 @@ struct Builder {
         const size_t part = sp.part_off, o_off = o.off;
         const int ks = sp.ks, Bn = B, odt = o.dt;
         const int64_t bias = sp.bias;
-        op("splitk_reduce@" + std::to_string(H) + "x" + std::to_string(Wd), [=](hipStream_t s) {
+        op("splitk_reduce" + at(H, Wd), [=](hipStream_t s) {
             ConvArgs c;
             c.B = Bn; c.H = H; c.W = Wd; c.Cout = Cout; c.C1 = Cout; c.taps = 1;
             c.scale = 1.f;
@@ -468,45 +512,68 @@ struct Builder {
         // stays (small-image kernels, shortcuts merged into split-K reductions: not measured in the other order).
         const bool sc_low = mod.up && mod.shortcut && !merge_sc && !fold_sc && m->wt->act_dt == DT_F32 && x1.dt == DT_F32 &&
                             (int64_t)B * x1.H * x1.W > 2048 && !getenv("FLOWSE_NO_SC_LOW");
+        // What every request for the shortcut Conv_2 / for Conv_0 has in common; the call sites name the rest
+        auto shortcut = [&](const Tn& s) {
+            ConvReq r = conv_req("conv2_1x1", s, mod.w_c2, mod.out_ch, 1);
+            r.bias = mod.w_c2_b;
+            r.no_stats = true;                           // a residual only: nobody normalises it
+            return r;
+        };
+        auto conv0 = [&](const char* label, const Tn& s) {
+            ConvReq r = conv_req(label, s, mod.w_c0, mod.out_ch, 9);
+            r.dense_row0 = mod.dense_row0;               // Conv_0.bias rides in the Dense_0 table
+            r.gnf = &gf;
+            return r;
+        };
         Tn xr;
         if (!mod.up && !mod.down) {
             if (mod.shortcut && !fold_sc) {
-                xs = conv("conv2_1x1", x1, x2, mod.w_c2, mod.w_c2_b, -1, mod.out_ch, 1, nullptr, 1.f, false, false, nullptr,
-                          false, -1, -1, merge_sc ? &sp : nullptr, nullptr, nullptr, nullptr, true);
+                ConvReq r = shortcut(x1);
+                r.b2 = x2;
+                if (merge_sc) r.defer = &sp;
+                xs = conv(r);
             }
             if (fusable(x1, x2 ? x2->C : 0)) {
                 // Conv_0(act(GroupNorm_0(x))) in one kernel: the normalised tensor never reaches HBM
                 GnBuf g0 = gn(x1, x2, mod.w_gn0_g, mod.w_gn0_b);
-                h1 = conv("conv0_3x3_gn", x1, x2, mod.w_c0, -1, mod.dense_row0, mod.out_ch, 9, nullptr, 1.f, false,
-                          false, &g0, true, mod.wq_c0, -1, nullptr, nullptr, &gf);
+                ConvReq r = conv0("conv0_3x3_gn", x1);
+                r.b2 = x2;
+                r.gin = &g0;
+                r.gin_silu = true;
+                r.wq_off = mod.wq_c0;
+                h1 = conv(r);
                 gn_release(g0);
             } else {
                 Tn h0 = gn_norm(x1, x2, mod.w_gn0_g, mod.w_gn0_b, true);
-                h1 = conv("conv0_3x3", h0, nullptr, mod.w_c0, -1, mod.dense_row0, mod.out_ch, 9, nullptr, 1.f, false, false,
-                          nullptr, false, -1, -1, nullptr, nullptr, &gf);
+                h1 = conv(conv0("conv0_3x3", h0));
                 release(h0);
             }
         } else if (sc_low) {
-            Tn xl = conv("conv2_1x1", x1, nullptr, mod.w_c2, -1, -1, mod.out_ch, 1, nullptr, 1.f, false, false, nullptr, false, -1,
-                         -1, nullptr, nullptr, nullptr, nullptr, true);
+            ConvReq r = shortcut(x1);
+            r.bias = -1;                                 // Conv_1's epilogue adds it (bias_sc below)
+            Tn xl = conv(r);
             xs = fir(xl, true, nullptr, false, nullptr);
             release(xl);
             GnBuf g0 = gn(x1, x2, mod.w_gn0_g, mod.w_gn0_b);
             Tn hr = fir(x1, true, &g0, true, nullptr);
             gn_release(g0);
-            h1 = conv("conv0_3x3", hr, nullptr, mod.w_c0, -1, mod.dense_row0, mod.out_ch, 9, nullptr, 1.f, false, false,
-                      nullptr, false, mod.wq_c0, -1, nullptr, nullptr, &gf);
+            ConvReq r0 = conv0("conv0_3x3", hr);
+            r0.wq_off = mod.wq_c0;
+            h1 = conv(r0);
             release(hr);
         } else {
             GnBuf g0 = gn(x1, x2, mod.w_gn0_g, mod.w_gn0_b);
             Tn hr = fir(x1, mod.up, &g0, true, nullptr, false, &xr);      // act(GN(x)) and x resampled in one pass
             gn_release(g0);
             // the shortcut Conv_2(x) (layerspp.py:268-270)
-            if (!fold_sc)
-                xs = conv("conv2_1x1", xr, nullptr, mod.w_c2, mod.w_c2_b, -1, mod.out_ch, 1, nullptr, 1.f, false, false, nullptr,
-                          false, -1, -1, merge_sc ? &sp : nullptr, nullptr, nullptr, nullptr, true);
-            h1 = conv("conv0_3x3", hr, nullptr, mod.w_c0, -1, mod.dense_row0, mod.out_ch, 9, nullptr, 1.f, false, false,
-                      nullptr, false, mod.wq_c0, -1, nullptr, nullptr, &gf);
+            if (!fold_sc) {
+                ConvReq r = shortcut(xr);
+                if (merge_sc) r.defer = &sp;
+                xs = conv(r);
+            }
+            ConvReq r0 = conv0("conv0_3x3", hr);
+            r0.wq_off = mod.wq_c0;
+            h1 = conv(r0);
             release(hr);
             if (!fold_sc) release(xr);
         }
@@ -537,40 +604,45 @@ struct Builder {
             // The fold was planned from PREDICTED shapes / types and the shortcut launch skipped; the Conv_1 that exists does not
             // take it (the two predicates agree today: this is the safety net for a policy that drifts).  The shortcut runs
             // now, as its own launch, and rides as Conv_1's residual: a little slower, never an unusable model.
-            xs = conv("conv2_1x1", *fo.s1, fo.s2, mod.w_c2, mod.w_c2_b, -1, mod.out_ch, 1, nullptr, 1.f, false, false, nullptr,
-                      false, -1, -1, nullptr, nullptr, nullptr, nullptr, true);
+            ConvReq r = shortcut(*fo.s1);
+            r.b2 = fo.s2;
+            xs = conv(r);
             if (mod.up || mod.down) release(xr);
             resid = &xs;
             fold = nullptr;
         }
+        auto conv1 = [&](const char* label, const Tn& s) {   // what every request for Conv_1 has in common
+            ConvReq r = conv_req(label, s, mod.w_c1, mod.out_ch, 9);
+            r.bias = mod.w_c1_b;
+            r.res = resid;
+            r.scale = rs2;
+            r.extra = extra;
+            r.bias_sc = bias_sc;
+            return r;
+        };
         if (gf.done && gf.apply) {                       // h1 already is act(GroupNorm_1(Conv_0(.)))
-            out = conv("conv1_3x3", h1, nullptr, mod.w_c1, mod.w_c1_b, -1, mod.out_ch, 9, resid, rs2, false, false, nullptr,
-                       false, -1, -1, nullptr, extra, nullptr, nullptr, false, bias_sc);
+            out = conv(conv1("conv1_3x3", h1));
             release(h1);
         } else if (fusable(h1, 0)) {
             GnBuf g1 = gf.done ? gf.g : gn(h1, nullptr, mod.w_gn1_g, mod.w_gn1_b);
-            out = conv(fold ? "conv1_3x3_gn_sc" : "conv1_3x3_gn", h1, nullptr, mod.w_c1, mod.w_c1_b, -1, mod.out_ch, 9, resid, rs2,
-                       false, false, &g1, true, mod.wq_c1, -1, nullptr, extra, nullptr, fold, false, bias_sc);
+            ConvReq r = conv1(fold ? "conv1_3x3_gn_sc" : "conv1_3x3_gn", h1);
+            r.gin = &g1;
+            r.gin_silu = true;
+            r.wq_off = mod.wq_c1;
+            r.fold = fold;
+            out = conv(r);
             gn_release(g1);
             release(h1);
             if (fold && (mod.up || mod.down)) release(xr);
         } else {
             Tn h2 = gn_norm(h1, nullptr, mod.w_gn1_g, mod.w_gn1_b, true);
             release(h1);
-            out = conv("conv1_3x3", h2, nullptr, mod.w_c1, mod.w_c1_b, -1, mod.out_ch, 9, resid, rs2, false, false, nullptr,
-                       false, -1, -1, nullptr, extra, nullptr, nullptr, false, bias_sc);
+            out = conv(conv1("conv1_3x3", h2));
             release(h2);
         }
         if (sp.valid) arena.release(sp.part_off);
         release(xs);
         return out;
-    }
-    // true when a conv of this shape runs split over K with the separate (two-pass) reduction launch
-    bool sk_two_pass(int dt, int H, int W, int Cin, int Cout, int taps) const {
-        const int ks = dt != DT_F32 ? ((conv_supports_head4(B, H, W, Cin, 0, Cout, taps) || conv16_uses_halo(B, H, W, Cin, 0, Cout, taps))
-                                           ? 1 : conv16_ksplit(B, H, W, Cin, Cout, taps))
-                                    : conv_ksplit(B, H, W, Cin, Cout, taps);
-        return ks > 1;
     }
 
     // AttnBlockpp.forward, layerspp.py:75-91
@@ -583,20 +655,36 @@ struct Builder {
         // (fp32 softmax state / accumulation); fp32 mode: everything fp32
         const int adt = x.dt;
         Tn hn = gn_norm(x, nullptr, mod.w_gn0_g, mod.w_gn0_b, false, adt);
-        Tn qkv = conv("attn_qkv", hn, nullptr, mod.w_qkv, mod.w_qkv_b, -1, 3 * C, 1, nullptr, 1.f, false, false, nullptr,
-                      false, -1, adt);
+        ConvReq rq = conv_req("attn_qkv", hn, mod.w_qkv, 3 * C, 1);
+        rq.bias = mod.w_qkv_b;
+        rq.out_dt = adt;
+        Tn qkv = conv(rq);
         release(hn);
         Tn o = alloc(x.H, x.W, C, adt);
         const size_t q_off = qkv.off, o_off = o.off;
-        op("attention@" + std::to_string(x.H) + "x" + std::to_string(x.W), [=](hipStream_t s) { return launch_attention(M->A(q_off), Bn, L, C, M->A(o_off), s, adt); },
+        op("attention" + at(x.H, x.W), [=](hipStream_t s) { return launch_attention(M->A(q_off), Bn, L, C, M->A(o_off), s, adt); },
            4.0 * Bn * (double)L * L * C, 4.0 * dt_size(adt) * Bn * L * C);
         release(qkv);
-        Tn out = conv("attn_out", o, nullptr, mod.w_o, mod.w_o_b, -1, C, 1, &x, rs2, false, false, nullptr, false, -1,
-                      x.dt);
+        ConvReq ro = conv_req("attn_out", o, mod.w_o, C, 1);
+        ro.bias = mod.w_o_b;
+        ro.res = &x;
+        ro.scale = rs2;
+        ro.out_dt = x.dt;
+        Tn out = conv(ro);
         release(o);
         return out;
     }
 };
+
+// Combine: conv1x1(x) + y in place on y (layerspp.py:55-59)
+static ConvReq combine_req(const Module& cb, const Tn& x, const Tn& y) {
+    ConvReq r = conv_req("combine_1x1", x, cb.w_a, cb.out_ch, 1);
+    r.bias = cb.w_a_b;
+    r.res = &y;
+    r.out_is_res = true;
+    r.cin4 = true;
+    return r;
+}
 
 // NCSNpp.forward, ncsnpp.py:247-404
 int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
@@ -611,10 +699,7 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
         return ERR_SHAPE;
     }
     plan->B = B; plan->F = F; plan->T = T;
-    Builder bd;
-    bd.m = m;
-    bd.plan = plan;
-    bd.B = B;
+    Builder bd(m, plan, B);
     flowse_model* M = m;
     const int nf = c.nf, td = m->wt->temb_dim;
     size_t mi = 0;
@@ -651,7 +736,12 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
     }
     const Module& cin = next();
     std::vector<Tn> hs;
-    hs.push_back(bd.conv("conv_in", in4, nullptr, cin.w_a, cin.w_a_b, -1, nf, 9, nullptr, 1.f, false, true));
+    {
+        ConvReq r = conv_req("conv_in", in4, cin.w_a, nf, 9);
+        r.bias = cin.w_a_b;
+        r.cin4 = true;
+        hs.push_back(bd.conv(r));
+    }
     Tn ipyr = in4;
     // ---- down path
     for (int lv = 0; lv < L; ++lv) {
@@ -670,7 +760,7 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
             bd.release(ipyr);
             ipyr = ip2;
             const Module& cb = next();
-            h = bd.conv("combine_1x1", ipyr, nullptr, cb.w_a, cb.w_a_b, -1, cb.out_ch, 1, &h, 1.f, true, true);
+            h = bd.conv(combine_req(cb, ipyr, h));
             hs.push_back(h);           // (updated in place; its statistics are the Combine kernel's, or dropped)
         }
     }
@@ -709,12 +799,18 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
         if (pfuse) g = bd.gn(h, nullptr, gnm.w_a, gnm.w_a_b);
         Tn ph = pfuse ? h : bd.gn_norm(h, nullptr, gnm.w_a, gnm.w_a_b, true, DT_F32);
         const GnBuf* pg = pfuse ? &g : nullptr;
+        ConvReq rp = conv_req("pyramid_conv", ph, pcv.w_a, 4, 9);
+        rp.bias = pcv.w_a_b;
+        rp.gin = pg;
+        rp.gin_silu = true;
         if (!pyr.valid()) {
-            pyr = bd.conv("pyramid_conv", ph, nullptr, pcv.w_a, pcv.w_a_b, -1, 4, 9, nullptr, 1.f, false, false, pg, true);
+            pyr = bd.conv(rp);
         } else {
             Tn up = bd.fir(pyr, true, nullptr, false, nullptr);
             bd.release(pyr);
-            pyr = bd.conv("pyramid_conv", ph, nullptr, pcv.w_a, pcv.w_a_b, -1, 4, 9, &up, 1.f, true, false, pg, true);
+            rp.res = &up;                                // accumulated in place on the upsampled pyramid
+            rp.out_is_res = true;
+            pyr = bd.conv(rp);
         }
         if (pfuse) bd.gn_release(g);
         if (!pfuse) bd.release(ph);
@@ -754,10 +850,7 @@ int build_block_plan(flowse_model* m, Plan* plan, int B, int H, int W, int C1) {
         return ERR_SHAPE;
     }
     plan->B = B; plan->F = H; plan->T = W;
-    Builder bd;
-    bd.m = m;
-    bd.plan = plan;
-    bd.B = B;
+    Builder bd(m, plan, B);
     flowse_model* M = m;
     const int td = m->wt->temb_dim;
     Tn x1 = bd.alloc(H, W, C1), x2;
@@ -784,7 +877,7 @@ int build_block_plan(flowse_model* m, Plan* plan, int B, int H, int W, int C1) {
     } else if (mod.kind == M_ATTN) {
         out = bd.attn(mod, x1);
     } else {                                               // Combine: conv1x1(x) + y (layerspp.py:55-59)
-        bd.conv("combine_1x1", x1, nullptr, mod.w_a, mod.w_a_b, -1, mod.out_ch, 1, &x2, 1.f, true, true);
+        bd.conv(combine_req(mod, x1, x2));
         out = x2;
     }
     {
