@@ -115,6 +115,34 @@ struct Plan {
     hipGraphExec_t exec = nullptr;
 };
 
+// One device allocation with its capacity in elements; p is null exactly when n is 0.  Grow-only, never copied.  The
+// destructor does not free: free_device_state (model_api.hip) releases every buffer with the owning device current.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    operator T*() const { return p; }
+    size_t bytes() const { return n * sizeof(T); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    // Room for `need` elements; growing discards the contents.  sync_first: the device may still be using the old buffer.
+    // A failed allocation leaves the buffer empty.
+    int reserve(size_t need, bool sync_first) {
+        if (need <= n) return OK;
+        if (sync_first) FLOWSE_HIP(hipDeviceSynchronize());
+        release();
+        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&p), need * sizeof(T)));
+        n = need;
+        return OK;
+    }
+};
+
 struct ProfAcc {
     int64_t launches = 0;
     double ms = 0.0, flops = 0.0, bytes = 0.0, issued = 0.0;
@@ -133,30 +161,23 @@ struct WeightSet {
     int64_t w_dense = -1, w_dense_b = -1;  // stacked Dense_0 (+ folded Conv_0.bias)
     int64_t w_out = -1, w_out_b = -1;
     // device state
-    float* d_w = nullptr;                  // native weight blob
-    int64_t d_w_numel = 0;
+    DevBuf<float> d_w;                     // native weight blob
     int precision = 0;                     // 0 fp32 (exact), 1 bf16x3 split (fp32-class), 2 bf16, 3 fp16 operands
-    uint16_t* d_wq = nullptr;              // bf16 planes of the 3x3 ResBlock convs (precision != 0)
-    int64_t d_wq_numel = 0;
+    DevBuf<uint16_t> d_wq;                 // bf16 planes of the 3x3 ResBlock convs (precision != 0)
     // 16-bit STORAGE modes (precision 2 / 3 on networks whose wide channel counts are multiples of 32): activations
     // between kernels are bf16 / half; d_w16 is an elementwise 16-bit copy of the packed weight blob d_w (same offsets)
     int act_dt = DT_F32;
-    uint16_t* d_w16 = nullptr;
-    int64_t d_w16_numel = 0;
+    DevBuf<uint16_t> d_w16;
     // 3x3 convs with Cin % 32 == 0 and Cout % 128 == 0 again in MFMA fragment order (launch_pc16_weights) at the SAME offsets
     // as in d_w16: the B operand of conv3x3_pc16_kernel's consumer waves, straight from L2
-    uint16_t* d_wfrag = nullptr;
-    int64_t d_wfrag_numel = 0;
+    DevBuf<uint16_t> d_wfrag;
     std::set<int64_t> frag_offs;           // packed weight offsets that have fragment-order weights
-    float* d_wino = nullptr;               // F(4,3) Winograd weights of the 3x3 convs the Winograd kernel can take
-    int64_t d_wino_numel = 0;
+    DevBuf<float> d_wino;                  // F(4,3) Winograd weights of the 3x3 convs the Winograd kernel can take
     std::map<int64_t, int64_t> wino_of;    // packed weight offset (d_w) -> offset in d_wino
-    float* d_wino2 = nullptr;              // F(4,3) x F(2,3) weights of the same convs (conv3x3_w2d_kernel; FLOWSE_W2D=0: absent)
-    int64_t d_wino2_numel = 0;
+    DevBuf<float> d_wino2;                 // F(4,3) x F(2,3) weights of the same convs (conv3x3_w2d_kernel; FLOWSE_W2D=0: absent)
     std::map<int64_t, int64_t> wino2_of;
-    float* d_wsm16 = nullptr;              // the same in the 16 x 16-tile fragment order (conv_smallm16_kernel), same offsets
-    float* d_wsm = nullptr;                // fragment-order copy of the conv weights with 32-aligned channel counts (conv_smallm_kernel)
-    int64_t d_wsm_numel = 0;
+    DevBuf<float> d_wsm;                   // fragment-order copy of the conv weights with 32-aligned channel counts (conv_smallm_kernel)
+    DevBuf<float> d_wsm16;                 // the same in the 16 x 16-tile fragment order (conv_smallm16_kernel), same size and offsets
     std::set<int64_t> wsm_offs;            // packed weight offsets (d_w) that have a copy at the SAME offset in d_wsm
     int device = -1;                       // HIP device that owns every d_* buffer of the set and of its handles
     bool storage16() const { return act_dt != DT_F32; }
@@ -170,22 +191,18 @@ struct flowse_model {
     flowse_config cfg;
     WeightSet* wt = nullptr;               // never null; shared with the parent when is_view
     bool is_view = false;                  // made by flowse_model_view_create: may not load weights or change the precision
-    char* d_ws = nullptr;                  // activation workspace
-    size_t d_ws_bytes = 0;
-    float* d_ts = nullptr;                 // [N][B] solver times
-    size_t d_ts_floats = 0;
+    DevBuf<char> d_ws;                     // activation workspace
+    DevBuf<float> d_ts;                    // [N][B] solver times
     std::map<std::tuple<int, int, int>, Plan> plans;
-    CallBlock* d_call = nullptr;           // per-call arguments of the boundary kernels, in device memory
+    DevBuf<CallBlock> d_call;              // per-call arguments of the boundary kernels, in device memory
     bool use_graph = false;                // FLOWSE_GRAPH=1: replay each shape's launch list as a hipGraph (slower, measured)
     // Callers on the NULL (legacy default) stream -- PyTorch's default stream IS the NULL stream -- cannot be captured;
     // their work runs on this internal stream instead, fenced against the NULL stream by events on both sides.
     hipStream_t gstream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     int64_t graph_launches = 0;            // hipGraphLaunch calls made by this handle (flowse_model_graph_launches)
-    float* d_rk = nullptr;                 // fixed-step RK scratch: stage input + slope accumulator, 2 x [B,1,F,T] complex64
-    size_t d_rk_floats = 0;
-    char* d_rk45 = nullptr;                // adaptive RK45 state (flowse_rk45_sample): y, y_new, K1..K7, stage input, norms
-    size_t d_rk45_bytes = 0;
+    DevBuf<float> d_rk;                    // fixed-step RK scratch: stage input + slope accumulator, 2 x [B,1,F,T] complex64
+    DevBuf<char> d_rk45;                   // adaptive RK45 state (flowse_rk45_sample): y, y_new, K1..K7, stage input, norms
     // single-module handles (flowse_block_create): one ResnetBlockBigGANpp / AttnBlockpp / Combine behind the same
     // weight packer, plan builder and kernels as the full network -- unit parity against the reference's modules
     int block_kind = -1;                   // -1: full network; else FLOWSE_BLOCK_*
@@ -237,6 +254,5 @@ int get_plan(flowse_model* m, int B, int F, int T, Plan** out);
 int exec_plan(flowse_model* m, Plan* p, hipStream_t s);
 int enter_stream(flowse_model* m, hipStream_t caller, hipStream_t* work);
 int leave_stream(flowse_model* m, hipStream_t caller, hipStream_t work);
-int reserve_times(flowse_model* m, size_t need);      // d_ts holds at least `need` floats (growth synchronises)
 
 }  // namespace flowse

@@ -30,12 +30,25 @@ static int check_device(const flowse_model* m) {
     return OK;
 }
 
-int get_plan(flowse_model* m, int B, int F, int T, Plan** out) {
+static int check_ready(const flowse_model* m) {
     if (!m->wt->d_w) {
         set_error("weights not loaded: call flowse_model_load_weights first");
         return ERR_STATE;
     }
-    if (const int rc = check_device(m)) return rc;
+    return check_device(m);
+}
+
+// Growing the workspace: the stream may still be using the old one, and captured graphs point into it (block handles
+// hold none).
+static int reserve_workspace(flowse_model* m, size_t bytes) {
+    if (bytes <= m->d_ws.n) return OK;
+    FLOWSE_HIP(hipDeviceSynchronize());
+    for (auto& kv : m->plans) drop_graph(&kv.second);
+    return m->d_ws.reserve(bytes, false);
+}
+
+int get_plan(flowse_model* m, int B, int F, int T, Plan** out) {
+    if (const int rc = check_ready(m)) return rc;
     auto key = std::make_tuple(B, F, T);
     auto it = m->plans.find(key);
     if (it == m->plans.end()) {
@@ -44,19 +57,8 @@ int get_plan(flowse_model* m, int B, int F, int T, Plan** out) {
         if (rc != OK) return rc;
         it = m->plans.emplace(key, std::move(p)).first;
     }
-    Plan* p = &it->second;
-    if (p->ws_bytes > m->d_ws_bytes) {
-        // growing the workspace: the stream may still be using the old one, and captured graphs point into it
-        FLOWSE_HIP(hipDeviceSynchronize());
-        for (auto& kv : m->plans) drop_graph(&kv.second);
-        if (m->d_ws) FLOWSE_HIP(hipFree(m->d_ws));
-        m->d_ws = nullptr;
-        m->d_ws_bytes = 0;
-        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_ws), p->ws_bytes));
-        m->d_ws_bytes = p->ws_bytes;
-    }
-    *out = p;
-    return OK;
+    *out = &it->second;
+    return reserve_workspace(m, it->second.ws_bytes);
 }
 
 static int prof_event(flowse_model* m, hipEvent_t* e) {
@@ -181,30 +183,22 @@ int leave_stream(flowse_model* m, hipStream_t caller, hipStream_t work) {
     return OK;
 }
 
-
-int reserve_times(flowse_model* m, size_t need) {
-    if (need > m->d_ts_floats) {
-        FLOWSE_HIP(hipDeviceSynchronize());
-        if (m->d_ts) FLOWSE_HIP(hipFree(m->d_ts));
-        m->d_ts = nullptr;
-        m->d_ts_floats = 0;
-        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_ts), need * sizeof(float)));
-        m->d_ts_floats = need;
-    }
-    return OK;
+// f(buffer) for every device buffer the handle itself holds / of a weight set: the one list of each that the release and
+// the byte count (flowse_model_device_bytes) go through
+template <class M, class Fn>
+static void each_owned_buffer(M* m, Fn f) {
+    f(m->d_ws); f(m->d_ts); f(m->d_call); f(m->d_rk); f(m->d_rk45);
+}
+template <class W, class Fn>
+static void each_weight_buffer(W* w, Fn f) {
+    f(w->d_w); f(w->d_wq); f(w->d_w16); f(w->d_wfrag); f(w->d_wino); f(w->d_wino2); f(w->d_wsm); f(w->d_wsm16);
 }
 
 // The buffers only this handle holds: workspace, plans, time table, RK scratch, CallBlock, stream, events, profiler.
 // Called with the set's device current and idle.
 static void free_owned_state(flowse_model* m) {
     clear_plans(m);
-    if (m->d_ws) (void)hipFree(m->d_ws);
-    if (m->d_ts) (void)hipFree(m->d_ts);
-    if (m->d_call) (void)hipFree(m->d_call);
-    if (m->d_rk) (void)hipFree(m->d_rk);
-    if (m->d_rk45) (void)hipFree(m->d_rk45);
-    m->d_ws = nullptr; m->d_ts = nullptr; m->d_call = nullptr; m->d_rk = nullptr; m->d_rk45 = nullptr;
-    m->d_ws_bytes = m->d_ts_floats = m->d_rk_floats = m->d_rk45_bytes = 0;
+    each_owned_buffer(m, [](auto& b) { b.release(); });
     if (m->gstream) (void)hipStreamDestroy(m->gstream);
     if (m->ev_in) (void)hipEventDestroy(m->ev_in);
     if (m->ev_out) (void)hipEventDestroy(m->ev_out);
@@ -217,13 +211,7 @@ static void free_owned_state(flowse_model* m) {
 
 // Every device buffer of a weight set; the host tables stay (the next upload rewrites them).
 static void free_weight_buffers(WeightSet* w) {
-    void* bufs[] = {w->d_w, w->d_wq, w->d_w16, w->d_wfrag, w->d_wino, w->d_wino2, w->d_wsm, w->d_wsm16};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    w->d_w = w->d_wino = w->d_wino2 = w->d_wsm = w->d_wsm16 = nullptr;
-    w->d_wq = w->d_w16 = w->d_wfrag = nullptr;
-    w->d_w_numel = w->d_wq_numel = w->d_w16_numel = w->d_wfrag_numel = 0;
-    w->d_wino_numel = w->d_wino2_numel = w->d_wsm_numel = 0;
+    each_weight_buffer(w, [](auto& b) { b.release(); });
     w->device = -1;
 }
 
@@ -272,18 +260,9 @@ struct RkGrid {
 
 // time table and RK scratch of one [B,1,F,T] solve on handle m (growth synchronises the device)
 static int reserve_rk(flowse_model* m, const RkGrid& g, int B, int F, int T) {
-    const int rc = reserve_times(m, g.nfe_t.size() * (size_t)B);
-    if (rc != OK) return rc;
+    if (const int rc = m->d_ts.reserve(g.nfe_t.size() * (size_t)B, true)) return rc;
     const size_t state = (size_t)2 * B * F * T;                 // floats of one complex64 [B,1,F,T] tensor
-    if (g.stages > 1 && m->d_rk_floats < 2 * state) {
-        FLOWSE_HIP(hipDeviceSynchronize());
-        if (m->d_rk) FLOWSE_HIP(hipFree(m->d_rk));
-        m->d_rk = nullptr;
-        m->d_rk_floats = 0;
-        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_rk), 2 * state * sizeof(float)));
-        m->d_rk_floats = 2 * state;
-    }
-    return OK;
+    return m->d_rk.reserve(g.stages > 1 ? 2 * state : 0, true);
 }
 
 struct RkRun {
@@ -333,6 +312,142 @@ static bool weights_shared(const flowse_model* m, const char* what) {
     set_error("%s: the weight set is shared by %d handles; destroy the views first", what, m->wt->holders);
     return true;
 }
+
+// ------------------------------------------------------------------------- flowse_model_load_weights, table by table
+// Each step derives one table of the set from the packed fp32 blob that is already in d_w (and from the packer's lists).
+// The weight buffers grow without a synchronisation: the upload synchronises once, before the first of them.
+
+// 16-bit storage modes: the elementwise 16-bit twin of the packed blob (conv weights keep their offsets) and, at the same
+// offsets, the fragment-order copies for the producer / consumer 3x3 kernel and the 16-bit small-image kernel
+static int upload_16bit_copies(WeightSet* w, Packer& pk) {
+    const int64_t n = (int64_t)pk.host.size(), n16 = (n + 3) & ~(int64_t)3;
+    if (const int rc = w->d_w16.reserve(n16, false)) return rc;
+    if (const int rc = launch_convert(w->d_w, DT_F32, w->d_w16, w->act_dt, n & ~(int64_t)3, nullptr)) return rc;
+    w->frag_offs.clear();
+    if (const int rc = w->d_wfrag.reserve(n16, false)) return rc;
+    for (auto& r : pk.wino) {
+        if ((r.Cout % 128) != 0 || (int64_t)r.Cout * 9 * r.Cin * 2 >= (1LL << 31)) continue;
+        if (const int rc = launch_pc16_weights(w->d_w16 + r.off, r.Cout, r.Cin, w->d_wfrag + r.off, nullptr)) return rc;
+        w->frag_offs.insert(r.off);
+    }
+    // ... and for every other conv with 32-aligned channel counts (1x1 shortcuts, attention projections, 3x3 with
+    // Cout % 128 != 0): the 16-bit small-image kernel reads the same layout
+    if (conv16_smallm_ok(1, 4, 4, 32, 0, 32, 1)) {
+        for (auto& r : pk.smallm) {
+            if (w->frag_offs.count(r.off) || (int64_t)r.Cout * r.taps * r.Cin * 2 >= (1LL << 31)) continue;
+            if (const int rc = launch_pc16_weights(w->d_w16 + r.off, r.Cout, r.Cin, w->d_wfrag + r.off, nullptr, r.taps)) return rc;
+            w->frag_offs.insert(r.off);
+        }
+    }
+    pk.wino.clear();                         // no fp32 Winograd kernels run on 16-bit activations
+    return OK;
+}
+
+// F(4,3) Winograd weights, derived on the device
+static int upload_f43_weights(WeightSet* w, const Packer& pk) {
+    w->wino_of.clear();
+    int64_t total = 0;
+    for (auto& r : pk.wino) {
+        w->wino_of[r.off] = total;
+        total += (conv_wino_numel(r.Cout, r.Cin) + 63) & ~(int64_t)63;
+    }
+    if (const int rc = w->d_wino.reserve(total, false)) return rc;
+    for (auto& r : pk.wino)
+        if (const int rc = launch_f43_weights(w->d_w + r.off, r.Cout, r.Cin, w->d_wino + w->wino_of[r.off], nullptr)) return rc;
+    return OK;
+}
+
+// fragment-order copies for the small-M kernels (fp32 activations only), at the same offsets as in d_w
+static int upload_smallm_copies(WeightSet* w, const Packer& pk) {
+    w->wsm_offs.clear();
+    if (w->storage16() || pk.smallm.empty() || !conv_smallm_ok(1, 4, 4, 32, 0, 32, 1)) return OK;
+    if (const int rc = w->d_wsm.reserve(pk.host.size(), false)) return rc;
+    if (const int rc = w->d_wsm16.reserve(pk.host.size(), false)) return rc;
+    for (auto& r : pk.smallm) {
+        if ((int64_t)r.Cout * r.taps * r.Cin * 4 >= (1LL << 31)) continue;
+        if (const int rc = launch_smallm_weights(w->d_w + r.off, r.Cout, r.taps, r.Cin, w->d_wsm + r.off, nullptr)) return rc;
+        if (const int rc = launch_smallm_weights(w->d_w + r.off, r.Cout, r.taps, r.Cin, w->d_wsm16 + r.off, nullptr, true)) return rc;
+        w->wsm_offs.insert(r.off);
+    }
+    return OK;
+}
+
+// F(4,3) x F(2,3) weights of the F(4,3) convs (the two-dimensional kernel takes the large images)
+static int upload_w2d_weights(WeightSet* w, const Packer& pk) {
+    w->wino2_of.clear();
+    if (!conv_w2d_enabled()) return OK;
+    int64_t total = 0;
+    for (auto& r : pk.wino) {
+        if ((int64_t)r.Cout * 24 * r.Cin * 4 >= (1LL << 31)) continue;
+        w->wino2_of[r.off] = total;
+        total += (conv_w2d_numel(r.Cout, r.Cin) + 63) & ~(int64_t)63;
+    }
+    if (const int rc = w->d_wino2.reserve(total, false)) return rc;
+    for (auto& r : pk.wino) {
+        const auto it = w->wino2_of.find(r.off);
+        if (it == w->wino2_of.end()) continue;
+        if (const int rc = launch_w2d_weights(w->d_w + r.off, r.Cout, r.Cin, w->d_wino2 + it->second, nullptr)) return rc;
+    }
+    return OK;
+}
+
+// optional bf16 planes for the 3x3 ResBlock convolutions the halo kernel can take, packed on the host from the caller's blob
+static int upload_bf16_planes(WeightSet* w, const float* blob) {
+    for (auto& mod : w->mods) mod.wq_c0 = mod.wq_c1 = -1;
+    if (w->precision == 0 || w->storage16()) return OK;
+    const int terms = w->precision == 1 ? 3 : 1;
+    std::vector<uint16_t> q;
+    auto plane = [&](int64_t param, int Cout, int Cin) {
+        const int64_t off = (int64_t)q.size();
+        q.resize(q.size() + conv_bf16_numel(Cout, Cin, terms));
+        pack_conv_bf16(blob + w->params[param].offset, Cout, Cin, terms, q.data() + off, w->precision == 3);
+        return off;
+    };
+    for (auto& mod : w->mods) {
+        if (mod.kind != M_RESBLOCK || (mod.out_ch % 128) != 0) continue;
+        if ((mod.in_ch % 32) == 0) mod.wq_c0 = plane(mod.p0 + 2, mod.out_ch, mod.in_ch);
+        mod.wq_c1 = plane(mod.p0 + 8, mod.out_ch, mod.out_ch);
+    }
+    if (const int rc = w->d_wq.reserve(q.size(), false)) return rc;
+    if (!q.empty()) FLOWSE_HIP(hipMemcpy(w->d_wq, q.data(), q.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    return OK;
+}
+
+// ------------------------------------------------------------------------------------- shared by the per-op test entries
+// the fields every conv entry fills
+static ConvArgs conv_args(const float* in1, int C1, const float* in2, int C2, const float* w, const float* bias,
+                          const float* bias2, int bias2_stride, const float* res, float* out, int B, int H, int W, int Cout,
+                          int taps, float scale) {
+    ConvArgs c;
+    c.in1 = in1; c.in2 = in2; c.C1 = C1; c.C2 = C2;
+    c.w = w; c.bias = bias; c.bias2 = bias2; c.bias2_stride = bias2_stride; c.res = res; c.out = out;
+    c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.taps = taps; c.scale = scale;
+    return c;
+}
+
+// Statistics and finalize of GroupNorm over cat[in1, in2], in `scratch` as flowse_op_group_norm_scratch_floats sizes it:
+// partials [B][nblk][C][2], mean [B][C], scale [B][C].  *gn: what the consumer normalises with.
+static int op_gn_prologue(const float* in1, int C1, const float* in2, int C2, const float* gamma, const float* beta, float eps,
+                          int B, int HW, float* scratch, hipStream_t s, GnParams* gn) {
+    const int C = C1 + C2, nblk = gn_partial_blocks(HW, C);
+    float* mean = scratch + (int64_t)B * nblk * C * 2;
+    float* scl = mean + (int64_t)B * C;
+    *gn = GnParams{mean, scl, beta};
+    const int rc = launch_gn_stats(in1, C1, in2, C2, B, HW, scratch, nblk, s);
+    if (rc != OK) return rc;
+    return launch_gn_finalize(scratch, nblk, C, nullptr, 0, 0, B, HW, std::min(C / 4, 32), gamma, eps, mean, scl, s);
+}
+
+// the caller's scratch of a 16-bit entry, handed out in sub-buffers rounded up to 256 bytes
+struct Carver {
+    char* p;
+    static int64_t up(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+    void* take(int64_t bytes) {
+        char* q = p;
+        p += up(bytes);
+        return q;
+    }
+};
 
 }  // namespace flowse
 // =============================================================================================== C ABI
@@ -406,11 +521,7 @@ int flowse_block_forward(flowse_model* m, const float* in1, int C1, const float*
         set_error("flowse_block_forward: bad argument (not a block handle, or a required pointer is null)");
         return ERR_ARG;
     }
-    if (!m->wt->d_w) {
-        set_error("weights not loaded: call flowse_model_load_weights first");
-        return ERR_STATE;
-    }
-    if (const int rc = check_device(m)) return rc;
+    if (const int rc = check_ready(m)) return rc;
     if (!in2 && m->block_kind == FLOWSE_BLOCK_RESNET) C1 = m->wt->mods[0].in_ch;
     auto key = std::make_tuple(B, H, W, C1);
     auto it = m->block_plans.find(key);
@@ -421,14 +532,7 @@ int flowse_block_forward(flowse_model* m, const float* in1, int C1, const float*
         it = m->block_plans.emplace(key, std::move(p)).first;
     }
     Plan* p = &it->second;
-    if (p->ws_bytes > m->d_ws_bytes) {
-        FLOWSE_HIP(hipDeviceSynchronize());
-        if (m->d_ws) FLOWSE_HIP(hipFree(m->d_ws));
-        m->d_ws = nullptr;
-        m->d_ws_bytes = 0;
-        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_ws), p->ws_bytes));
-        m->d_ws_bytes = p->ws_bytes;
-    }
+    if (const int rc = reserve_workspace(m, p->ws_bytes)) return rc;
     m->bcall.in1 = in1;
     m->bcall.in2 = in2;
     m->bcall.temb_act = temb_act;
@@ -469,14 +573,8 @@ int flowse_model_set_precision(flowse_model* m, int mode) {
             if (const int rc = check_device(m)) return rc;      // before any state changes: a failure leaves the handle as is
             FLOWSE_HIP(hipDeviceSynchronize());
             clear_plans(m);
-            FLOWSE_HIP(hipFree(m->wt->d_w));
-            m->wt->d_w = nullptr;
-            m->wt->d_w_numel = 0;
-            if (m->wt->d_w16) {      // the 16-bit twin belongs to the mode that is being left
-                FLOWSE_HIP(hipFree(m->wt->d_w16));
-                m->wt->d_w16 = nullptr;
-                m->wt->d_w16_numel = 0;
-            }
+            m->wt->d_w.release();
+            m->wt->d_w16.release();  // the 16-bit twin belongs to the mode that is being left
         }
         m->wt->precision = mode;
         m->wt->act_dt = DT_F32;      // recomputed by the next flowse_model_load_weights
@@ -497,162 +595,26 @@ int flowse_model_load_weights(flowse_model* m, const float* blob, int64_t numel)
     }
     if (weights_shared(m, "flowse_model_load_weights")) return ERR_STATE;      // before the packer rewrites shared tables
     Packer pk;
-    const int rc = pack_weights(m, blob, pk);
-    if (rc != OK) return rc;
+    if (const int prc = pack_weights(m, blob, pk)) return prc;
     int dev = 0;
     FLOWSE_HIP(hipGetDevice(&dev));
     if (m->wt->device >= 0 && m->wt->device != dev) free_device_state(m);      // the handle moves to the current device
     m->wt->device = dev;
     FLOWSE_HIP(hipDeviceSynchronize());
     clear_plans(m);          // closures captured weight offsets of the previous packing
-    if (!m->d_call) FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_call), sizeof(CallBlock)));
-    if (m->wt->d_w && m->wt->d_w_numel < (int64_t)pk.host.size()) {
-        FLOWSE_HIP(hipFree(m->wt->d_w));
-        m->wt->d_w = nullptr;
-    }
-    if (!m->wt->d_w) {
-        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_w), pk.host.size() * sizeof(float)));
-        m->wt->d_w_numel = (int64_t)pk.host.size();
-    }
-    FLOWSE_HIP(hipMemcpy(m->wt->d_w, pk.host.data(), pk.host.size() * sizeof(float), hipMemcpyHostToDevice));
-    m->wt->act_dt = storage_type_for(m);
-    if (m->storage16()) {                    // elementwise 16-bit twin of the packed blob (conv weights keep their offsets)
-        const int64_t n16 = ((int64_t)pk.host.size() + 3) & ~(int64_t)3;
-        if (m->wt->d_w16 && m->wt->d_w16_numel < n16) {
-            FLOWSE_HIP(hipFree(m->wt->d_w16));
-            m->wt->d_w16 = nullptr;
-        }
-        if (!m->wt->d_w16) {
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_w16), n16 * sizeof(uint16_t)));
-            m->wt->d_w16_numel = n16;
-        }
-        const int crc = launch_convert(m->wt->d_w, DT_F32, m->wt->d_w16, m->wt->act_dt, (int64_t)pk.host.size() & ~(int64_t)3, nullptr);
-        if (crc != OK) return crc;
-        // fragment-order copies for the producer / consumer 3x3 kernel, same offsets as in d_w16
-        m->wt->frag_offs.clear();
-        if (m->wt->d_wfrag && m->wt->d_wfrag_numel < n16) {
-            FLOWSE_HIP(hipFree(m->wt->d_wfrag));
-            m->wt->d_wfrag = nullptr;
-        }
-        if (!m->wt->d_wfrag) {
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wfrag), n16 * sizeof(uint16_t)));
-            m->wt->d_wfrag_numel = n16;
-        }
-        for (auto& r : pk.wino) {
-            if ((r.Cout % 128) != 0 || (int64_t)r.Cout * 9 * r.Cin * 2 >= (1LL << 31)) continue;
-            const int frc = launch_pc16_weights(m->wt->d_w16 + r.off, r.Cout, r.Cin, m->wt->d_wfrag + r.off, nullptr);
-            if (frc != OK) return frc;
-            m->wt->frag_offs.insert(r.off);
-        }
-        // ... and for every other conv with 32-aligned channel counts (1x1 shortcuts, attention projections, 3x3 with
-        // Cout % 128 != 0): the 16-bit small-image kernel reads the same layout
-        if (conv16_smallm_ok(1, 4, 4, 32, 0, 32, 1)) {
-            for (auto& r : pk.smallm) {
-                if (m->wt->frag_offs.count(r.off) || (int64_t)r.Cout * r.taps * r.Cin * 2 >= (1LL << 31)) continue;
-                const int frc = launch_pc16_weights(m->wt->d_w16 + r.off, r.Cout, r.Cin, m->wt->d_wfrag + r.off, nullptr, r.taps);
-                if (frc != OK) return frc;
-                m->wt->frag_offs.insert(r.off);
-            }
-        }
-        pk.wino.clear();                     // no fp32 Winograd kernels run on 16-bit activations
-    }
-    // F(4,3) Winograd weights, derived on the device from the packed fp32 weights just uploaded
-    m->wt->wino_of.clear();
-    int64_t wino_total = 0;
-    for (auto& r : pk.wino) {
-        m->wt->wino_of[r.off] = wino_total;
-        wino_total += (conv_wino_numel(r.Cout, r.Cin) + 63) & ~(int64_t)63;
-    }
-    if (m->wt->d_wino && m->wt->d_wino_numel < wino_total) {
-        FLOWSE_HIP(hipFree(m->wt->d_wino));
-        m->wt->d_wino = nullptr;
-    }
-    if (!m->wt->d_wino && wino_total > 0) {
-        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wino), wino_total * sizeof(float)));
-        m->wt->d_wino_numel = wino_total;
-    }
-    for (auto& r : pk.wino) {
-        float* dst = m->wt->d_wino + m->wt->wino_of[r.off];
-        const int wrc = launch_f43_weights(m->wt->d_w + r.off, r.Cout, r.Cin, dst, nullptr);
-        if (wrc != OK) return wrc;
-    }
-    // fragment-order copies for the small-M kernel (fp32 activations only), at the same offsets as in d_w
-    m->wt->wsm_offs.clear();
-    if (!m->storage16() && !pk.smallm.empty() && conv_smallm_ok(1, 4, 4, 32, 0, 32, 1)) {
-        const int64_t nw = (int64_t)pk.host.size();
-        if (m->wt->d_wsm && m->wt->d_wsm_numel < nw) {
-            FLOWSE_HIP(hipFree(m->wt->d_wsm));
-            FLOWSE_HIP(hipFree(m->wt->d_wsm16));
-            m->wt->d_wsm = m->wt->d_wsm16 = nullptr;
-        }
-        if (!m->wt->d_wsm) {
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wsm), nw * sizeof(float)));
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wsm16), nw * sizeof(float)));
-            m->wt->d_wsm_numel = nw;
-        }
-        for (auto& r : pk.smallm) {
-            if ((int64_t)r.Cout * r.taps * r.Cin * 4 >= (1LL << 31)) continue;
-            int src = launch_smallm_weights(m->wt->d_w + r.off, r.Cout, r.taps, r.Cin, m->wt->d_wsm + r.off, nullptr);
-            if (src == OK) src = launch_smallm_weights(m->wt->d_w + r.off, r.Cout, r.taps, r.Cin, m->wt->d_wsm16 + r.off, nullptr, true);
-            if (src != OK) return src;
-            m->wt->wsm_offs.insert(r.off);
-        }
-    }
-    // F(4,3) x F(2,3) weights of the same convs (the two-dimensional kernel takes the large images)
-    m->wt->wino2_of.clear();
-    if (conv_w2d_enabled()) {
-        int64_t w2_total = 0;
-        for (auto& r : pk.wino) {
-            if ((int64_t)r.Cout * 24 * r.Cin * 4 >= (1LL << 31)) continue;
-            m->wt->wino2_of[r.off] = w2_total;
-            w2_total += (conv_w2d_numel(r.Cout, r.Cin) + 63) & ~(int64_t)63;
-        }
-        if (m->wt->d_wino2 && m->wt->d_wino2_numel < w2_total) {
-            FLOWSE_HIP(hipFree(m->wt->d_wino2));
-            m->wt->d_wino2 = nullptr;
-        }
-        if (!m->wt->d_wino2 && w2_total > 0) {
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wino2), w2_total * sizeof(float)));
-            m->wt->d_wino2_numel = w2_total;
-        }
-        for (auto& r : pk.wino) {
-            const auto it = m->wt->wino2_of.find(r.off);
-            if (it == m->wt->wino2_of.end()) continue;
-            const int wrc = launch_w2d_weights(m->wt->d_w + r.off, r.Cout, r.Cin, m->wt->d_wino2 + it->second, nullptr);
-            if (wrc != OK) return wrc;
-        }
-    }
+    WeightSet* w = m->wt;
+    int rc = m->d_call.reserve(1, false);
+    if (rc == OK) rc = w->d_w.reserve(pk.host.size(), false);
+    if (rc != OK) return rc;
+    FLOWSE_HIP(hipMemcpy(w->d_w, pk.host.data(), pk.host.size() * sizeof(float), hipMemcpyHostToDevice));
+    w->act_dt = storage_type_for(m);
+    if (w->storage16()) rc = upload_16bit_copies(w, pk);
+    if (rc == OK) rc = upload_f43_weights(w, pk);
+    if (rc == OK) rc = upload_smallm_copies(w, pk);
+    if (rc == OK) rc = upload_w2d_weights(w, pk);
+    if (rc != OK) return rc;
     FLOWSE_HIP(hipDeviceSynchronize());
-    // optional bf16 planes for the 3x3 ResBlock convolutions the halo kernel can take
-    for (auto& mod : m->wt->mods) mod.wq_c0 = mod.wq_c1 = -1;
-    if (m->wt->precision != 0 && !m->storage16()) {
-        const int terms = m->wt->precision == 1 ? 3 : 1;
-        std::vector<uint16_t> q;
-        for (auto& mod : m->wt->mods) {
-            if (mod.kind != M_RESBLOCK || (mod.out_ch % 128) != 0) continue;
-            if ((mod.in_ch % 32) == 0) {
-                mod.wq_c0 = (int64_t)q.size();
-                q.resize(q.size() + conv_bf16_numel(mod.out_ch, mod.in_ch, terms));
-                pack_conv_bf16(blob + m->wt->params[mod.p0 + 2].offset, mod.out_ch, mod.in_ch, terms, q.data() + mod.wq_c0,
-                               m->wt->precision == 3);
-            }
-            mod.wq_c1 = (int64_t)q.size();
-            q.resize(q.size() + conv_bf16_numel(mod.out_ch, mod.out_ch, terms));
-            pack_conv_bf16(blob + m->wt->params[mod.p0 + 8].offset, mod.out_ch, mod.out_ch, terms, q.data() + mod.wq_c1,
-                           m->wt->precision == 3);
-        }
-        if (m->wt->d_wq && m->wt->d_wq_numel < (int64_t)q.size()) {
-            FLOWSE_HIP(hipFree(m->wt->d_wq));
-            m->wt->d_wq = nullptr;
-        }
-        if (!m->wt->d_wq && !q.empty()) {
-            FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->wt->d_wq), q.size() * sizeof(uint16_t)));
-            m->wt->d_wq_numel = (int64_t)q.size();
-        }
-        if (!q.empty())
-            FLOWSE_HIP(hipMemcpy(m->wt->d_wq, q.data(), q.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    }
-    return OK;
+    return upload_bf16_planes(w, blob);
 }
 
 int flowse_model_reserve(flowse_model* m, int B, int F, int T, int64_t* workspace_bytes) {
@@ -897,14 +859,15 @@ int flowse_model_view_create(flowse_model* parent, flowse_model** out) {
         return ERR_STATE;
     }
     if (const int rc = check_device(parent)) return rc;
-    CallBlock* call = nullptr;
-    FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&call), sizeof(CallBlock)));
     flowse_model* v = new flowse_model();
+    if (const int rc = v->d_call.reserve(1, false)) {
+        delete v;
+        return rc;
+    }
     v->cfg = parent->cfg;
     v->wt = parent->wt;
     v->is_view = true;
     v->use_graph = parent->use_graph;
-    v->d_call = call;
     ++v->wt->holders;
     *out = v;
     return OK;
@@ -912,14 +875,11 @@ int flowse_model_view_create(flowse_model* parent, flowse_model** out) {
 
 int64_t flowse_model_device_bytes(const flowse_model* m, int what) {
     if (!m || (what != FLOWSE_BYTES_WEIGHTS && what != FLOWSE_BYTES_OWNED)) return 0;
-    if (what == FLOWSE_BYTES_OWNED)
-        return (int64_t)m->d_ws_bytes + (int64_t)m->d_rk45_bytes + 4 * (int64_t)(m->d_ts_floats + m->d_rk_floats) +
-               (m->d_call ? (int64_t)sizeof(CallBlock) : 0);
-    const WeightSet* w = m->wt;
-    auto n = [](const void* p, int64_t numel) { return p ? numel : (int64_t)0; };
-    return 4 * (n(w->d_w, w->d_w_numel) + n(w->d_wino, w->d_wino_numel) + n(w->d_wino2, w->d_wino2_numel) +
-                n(w->d_wsm, w->d_wsm_numel) + n(w->d_wsm16, w->d_wsm_numel)) +
-           2 * (n(w->d_wq, w->d_wq_numel) + n(w->d_w16, w->d_w16_numel) + n(w->d_wfrag, w->d_wfrag_numel));
+    int64_t total = 0;
+    auto add = [&](const auto& b) { total += (int64_t)b.bytes(); };
+    if (what == FLOWSE_BYTES_OWNED) each_owned_buffer(m, add);
+    else each_weight_buffer(m->wt, add);
+    return total;
 }
 
 int flowse_model_weight_holders(const flowse_model* m) { return (m && m->wt->d_w) ? m->wt->holders : 0; }
@@ -1071,10 +1031,7 @@ int flowse_op_conv2d(const float* in1, int C1, const float* in2, int C2, const f
         set_error("flowse_op_conv2d: null argument");
         return ERR_ARG;
     }
-    ConvArgs c;
-    c.in1 = in1; c.in2 = in2; c.C1 = C1; c.C2 = in2 ? C2 : 0;
-    c.w = w; c.bias = bias; c.bias2 = bias2; c.bias2_stride = bias2_stride; c.res = res; c.out = out;
-    c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.taps = taps; c.scale = scale;
+    ConvArgs c = conv_args(in1, C1, in2, in2 ? C2 : 0, w, bias, bias2, bias2_stride, res, out, B, H, W, Cout, taps, scale);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (C1 == 4 && !in2) return launch_conv_cin4(c, s);
     if (splitk_scratch && conv1x1_stream_ok(B, H, W, c.C1, c.C2, Cout, taps)) {   // the model handle's kernel for this shape
@@ -1107,18 +1064,10 @@ int flowse_op_group_norm(const float* in1, int C1, const float* in2, int C2, con
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!in2) C2 = 0;
-    const int C = C1 + C2, HW = H * W;
-    const int G = std::min(C / 4, 32);
-    const int nblk = gn_partial_blocks(HW, C);
-    float* part = scratch;
-    float* mean = scratch + (int64_t)B * nblk * C * 2;
-    float* scl = mean + (int64_t)B * C;
-    int rc = launch_gn_stats(in1, C1, in2, C2, B, HW, part, nblk, s);
+    GnParams p;
+    const int rc = op_gn_prologue(in1, C1, in2, C2, gamma, beta, eps, B, H * W, scratch, s, &p);
     if (rc != OK) return rc;
-    rc = launch_gn_finalize(part, nblk, C, nullptr, 0, 0, B, HW, G, gamma, eps, mean, scl, s);
-    if (rc != OK) return rc;
-    GnParams p{mean, scl, beta};
-    return launch_gn_apply(in1, C1, in2, C2, B, HW, p, silu, out, s);
+    return launch_gn_apply(in1, C1, in2, C2, B, H * W, p, silu, out, s);
 }
 
 int flowse_op_conv3x3_gn(const float* in1, int C1, const float* in2, int C2, const float* gamma, const float* beta,
@@ -1136,23 +1085,10 @@ int flowse_op_conv3x3_gn(const float* in1, int C1, const float* in2, int C2, con
         return ERR_SHAPE;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int C = C1 + C2, HW = H * W;
-    const int G = std::min(C / 4, 32);
-    const int nblk = gn_partial_blocks(HW, C);
-    float* part = scratch;
-    float* mean = scratch + (int64_t)B * nblk * C * 2;
-    float* scl = mean + (int64_t)B * C;
-    int rc = launch_gn_stats(in1, C1, in2, C2, B, HW, part, nblk, s);
-    if (rc != OK) return rc;
-    rc = launch_gn_finalize(part, nblk, C, nullptr, 0, 0, B, HW, G, gamma, eps, mean, scl, s);
-    if (rc != OK) return rc;
-    ConvArgs c;
-    c.in1 = in1; c.in2 = in2; c.C1 = C1; c.C2 = C2;
-    c.w = w; c.bias = bias; c.bias2 = bias2; c.bias2_stride = bias2_stride; c.res = res; c.out = out;
-    c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.taps = 9; c.scale = scale;
-    c.gn = GnParams{mean, scl, beta};
+    ConvArgs c = conv_args(in1, C1, in2, C2, w, bias, bias2, bias2_stride, res, out, B, H, W, Cout, 9, scale);
     c.gn_silu = silu;
-    return launch_conv(c, s);
+    const int rc = op_gn_prologue(in1, C1, in2, C2, gamma, beta, eps, B, H * W, scratch, s, &c.gn);
+    return rc != OK ? rc : launch_conv(c, s);
 }
 
 static int op_conv3x3_winograd(const float* in1, int C1, const float* in2, int C2, const float* gamma,
@@ -1174,10 +1110,7 @@ static int op_conv3x3_winograd(const float* in1, int C1, const float* in2, int C
     float* wf = scratch + flowse_op_group_norm_scratch_floats(B, HW, C);
     int rc = two_d ? launch_w2d_weights(w, Cout, C, wf, s) : launch_f43_weights(w, Cout, C, wf, s);
     if (rc != OK) return rc;
-    ConvArgs c;
-    c.in1 = in1; c.in2 = in2; c.C1 = C1; c.C2 = C2;
-    c.w = w; c.bias = bias; c.bias2 = bias2; c.bias2_stride = bias2_stride; c.res = res; c.out = out;
-    c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.taps = 9; c.scale = scale;
+    ConvArgs c = conv_args(in1, C1, in2, C2, w, bias, bias2, bias2_stride, res, out, B, H, W, Cout, 9, scale);
     if (two_d) c.wino2 = wf;
     else c.wino = wf;
     const int ks = two_d ? 1 : conv_ksplit(B, H, W, C, Cout, 9);
@@ -1186,17 +1119,9 @@ static int op_conv3x3_winograd(const float* in1, int C1, const float* in2, int C
         c.partial = wf + conv_wino_numel(Cout, C);
     }
     if (gamma) {
-        const int G = std::min(C / 4, 32);
-        const int nblk = gn_partial_blocks(HW, C);
-        float* part = scratch;
-        float* mean = scratch + (int64_t)B * nblk * C * 2;
-        float* scl = mean + (int64_t)B * C;
-        rc = launch_gn_stats(in1, C1, in2, C2, B, HW, part, nblk, s);
-        if (rc != OK) return rc;
-        rc = launch_gn_finalize(part, nblk, C, nullptr, 0, 0, B, HW, G, gamma, eps, mean, scl, s);
-        if (rc != OK) return rc;
-        c.gn = GnParams{mean, scl, beta};
         c.gn_silu = silu;
+        rc = op_gn_prologue(in1, C1, in2, C2, gamma, beta, eps, B, HW, scratch, s, &c.gn);
+        if (rc != OK) return rc;
     }
     // the 2-D entry names its kernel: every shape conv_w2d_shape_ok admits runs it (launch_conv's policy would hand images of
     // up to 2048 pixels to another kernel, or refuse their fused GroupNorm input)
@@ -1252,8 +1177,8 @@ static int op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
     const bool head = Cout == 4 && taps == 9 && !in2 && conv_supports_head4(B, H, W, C1, 0, Cout, taps);
     const int ks = (halo || head) ? 1 : conv16_ksplit(B, H, W, (int)C, Cout, taps);
     const int64_t nw = ((int64_t)Cout * taps * C + 3) & ~(int64_t)3;
-    // the same 256-byte round-up per sub-buffer as take() below, upper bound over the optional ones
-    auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
+    // the carver's round-up per sub-buffer, upper bound over the optional ones
+    const auto up = Carver::up;
     const int64_t need = up(2 * M * C1) + up(2 * M * C2) + 2 * up(2 * nw) + 2 * up(2 * M * Cout) +
                          (ks > 1 ? up(4 * (int64_t)ks * M * Cout) : 0);
     if (scratch_bytes < need) {
@@ -1264,18 +1189,17 @@ static int op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
         set_error("flowse_op_conv2d_16: fused GroupNorm input only on LDS-halo shapes");
         return ERR_SHAPE;
     }
-    char* p = static_cast<char*>(scratch);
-    auto take = [&](int64_t bytes) { char* q = p; p += (bytes + 255) & ~(int64_t)255; return q; };
-    void* a1 = take(2 * M * C1);
-    void* a2 = C2 ? take(2 * M * C2) : nullptr;
-    void* wq = take(2 * nw);
+    Carver cv{static_cast<char*>(scratch)};
+    void* a1 = cv.take(2 * M * C1);
+    void* a2 = C2 ? cv.take(2 * M * C2) : nullptr;
+    void* wq = cv.take(2 * nw);
     const bool frag = (taps == 9 && conv16_uses_pc(B, H, W, C1, C2, Cout, taps)) || conv16_smallm_ok(B, H, W, C1, C2, Cout, taps);
-    void* wfrag = frag ? take(2 * nw) : nullptr;
+    void* wfrag = frag ? cv.take(2 * nw) : nullptr;
     const bool direct = head || out_f32;                   // fp32 res / out, used in place
-    void* r16 = res && !direct ? take(2 * M * Cout) : nullptr;
-    void* o16 = direct ? nullptr : take(2 * M * Cout);
-    float* part = ks > 1 ? reinterpret_cast<float*>(take(4 * (int64_t)ks * M * Cout)) : nullptr;
-    if ((size_t)(p - static_cast<char*>(scratch)) > (size_t)scratch_bytes) {
+    void* r16 = res && !direct ? cv.take(2 * M * Cout) : nullptr;
+    void* o16 = direct ? nullptr : cv.take(2 * M * Cout);
+    float* part = ks > 1 ? static_cast<float*>(cv.take(4 * (int64_t)ks * M * Cout)) : nullptr;
+    if ((size_t)(cv.p - static_cast<char*>(scratch)) > (size_t)scratch_bytes) {
         set_error("flowse_op_conv2d_16: scratch too small");
         return ERR_ARG;
     }
@@ -1285,11 +1209,9 @@ static int op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
     if (rc == OK && frag) rc = launch_pc16_weights(wq, Cout, (int)C, wfrag, s, taps);
     if (rc == OK && r16) rc = launch_convert(res, DT_F32, r16, dt, M * Cout, s);
     if (rc != OK) return rc;
-    ConvArgs c;
-    c.in1 = static_cast<const float*>(a1); c.in2 = static_cast<const float*>(a2); c.C1 = C1; c.C2 = C2;
-    c.w = w; c.bias = bias; c.bias2 = bias2; c.bias2_stride = bias2 ? bias2_stride : 0;
-    c.res = static_cast<const float*>(r16); c.out = static_cast<float*>(o16);
-    c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.taps = taps; c.scale = scale;
+    ConvArgs c = conv_args(static_cast<const float*>(a1), C1, static_cast<const float*>(a2), C2, w, bias, bias2,
+                           bias2 ? bias2_stride : 0, static_cast<const float*>(r16), static_cast<float*>(o16), B, H, W, Cout,
+                           taps, scale);
     c.ksplit = ks; c.partial = part;
     c.wq = wq; c.terms = 1; c.wq_f16 = dt == DT_F16 ? 1 : 0;
     c.wfrag = wfrag;
@@ -1351,22 +1273,21 @@ int flowse_op_resblock_tail_16(const float* h, int C, const float* gn_mean, cons
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t M = (int64_t)B * H * W, XC = (int64_t)XC1 + XC2;
     const int64_t nw1 = ((int64_t)Cout * 9 * C + 3) & ~(int64_t)3, nw2 = ((int64_t)Cout * XC + 3) & ~(int64_t)3;
-    auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
+    const auto up = Carver::up;
     const int64_t need = up(2 * M * C) + up(2 * M * XC1) + up(2 * M * XC2) + 2 * up(2 * nw1) + 2 * up(2 * nw2) + up(2 * M * Cout);
     if (scratch_bytes < need) {
         set_error("flowse_op_resblock_tail_16: scratch needs %lld bytes", (long long)need);
         return ERR_ARG;
     }
-    char* p = static_cast<char*>(scratch);
-    auto take = [&](int64_t bytes) { char* q = p; p += (bytes + 255) & ~(int64_t)255; return q; };
-    void* h16 = take(2 * M * C);
-    void* a1 = take(2 * M * XC1);
-    void* a2 = XC2 ? take(2 * M * XC2) : nullptr;
-    void* wq1 = take(2 * nw1);
-    void* wf1 = take(2 * nw1);
-    void* wq2 = take(2 * nw2);
-    void* wf2 = take(2 * nw2);
-    void* o16 = take(2 * M * Cout);
+    Carver cv{static_cast<char*>(scratch)};
+    void* h16 = cv.take(2 * M * C);
+    void* a1 = cv.take(2 * M * XC1);
+    void* a2 = XC2 ? cv.take(2 * M * XC2) : nullptr;
+    void* wq1 = cv.take(2 * nw1);
+    void* wf1 = cv.take(2 * nw1);
+    void* wq2 = cv.take(2 * nw2);
+    void* wf2 = cv.take(2 * nw2);
+    void* o16 = cv.take(2 * M * Cout);
     int rc = launch_convert(h, DT_F32, h16, dt, M * C, s);
     if (rc == OK) rc = launch_convert(x1, DT_F32, a1, dt, M * XC1, s);
     if (rc == OK && XC2) rc = launch_convert(x2, DT_F32, a2, dt, M * XC2, s);
@@ -1375,11 +1296,9 @@ int flowse_op_resblock_tail_16(const float* h, int C, const float* gn_mean, cons
     if (rc == OK) rc = launch_pc16_weights(wq1, Cout, C, wf1, s, 9);
     if (rc == OK) rc = launch_pc16_weights(wq2, Cout, (int)XC, wf2, s, 1);
     if (rc != OK) return rc;
-    ConvArgs c;
-    c.in1 = static_cast<const float*>(h16); c.in2 = nullptr; c.C1 = C; c.C2 = 0;
-    c.w = w1; c.bias = b1; c.bias_x = b2; c.bias2 = nullptr; c.bias2_stride = 0; c.res = nullptr;
-    c.out = static_cast<float*>(o16);
-    c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.taps = 9; c.scale = scale;
+    ConvArgs c = conv_args(static_cast<const float*>(h16), C, nullptr, 0, w1, b1, nullptr, 0, nullptr,
+                           static_cast<float*>(o16), B, H, W, Cout, 9, scale);
+    c.bias_x = b2;
     c.wq = wq1; c.terms = 1; c.wq_f16 = dt == DT_F16 ? 1 : 0;
     c.wfrag = wf1;
     c.sc1 = a1; c.SC1 = XC1; c.sc2 = a2; c.SC2 = XC2; c.wfrag_sc = wf2;
@@ -1418,14 +1337,14 @@ int flowse_op_attention_16(const float* qkv, float* out, int B, int L, int C, in
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t n = (int64_t)B * L * C;
-    auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-    const int64_t need = up(2 * 3 * n) + up(2 * n);
+    const int64_t need = Carver::up(2 * 3 * n) + Carver::up(2 * n);
     if (scratch_bytes < need) {
         set_error("flowse_op_attention_16: scratch needs %lld bytes", (long long)need);
         return ERR_ARG;
     }
-    char* q16 = static_cast<char*>(scratch);
-    char* o16 = q16 + up(2 * 3 * n);
+    Carver cv{static_cast<char*>(scratch)};
+    void* q16 = cv.take(2 * 3 * n);
+    void* o16 = cv.take(2 * n);
     int rc = launch_convert(qkv, DT_F32, q16, dt, 3 * n, s);
     if (rc == OK) rc = launch_attention(q16, B, L, C, o16, s, dt);
     if (rc != OK) return rc;

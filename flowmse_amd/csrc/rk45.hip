@@ -269,18 +269,10 @@ extern "C" int flowse_rk45_sample(flowse_model* m, void* x_inout, const void* y,
     Plan* p = nullptr;
     int rc = get_plan(m, B, F, T, &p);
     if (rc != OK) return rc;
-    rc = reserve_times(m, (size_t)B);
-    if (rc != OK) return rc;
     const int64_t n = (int64_t)B * F * T;                        // complex elements of the state
-    const size_t need = rk45_bytes(n);
-    if (m->d_rk45_bytes < need) {
-        FLOWSE_HIP(hipDeviceSynchronize());
-        if (m->d_rk45) FLOWSE_HIP(hipFree(m->d_rk45));
-        m->d_rk45 = nullptr;
-        m->d_rk45_bytes = 0;
-        FLOWSE_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_rk45), need));
-        m->d_rk45_bytes = need;
-    }
+    rc = m->d_ts.reserve((size_t)B, true);
+    if (rc == OK) rc = m->d_rk45.reserve(rk45_bytes(n), true);
+    if (rc != OK) return rc;
     Rk45State st = carve(m->d_rk45, n);
     hipStream_t caller = static_cast<hipStream_t>(stream), s = nullptr;
     rc = enter_stream(m, caller, &s);
