@@ -1,6 +1,6 @@
 // Replaces (reference): ddpm_conv1x1 (flowmse/backbones/ncsnpp_utils/layers.py:100-105) = the shortcut Conv_2 of
 // ResnetBlockBigGANpp (layerspp.py:268-270) and NIN (layers.py:546-555) on the LARGE images of the fp32 mode.
-#include "conv_common.h"
+#include "conv_smallm.h"
 
 namespace flowse {
 
@@ -15,18 +15,14 @@ namespace flowse {
 // A fragment (16 bytes per lane straight from the activation tensor, through a per-wave buffer descriptor: rows past M read
 // as zero) and FOUR B fragments (the fragment-order weight copy the small-image kernel uses, 1 KB per wave-level request,
 // L2-resident: the whole matrix is 64-256 KB) and issues 16 MFMAs.  No LDS, no barrier, no VALU in the loop; requests run
-// three k-blocks ahead through register rings with compile-time slots.  Output: straight from the accumulator layout (a lane
+// three k-blocks ahead through the branch-free register ring of the small-image kernels (described at ring_run,
+// conv_smallm.h).  Output: straight from the accumulator layout (a lane
 // holds one channel of 16 pixels per tile: 64 dword stores per wave, 128 contiguous bytes per half-wave; the output is 1/3 of
 // the traffic and far from store-issue bound here), bias / per-sample bias / residual added on the way; GroupNorm partial
 // statistics per block of 256 pixels (eight waves meet once in LDS).
 constexpr int C1_PX = 32;            // pixels per wave
 constexpr int C1_WAVES = 8;          // waves per block (256 pixels: the statistics block).  (Four-wave blocks, three per CU so that
                                      // output stages overlap other blocks' MFMAs, measured 6 % slower: 12 waves' requests per CU)
-
-template <class F, int... I>
-__device__ __forceinline__ void c1_unroll(F& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
 
 __global__ __launch_bounds__(512, 2) void conv1x1_stream_kernel(ConvArgs a) {
     __shared__ float red[C1_WAVES * 128 * 2];            // per wave and channel: mean, M2 of its 32 pixels
@@ -96,25 +92,26 @@ __global__ __launch_bounds__(512, 2) void conv1x1_stream_kernel(ConvArgs a) {
         acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(ra[R].w), __uint_as_float(rb[R][2].w), acc[2], 0, 0, 0);
         acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(ra[R].w), __uint_as_float(rb[R][3].w), acc[3], 0, 0, 0);
     };
-    // a uniform loop of D-step groups, requests D - 1 steps ahead, none under a branch; a tail of at most D - 1 steps whose
-    // operands are already in flight
+    // The loop of ring_run (conv_smallm.h) with first = 0, stride = 1, written out in the kernel.  S = 4 nchunks is whole
+    // D-step groups, and hipcc sees that only when it meets the loop in the kernel's own body: it drops the tail and moves the
+    // prologue's requests behind the S >= D test.  Through ring_run the tail's 48 MFMAs stay (profiles/smallm_shared_asm.md).
     {
         auto pro = [&](auto dc) {
             constexpr int d = decltype(dc)::value;
             if constexpr (d < D - 1) gload(d, dc);
         };
-        c1_unroll(pro, std::make_integer_sequence<int, D>{});
+        ring_unroll(pro, std::make_integer_sequence<int, D>{});
     }
     int i = 0;
     for (; i + D <= S; i += D) {
         auto step = [&](auto dc) {
             constexpr int d = decltype(dc)::value;
             gload(i + d + D - 1, std::integral_constant<int, (d + D - 1) % D>{});
-            __builtin_amdgcn_sched_barrier(0);            // (hipcc otherwise sinks the requests down to their first use)
+            __builtin_amdgcn_sched_barrier(0);
             compute(dc);
             __builtin_amdgcn_sched_barrier(0);
         };
-        c1_unroll(step, std::make_integer_sequence<int, D>{});
+        ring_unroll(step, std::make_integer_sequence<int, D>{});
     }
     {
         const int rem = S - i;
@@ -124,7 +121,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_stream_kernel(ConvArgs a) {
                 if (d < rem) compute(dc);
             }
         };
-        c1_unroll(tail, std::make_integer_sequence<int, D>{});
+        ring_unroll(tail, std::make_integer_sequence<int, D>{});
     }
 
     // ---- output straight from the C/D layout of the 32x32 MFMA: col = lane & 31 (channel), row = (r & 3) + 8 (r >> 2) + 4 kh.

@@ -15,7 +15,7 @@
 // Replaces (reference): ddpm_conv3x3 / ddpm_conv1x1 (flowmse/backbones/ncsnpp_utils/layers.py:100-124), NIN (:546-555).
 #include <cstdio>
 
-#include "conv_common.h"
+#include "conv_smallm.h"
 
 namespace flowse {
 
@@ -51,13 +51,9 @@ bool conv_w2d_enabled() { return g_w2d && !g_no_wino_policy; }
 static const bool g_no_smallm = getenv("FLOWSE_NO_SMALLM") != nullptr;
 static const int g_smallm_max = getenv("FLOWSE_SMALLM_MAX") ? atoi(getenv("FLOWSE_SMALLM_MAX")) : 2048;
 bool conv_smallm_ok(int B, int H, int W, int C1, int C2, int Cout, int taps) {
-    if (g_no_smallm || g_force_generic || (taps != 1 && taps != 9) || (C1 % KC) || (C2 % KC) || (Cout % 32) || C1 <= 0) return false;
-    const int64_t M = (int64_t)B * H * W;
     // (2048 pixels = 16 x 16 at batch 8: 4.96 vs 5.76 ms for the level against the sliced F(4,3) kernel + reduction launches,
     // A-B-A-B on one box; FLOWSE_SMALLM_MAX moves the limit)
-    if (M > g_smallm_max || M < 1) return false;
-    const int64_t cmax = C1 > C2 ? C1 : C2;
-    return (int64_t)(32 + 2 * W + 2) * cmax * 4 < (1LL << 31) && (int64_t)Cout * taps * (C1 + C2) * 4 < (1LL << 31);
+    return !g_no_smallm && !g_force_generic && sm_shape_ok(B, H, W, C1, C2, Cout, taps, g_smallm_max, 4);
 }
 bool conv_force_generic() { return g_force_generic; }
 
