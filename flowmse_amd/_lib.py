@@ -20,6 +20,7 @@ FLOWSE_MAX_ATTN = 4
 FLOWSE_MAX_LANES = 4
 FLOWSE_MAX_SPEC_ROWS = 64
 FLOWSE_BYTES_WEIGHTS, FLOWSE_BYTES_OWNED = 0, 1
+FLOWSE_LOSS_MSE, FLOWSE_LOSS_MAE = 0, 1
 
 
 class FlowseError(RuntimeError):
@@ -92,6 +93,10 @@ SIGNATURES = {
     "flowse_metrics_workspace_bytes": (_i64, [_i]),
     "flowse_estoi": (_i, [_fp, _fp, _i, _vp, _i64, _vp, _vp]),
     "flowse_energy_ratios": (_i, [_fp, _fp, _fp, _i, _vp, _i64, _vp, _vp]),
+    "flowse_fm_pair": (_i, [_vp, _vp, _fp, _vp, _vp, C.c_uint64, _f, _f, _vp, _vp, _i, _i, _i, _vp]),
+    "flowse_fm_loss_workspace_bytes": (_i64, [_i, _i, _i]),
+    "flowse_fm_loss_rows": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _f, _f, _i, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "flowse_fm_loss": (_i, [_vp, _vp, _vp, _fp, _vp, _vp, C.c_uint64, _f, _f, _i, _vp, _i, _i, _i, _vp]),
     "flowse_profile_begin": (_i, [_vp, _i]),
     "flowse_profile_end": (_i, [_vp, C.c_char_p, _i]),
     "flowse_upfirdn2d": (_i, [_fp, _fp] + [_i] * 13 + [_fp, _i, _i, _vp]),

@@ -270,6 +270,22 @@ class NCSNpp(nn.Module):
                                                   B, F, T, mode, _lib.current_stream()))
         return out
 
+    def fm_loss(self, x0, y, t, z, keys_dev, seed, sigma_min, sigma_max, loss_code):
+        """One ``flowse_fm_loss`` call: float64 [B + 1] on the device, the B row losses of the flow-matching objective
+        and their mean.  ``z`` (complex64 like x0) or ``keys_dev`` (int64 [B] on the device), exactly one."""
+        self._check_io(x0, y, t)
+        self._ensure_uploaded(x0.device)
+        x0, y = x0.contiguous(), y.contiguous()
+        t = t.to(device=x0.device, dtype=torch.float32).contiguous()
+        z = None if z is None else z.to(x0.device).contiguous()
+        B, _, F, T = x0.shape
+        out = torch.empty(B + 1, dtype=torch.float64, device=x0.device)
+        with torch.cuda.device(x0.device):
+            _lib.check(_lib.lib.flowse_fm_loss(self._handle, _lib.ptr(x0), _lib.ptr(y), _lib.ptr(t), _lib.ptr(z),
+                                               _lib.ptr(keys_dev), seed, sigma_min, sigma_max, loss_code, _lib.ptr(out),
+                                               B, F, T, _lib.current_stream()))
+        return out
+
     def forward(self, x, time_cond):
         if x.dim() != 4 or x.shape[1] != 2:
             raise ValueError(f"expected complex input [B,2,F,T], got {tuple(x.shape)}")

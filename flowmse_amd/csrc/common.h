@@ -220,6 +220,16 @@ __device__ __forceinline__ void chan_merge4(float& nA, float* acc8, float nB, co
     nA = n;
 }
 
+// ------------------------------------------------------------------ float64 block reduction (metrics.hip, fmloss.hip)
+// tree sum of red[0 .. n) (n a power of two <= blockDim.x) into red[0]: the same order for every call
+__device__ __forceinline__ void tree_sum(double* red, int n) {
+    for (int s = n >> 1; s > 0; s >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    }
+    __syncthreads();
+}
+
 // ------------------------------------------------------------------ conv (implicit GEMM, MFMA fp32)
 struct ConvArgs {
     // in1 / in2 hold elements of type in_dt, res / out of type out_dt (declared float*: the fp32 kernels use them as

@@ -52,15 +52,6 @@ static void design_estoi_taps(double* h) {
     for (int k = 0; k < MET_TAPS; ++k) h[k] /= sum;
 }
 
-// tree sum of red[0 .. n) (n a power of two <= blockDim.x) into red[0]: the same order for every call
-__device__ __forceinline__ void tree_sum(double* red, int n) {
-    for (int s = n >> 1; s > 0; s >>= 1) {
-        __syncthreads();
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    }
-    __syncthreads();
-}
-
 // grid (ceil(L10 / 256), 2): row 0 the clean signal, row 1 the processed one.  c = 290 + 8 n, p = c mod 5, q = c div 5,
 // out[n] = sum_{j < 117} H[p][j] x[q - j], x zero outside [0, L); 64-bit sample indices as in resample.hip.
 __global__ __launch_bounds__(256) void met_resample_kernel(const float* __restrict__ clean, const float* __restrict__ proc,

@@ -203,6 +203,7 @@ struct flowse_model {
     int64_t graph_launches = 0;            // hipGraphLaunch calls made by this handle (flowse_model_graph_launches)
     DevBuf<float> d_rk;                    // fixed-step RK scratch: stage input + slope accumulator, 2 x [B,1,F,T] complex64
     DevBuf<char> d_rk45;                   // adaptive RK45 state (flowse_rk45_sample): y, y_new, K1..K7, stage input, norms
+    DevBuf<char> d_fm;                     // flowse_fm_loss: x_t, v (complex64 [B,1,F,T] each) and the loss partials; first use
     // single-module handles (flowse_block_create): one ResnetBlockBigGANpp / AttnBlockpp / Combine behind the same
     // weight packer, plan builder and kernels as the full network -- unit parity against the reference's modules
     int block_kind = -1;                   // -1: full network; else FLOWSE_BLOCK_*

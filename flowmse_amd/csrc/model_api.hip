@@ -187,7 +187,7 @@ int leave_stream(flowse_model* m, hipStream_t caller, hipStream_t work) {
 // the byte count (flowse_model_device_bytes) go through
 template <class M, class Fn>
 static void each_owned_buffer(M* m, Fn f) {
-    f(m->d_ws); f(m->d_ts); f(m->d_call); f(m->d_rk); f(m->d_rk45);
+    f(m->d_ws); f(m->d_ts); f(m->d_call); f(m->d_rk); f(m->d_rk45); f(m->d_fm);
 }
 template <class W, class Fn>
 static void each_weight_buffer(W* w, Fn f) {

@@ -9,32 +9,9 @@
 //   words (0, 1) -> the value at the even frame t, words (2, 3) -> the value at t + 1
 //   u1 = ((w_a >> 9) + 0.5) * 2^-23 in (0, 1),  u2 = (w_b >> 8) * 2^-24 in [0, 1)      (both exact in fp32)
 //   z  = sqrtf(-logf(u1)) * (cospif(2 u2) + i sinpif(2 u2))                                (E|z|^2 = 1)
-#include "common.h"
+#include "noise.h"
 
 namespace flowse {
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t (&w)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-
-__device__ __forceinline__ float2 complex_normal(uint32_t wa, uint32_t wb) {
-    const float u1 = ((float)(wa >> 9) + 0.5f) * 0x1p-23f;       // 23-bit integer + 0.5: exact
-    const float u2x2 = (float)(wb >> 8) * 0x1p-23f;              // 2 * u2, exact
-    const float r = sqrtf(-logf(u1));
-    return make_float2(r * cospif(u2x2), r * sinpif(u2x2));
-}
 
 // One thread per Philox call: frames (2 t2, 2 t2 + 1) of one bin of one row = one 16-byte load and store.  The float4
 // index of a thread IS its linear index (rows are [F][T] complex, T even).  ADD: out = y + sigma * z, else out = z.

@@ -16,6 +16,9 @@ weights and synthetic noisy/clean pairs (no checkpoint or dataset needed) as an 
 bin and frame) instead of the process-wide generator, and ``--gpus N`` shards the set over N GPUs of this node, one
 process each; in keyed mode the wavs and the CSV are byte-identical for any ``--gpus``, any ``--streams`` and any file
 order (they depend on weights, utterance, seed, solver settings and ``--batch`` only).
+
+``--valid_loss K`` (keyed noise only) adds a ``valid_loss`` column: the flow-matching loss the model is trained on
+(reference ``VFModel._step``, model.py:130-143), on each file's 256-frame validation item, mean over K keyed draws.
 """
 import argparse
 import csv
@@ -228,6 +231,10 @@ def build_parser():
                     help="host: ESTOI from pystoi where importable (nan otherwise), the energy ratios in numpy. device: ESTOI "
                          "and SI-SDR / SI-SIR / SI-SAR in float64 on the GPU (flowmse_amd.metrics), read back once per "
                          "sampler call; PESQ stays on the host either way")
+    ap.add_argument("--valid_loss", type=int, default=0, metavar="K",
+                    help="also score every file's validation item (centre crop / pad to 256 frames, as the reference's "
+                         "validation set builds it) with the flow-matching loss the model is trained on: a valid_loss column "
+                         "with the mean over K keyed draws of (t, z). Needs --noise keyed. 0 = off")
     ap.add_argument("--gpus", type=int, default=1,
                     help="shard the test set over this many GPUs of this node, one process each (keyed noise only)")
     return ap
@@ -245,6 +252,10 @@ def parse_args(argv=None, ap=None):
         ap.error("--gpus > 1 needs --noise keyed: a single host random stream has no meaning across ranks")
     if args.noise is None:
         args.noise = "keyed" if args.gpus > 1 else "torch"
+    if args.valid_loss < 0:
+        ap.error(f"--valid_loss must be >= 0, got {args.valid_loss}")
+    if args.valid_loss and args.noise != "keyed":
+        ap.error("--valid_loss needs --noise keyed: its times and noise are draws of the keyed stream")
     return args
 
 
@@ -343,6 +354,9 @@ def _write_reports(target_dir, data, args, model, epoch, noise_seed):
         f.write("SI-SDR: {} \n".format(mean_std(data["si_sdr"])))
         f.write("SI-SIR: {} \n".format(mean_std(data["si_sir"])))
         f.write("SI-SAR: {} \n".format(mean_std(data["si_sar"])))
+        if "valid_loss" in data:                                   # --valid_loss only: the other files are unchanged
+            a = np.asarray(data["valid_loss"], dtype=np.float64)
+            f.write(f"valid_loss: {a.mean():.6g} ± {a.std():.6g} \n")
     with open(os.path.join(target_dir, "_settings.txt"), "w") as f:
         f.write(f"epoch: {epoch}\ncheckpoint file: {args.ckpt}\nodesolver_type: {args.odesolver_type}\n")
         f.write(f"odesolver: {args.odesolver}\nReverse starting point: {args.reverse_starting_point}\n")
@@ -353,6 +367,8 @@ def _write_reports(target_dir, data, args, model, epoch, noise_seed):
         f.write(f"noise: {args.noise}\nnoise seed: {noise_seed}\ngpus: {args.gpus}\n")
         if getattr(args, "metrics", "host") == "device":           # a host run's file is unchanged
             f.write("metrics: device\n")
+        if getattr(args, "valid_loss", 0):
+            f.write(f"valid_loss draws: {args.valid_loss}\n")
 
 
 _COLUMNS = ("filename", "pesq", "estoi", "si_sdr", "si_sir", "si_sar")
@@ -423,6 +439,7 @@ def _main_keyed(args, ap):
     """Keyed-noise run, as one rank of ``--gpus N`` or in-process at ``--gpus 1``: the same plan and the same calls."""
     import torch.distributed as dist
     from flowmse_amd.parallel import gather_rows, plan_shards
+    from flowmse_amd.util.inference import keyed_valid_losses, validation_item
     from flowmse_amd.util.noise import utterance_key
     rank, world = _enter_rank(args)
     seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(8), "little")
@@ -470,6 +487,15 @@ def _main_keyed(args, ap):
             metric_rows, outs = _metrics_device(pesq, [(waves[i][0], yd, x_hat) for i, yd, x_hat in zip(flat, ys, outs)])
         else:
             metric_rows = [_metrics(pesq, stoi, waves[i][0], waves[i][1], x_hat) for i, x_hat in zip(flat, outs)]
+        if args.valid_loss:            # per planned batch, so that the rows of a call do not depend on --gpus or --streams
+            at = {i: j for j, i in enumerate(flat)}
+            for g in chunk:
+                items = [validation_item(model, torch.from_numpy(waves[i][0])[None].cuda(),
+                                         torch.from_numpy(waves[i][1])[None].cuda()) for i in g]
+                vl = keyed_valid_losses(model, items, [names[i] for i in g], seed=seed, draws=args.valid_loss,
+                                        batch=args.batch)
+                for i, v in zip(g, vl):
+                    metric_rows[at[i]] = tuple(metric_rows[at[i]]) + (float(v),)
         for i, x_hat, m in zip(flat, outs, metric_rows):
             y = waves[i][1]
             _write_wav(target_dir + "files/" + names[i], x_hat, 16000)
@@ -479,7 +505,8 @@ def _main_keyed(args, ap):
     if rank == 0:
         rows.sort(key=lambda r: r[0])                              # the global sorted-filename order
         assert [r[0] for r in rows] == list(range(len(names))), "every utterance exactly once"
-        data = {c: [r[1 + j] for r in rows] for j, c in enumerate(_COLUMNS)}
+        columns = _COLUMNS + (("valid_loss",) if args.valid_loss else ())
+        data = {c: [r[1 + j] for r in rows] for j, c in enumerate(columns)}
         _write_reports(target_dir, data, args, model, epoch, seed)
         print(f"enhanced {len(names)} utterances ({sum(r[-1] for r in rows)} frames) in {dt:.2f} s on {world} GPU(s), "
               f"keyed noise seed {seed} -> {target_dir}")

@@ -3,7 +3,9 @@
 Reference: flowmse/model.py:19-206.  What evaluate.py uses (evaluate.py:64-132): ``load_from_checkpoint``,
 ``eval(no_ema=False)`` (= swap the EMA shadow weights in, model.py:92-103), ``.cuda()``, ``.ode``, ``_stft``,
 ``_forward_transform``, ``to_audio`` and the model itself as ``VF_fn(x, t, y)`` (= ``-dnn(cat[x,y], t)``,
-model.py:164-170).  Training (loss, optimizer, Lightning hooks, dataloaders) is out of scope.
+model.py:164-170).  The flow-matching objective is here forward-only (``_loss``, ``_step``, ``loss_rows``: model.py:118-143,
+the number ``validation_step`` logs as ``valid_loss``); training itself (backward, optimizer, Lightning hooks, dataloaders)
+is out of scope.
 """
 import pickle
 import types
@@ -176,6 +178,62 @@ class VFModel(nn.Module):
     def forward(self, x, t, y):
         """-dnn(cat([x, y], 1), t) (model.py:164-170); x, y complex64 [B,1,F,T] on 'cuda', t float32 [B]."""
         return self.dnn.vf_call(x, t, y, 1)
+
+    # ------------------------------------------------------------------ objective (model.py:118-143), forward only
+    def _loss(self, vectorfield, condVF):
+        """The reference's ``_loss`` (model.py:118-128): 0.5 * sum over (channel, bin, frame) of |err|^2 ('mse') or |err|
+        ('mae'), mean over the batch.  An unknown ``loss_type`` raises (the reference falls through to an unbound name)."""
+        from flowmse_amd.fmloss import loss_type_code
+        err = vectorfield - condVF
+        losses = err.abs() if loss_type_code(self.loss_type) else torch.square(err.abs())
+        return torch.mean(0.5 * torch.sum(losses.reshape(losses.shape[0], -1), dim=-1))
+
+    def _loss_draws(self, x0, t, z, keys, seed):
+        """(t, z, keys, Philox seed) of one objective evaluation: what is not given is drawn -- from the keyed stream with
+        ``keys`` (seed ^ 0x6C6F7373, apart from the sampler's prior noise), else from torch's generator as the reference
+        does (model.py:132-135)."""
+        from flowmse_amd.util.noise import loss_seed, loss_times
+        if keys is not None and z is not None:
+            raise ValueError("pass either z or keys, not both")
+        B = x0.shape[0]
+        if keys is not None:
+            from flowmse_amd.odes import key_words
+            keys = key_words(keys, B)
+        if t is None:
+            if keys is not None:
+                t = torch.from_numpy(loss_times(keys, loss_seed(seed), self.T_rev, self.t_eps)[:, 0].copy())
+            else:
+                rdm = (1 - torch.rand(B, device=x0.device)) * (self.T_rev - self.t_eps) + self.t_eps
+                t = torch.min(rdm, torch.tensor(self.T_rev, device=x0.device))
+        if z is None and keys is None:
+            z = torch.randn_like(x0)
+        return t.to(x0.device), z, keys, loss_seed(seed)
+
+    def _fm_loss(self, x0, y, t, z, keys, seed):
+        """float64 [B + 1]: row losses and their mean.  HIP tensors: one ``flowse_fm_loss`` call."""
+        from flowmse_amd.fmloss import loss_type_code
+        code = loss_type_code(self.loss_type)
+        t, z, keys, pseed = self._loss_draws(x0, t, z, keys, seed)
+        if x0.is_cuda:
+            from flowmse_amd.odes import device_keys
+            kd = None if keys is None else device_keys(keys, x0.shape[0], x0.device)
+            return self.dnn.fm_loss(x0, y, t, z, kd, pseed, float(self.ode.sigma_min), float(self.ode.sigma_max), code)
+        x_t, _, u = self.ode.marginal_sample(x0, t, y, z, keys=keys, seed=pseed, with_target=True)
+        err = (self(x_t, t, y) - u).abs().double()
+        rows = 0.5 * (err if code else err * err).reshape(err.shape[0], -1).sum(-1)
+        return torch.cat([rows, rows.mean().reshape(1)])
+
+    def _step(self, batch, batch_idx=None, *, t=None, z=None, keys=None, seed=0):
+        """The reference's ``_step`` (model.py:130-143), forward only: the flow-matching loss of ``batch = (x0, y)`` as a
+        0-d float64 tensor on the inputs' device.  ``t`` / ``z`` may be given; ``keys`` (one 64-bit key per row) with
+        ``seed`` draws both from the keyed stream (``util.noise.loss_times`` and the noise of row key ``keys[b]``), so the
+        value depends on (weights, keys, seed) only."""
+        x0, y = batch
+        return self._fm_loss(x0, y, t, z, keys, seed)[-1]
+
+    def loss_rows(self, x0, y, t=None, z=None, *, keys=None, seed=0):
+        """The [B] per-row values whose mean ``_step`` returns (float64, on the inputs' device)."""
+        return self._fm_loss(x0, y, t, z, keys, seed)[:-1]
 
     def weights_frozen(self):
         """Context manager of the backbone: no in-place parameter updates inside (see NCSNpp.weights_frozen)."""

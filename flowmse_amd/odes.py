@@ -146,3 +146,63 @@ class FLOWMATCHING(ODE):
                                                                  self.prior_std(), _lib.ptr(x_T), B, F, T,
                                                                  _lib.current_stream()))
         return x_T, None
+
+    # ---- one training / validation pair of the path (reference VFModel._step, flowmse/model.py:134-140) ----------
+    def marginal_sample(self, x0, t, y, z=None, *, keys=None, seed=0, with_target=False):
+        """``x_t = mean(t) + sigma(t) z`` and, with ``with_target``, the conditional field
+        ``u = der_std z + der_mean = (sigma_max - sigma_min) z + (y - x0)``.  Returns ``(x_t, z_or_None[, u])``.
+
+        ``z=None`` without ``keys`` draws ``torch.randn_like(x0)`` as the reference does; ``keys`` (one 64-bit key per
+        row, as in ``prior_sampling``) with ``seed`` takes z from the keyed stream instead.  On HIP tensors this is one
+        ``flowse_fm_pair`` launch -- keyed noise is generated in registers and the returned ``z`` is ``None`` -- on CPU
+        tensors the tensor formulas of ``marginal_prob`` / ``der_mean`` / ``der_std``."""
+        if keys is not None and z is not None:
+            raise ValueError("marginal_sample: pass either z or keys, not both")
+        if x0.shape != y.shape or x0.dim() != 4 or x0.shape[1] != 1 or x0.dtype != torch.complex64 or y.dtype != x0.dtype:
+            raise ValueError(f"marginal_sample: x0, y must be complex64 [B,1,F,T], got {x0.dtype} {tuple(x0.shape)} / "
+                             f"{y.dtype} {tuple(y.shape)}")
+        B, _, F, T = x0.shape
+        if t.shape != (B,):
+            raise ValueError(f"marginal_sample: t must have shape [{B}], got {tuple(t.shape)}")
+        if keys is None and z is None:
+            z = torch.randn_like(x0)
+        if not x0.is_cuda:
+            if keys is not None:
+                from flowmse_amd.util.noise import keyed_noise_reference
+                z = torch.from_numpy(keyed_noise_reference(key_words(keys, B), int(seed) & _MASK64, F, T)).to(torch.complex64)
+            t = t.to(torch.float32)
+            mean, std = self.marginal_prob(x0, t, y)
+            x_t = mean + _bcast(std) * z
+            return (x_t, z, self.der_std(t) * z + self.der_mean(x0, t, y)) if with_target else (x_t, z)
+        from flowmse_amd import _lib
+        if T % 2:
+            raise ValueError(f"marginal_sample: the kernel takes an even number of frames, got T={T}")
+        x0c, yc = x0.contiguous(), y.contiguous()
+        zc = None if z is None else z.to(x0.device).contiguous()
+        kd = None if keys is None else device_keys(keys, B, x0.device)
+        td = t.to(device=x0.device, dtype=torch.float32).contiguous()
+        x_t = torch.empty_like(x0c)
+        u = torch.empty_like(x0c) if with_target else None
+        with torch.cuda.device(x0.device):
+            _lib.check(_lib.lib.flowse_fm_pair(_lib.ptr(x0c), _lib.ptr(yc), _lib.ptr(td), _lib.ptr(zc), _lib.ptr(kd),
+                                               int(seed) & _MASK64, float(self.sigma_min), float(self.sigma_max),
+                                               _lib.ptr(x_t), _lib.ptr(u), B, F, T, _lib.current_stream()))
+        return (x_t, z, u) if with_target else (x_t, z)
+
+
+_MASK64 = 0xFFFFFFFFFFFFFFFF
+
+
+def key_words(keys, B):
+    """The B row keys as Python ints in [0, 2**64): from a sequence of ints or an int64 tensor holding the same bits."""
+    words = [int(k) & _MASK64 for k in (keys.reshape(-1).tolist() if torch.is_tensor(keys) else keys)]
+    if len(words) != B:
+        raise ValueError(f"{len(words)} keys for a batch of {B}")
+    return words
+
+
+def device_keys(keys, B, device):
+    """The B row keys as an int64 device tensor holding the 64 key bits (torch has no arithmetic-free uint64 everywhere)."""
+    if torch.is_tensor(keys) and keys.dtype == torch.int64 and keys.numel() == B:
+        return keys.to(device).contiguous()
+    return torch.tensor([k - (1 << 64) if k >= (1 << 63) else k for k in key_words(keys, B)], dtype=torch.int64, device=device)

@@ -77,3 +77,42 @@ def utterance_key(name):
     """64-bit key of an utterance: the 8-byte BLAKE2b digest of the file's base name, little-endian.  Depends on the
     name only -- not on the directory, the listing, or the position in it."""
     return int.from_bytes(hashlib.blake2b(os.path.basename(name).encode(), digest_size=8).digest(), "little")
+
+
+# ---------------------------------------------------------------------------------------------- flow-matching loss draws
+# The objective of ``VFModel._step`` draws a time and a noise tensor per row.  Both come from the stream above, so a loss
+# depends on (weights, file name, seed, draw index) only (INTEGRATION.md, "Loss draws on the keyed stream").
+LOSS_TIME_BIN = 0xFFFFFFFF       # counter word 1 of a time draw: a bin index of the noise stream never reaches it
+LOSS_SEED_XOR = 0x6C6F7373       # "loss": the facade's Philox seed of the loss is seed ^ this, apart from the sampler's x_T noise
+_DRAW_MUL = 0x9E3779B97F4A7C15
+
+
+def draw_key(key, k):
+    """Row key of draw ``k`` of utterance ``key``: ``key ^ (k * 0x9E3779B97F4A7C15 mod 2**64)``; draw 0 is the key itself."""
+    return (int(key) ^ ((int(k) * _DRAW_MUL) & _MASK64)) & _MASK64
+
+
+def loss_seed(seed):
+    """The Philox seed ``VFModel._step`` / ``evaluate --valid_loss`` use for the loss draws of run seed ``seed``."""
+    return (int(seed) ^ LOSS_SEED_XOR) & _MASK64
+
+
+def loss_times(keys, seed, T_rev, t_eps, draws=1):
+    """The times of the flow-matching loss, float32 [len(keys), draws].  Draw ``k`` of key ``key`` reads word 0 of
+    ``Philox4x32-10(counter = (k, 0xFFFFFFFF, lo32(key), hi32(key)), key = (lo32(seed), hi32(seed)))``,
+    ``u01 = (w0 >> 8) * 2**-24``, and then the reference's expression (flowmse/model.py:132-133) in float32:
+    ``t = min((1 - u01) * (T_rev - t_eps) + t_eps, T_rev)``.  ``t_eps <= 0`` raises: the field divides by t."""
+    if not float(t_eps) > 0.0:
+        raise ValueError(f"loss_times: t_eps must be > 0 (the vector field divides by t), got {t_eps}")
+    if not float(T_rev) >= float(t_eps):
+        raise ValueError(f"loss_times: T_rev must be >= t_eps, got T_rev={T_rev} t_eps={t_eps}")
+    keys = np.asarray([int(k) & _MASK64 for k in np.asarray(keys, dtype=np.uint64).reshape(-1).tolist()], dtype=np.uint64)
+    seed = int(seed) & _MASK64
+    k = np.arange(int(draws), dtype=np.uint64)[None, :]
+    w0 = philox4x32_10((k, LOSS_TIME_BIN, keys[:, None] & np.uint64(_MASK32), keys[:, None] >> np.uint64(32)),
+                       (seed & _MASK32, seed >> 32))[0]
+    w0 = np.broadcast_to(w0, (keys.shape[0], int(draws)))
+    u01 = ((w0 >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)      # 24 bits: exact
+    span = np.float32(float(T_rev) - float(t_eps))             # the reference subtracts two Python floats
+    t = (np.float32(1.0) - u01) * span + np.float32(t_eps)
+    return np.minimum(t, np.float32(T_rev)).astype(np.float32)

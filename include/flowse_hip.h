@@ -91,7 +91,7 @@ void flowse_model_destroy(flowse_model* m);
 int flowse_model_view_create(flowse_model* parent, flowse_model** out);
 /* Device memory in bytes.  FLOWSE_BYTES_WEIGHTS: the weight set the handle refers to (every layout), the same number for
  * a parent and its views.  FLOWSE_BYTES_OWNED: what only this handle holds (workspace, time table, RK scratch, RK45
- * state, per-call argument block).  0 for a null handle or an unknown `what`. */
+ * state, flow-matching loss scratch, per-call argument block).  0 for a null handle or an unknown `what`. */
 #define FLOWSE_BYTES_WEIGHTS 0
 #define FLOWSE_BYTES_OWNED 1
 int64_t flowse_model_device_bytes(const flowse_model* m, int what);
@@ -402,6 +402,48 @@ int flowse_estoi(const float* clean, const float* proc, int L, void* workspace, 
                  void* stream);
 int flowse_energy_ratios(const float* est, const float* clean, const float* noisy, int L, void* workspace,
                          int64_t workspace_bytes, double* out3, void* stream);
+
+/* ---- flow-matching objective: the number a checkpoint is trained on (opt-in: VFModel._step, evaluate --valid_loss) ----
+ * Forward only.  Restated from the reference's VFModel._step (flowmse/model.py:130-143); for a row with clean spectrogram
+ * x0, noisy y (complex64 [B,1,F,T]), time t (float32 [B], device) and noise z:
+ *   sigma(t) = (1 - t) sigma_min + t sigma_max                            odes.py:86-88
+ *   x_t      = (1 - t) x0 + t y + sigma(t) z                              odes.py:83-84, model.py:134-137
+ *   u        = (sigma_max - sigma_min) z + (y - x0)                       odes.py:102-107, model.py:138-140
+ *   v        = VFModel.forward(x_t, t, y) = -dnn(cat[x_t, y], t)          model.py:141, 164-170
+ *   loss_b   = 0.5 * sum_{f,frame} |v - u|^2      (FLOWSE_LOSS_MSE)       model.py:118-128
+ *            = 0.5 * sum_{f,frame} |v - u|        (FLOWSE_LOSS_MAE)
+ *   loss     = mean_b loss_b
+ * The time a training step draws, t_b = min((1 - rand)(T_rev - t_eps) + t_eps, T_rev) (model.py:132-133), is the
+ * caller's: flowmse_amd.util.noise.loss_times restates it on the keyed stream.
+ * z is a tensor (z != NULL) or generated in registers from the keyed stream of flowse_prior_sample_keyed (keys_dev != NULL:
+ * B 64-bit words in device memory, with `seed`; frame offsets are 0); exactly one of the two is non-NULL.  T must be even
+ * and the complex64 pointers 16-byte aligned.  Bad arguments return FLOWSE_ERR_ARG with the entry's name in the message
+ * and launch nothing.  Every entry only enqueues: no host synchronisation (flowse_fm_loss grows the handle's buffers first
+ * where it must, as every per-call entry does).
+ * flowse_fm_pair: x_t into xt_out and, when target_out != NULL, u into target_out, both complex64 [B,1,F,T], in fp32 with
+ *   the reference's operation order: a = 1 - t, sig = a sigma_min + t sigma_max, x_t = (a x0 + t y) + sig z,
+ *   u = (sigma_max - sigma_min) z + (y - x0); each operation rounds once.
+ * flowse_fm_loss_rows: from a field vf (complex64 [B,1,F,T]) the B row losses and their mean into out[0 .. B] (B + 1
+ *   doubles, device).  u and d = vf - u are formed in float64 from the fp32 inputs and summed in float64: per row in
+ *   fixed blocks whose number depends on (F, T) only, each block a strided per-thread sum and a fixed-order tree, the
+ *   blocks then in index order, the rows of the mean in row order.  No atomics: a row's value does not depend on B or on
+ *   its position, and the same input gives the same bits.  `workspace`: flowse_fm_loss_workspace_bytes(B, F, T) bytes of
+ *   device memory (-FLOWSE_ERR_ARG for a bad shape).
+ * flowse_fm_loss: flowse_fm_pair, then the shape's launch list in mode 1 (flowse_vf_forward's path, per-row t), then
+ *   flowse_fm_loss_rows, on one stream; bit-identical to the three calls made separately.  x_t, v and the partials live in
+ *   one buffer of the handle that is allocated by the first call (counted by FLOWSE_BYTES_OWNED; growing it synchronises
+ *   the device once).  Works in every precision mode: the boundary tensors are complex64 in all of them. */
+#define FLOWSE_LOSS_MSE 0
+#define FLOWSE_LOSS_MAE 1
+int flowse_fm_pair(const void* x0, const void* y, const float* t_dev, const void* z, const uint64_t* keys_dev, uint64_t seed,
+                   float sigma_min, float sigma_max, void* xt_out, void* target_out, int B, int F, int T, void* stream);
+int64_t flowse_fm_loss_workspace_bytes(int B, int F, int T);
+int flowse_fm_loss_rows(const void* vf, const void* x0, const void* y, const void* z, const uint64_t* keys_dev, uint64_t seed,
+                        float sigma_min, float sigma_max, int loss_type, double* out, void* workspace, int64_t workspace_bytes,
+                        int B, int F, int T, void* stream);
+int flowse_fm_loss(flowse_model* m, const void* x0, const void* y, const float* t_dev, const void* z, const uint64_t* keys_dev,
+                   uint64_t seed, float sigma_min, float sigma_max, int loss_type, double* out, int B, int F, int T,
+                   void* stream);
 
 /* ---- in-library kernel timing (used by bench.py for the live roofline figure) -------------------------
  * Between _begin and _end every selected launch of this handle is bracketed by HIP events on the launch
