@@ -98,7 +98,7 @@ def enhance_long(model, y, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRA
     the waveform from one ``flowse_istft_decompress_chunks`` launch; nothing of the recording's length but its samples,
     the chunk rows and the waveform is held.  With ``VF_fn`` or CPU tensors the same steps run as torch ops -- stft,
     spec_fwd, index, sampler, blend (float64, rounded to complex64), spec_back, istft: the oracle composition."""
-    from flowmse_amd.evaluate import enhance_waveform
+    from flowmse_amd.evaluate import _analyze, _fused_ok, enhance_waveform
     from flowmse_amd.sampling import get_white_box_solver
     if int(batch) < 1:
         raise ValueError(f"enhance_long: batch must be >= 1, got {batch}")
@@ -117,13 +117,13 @@ def enhance_long(model, y, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRA
                                 noise_seed=noise_seed, as_tensor=as_tensor)
     norm_factor = y.abs().max().item()
     y = y.to(device)
-    fused = VF_fn is None and hasattr(dm, "fused_ok") and dm.fused_ok(y)
+    fused = _fused_ok(model, [y], VF_fn)
     if fused:                      # the chunk rows straight from the samples: one HIP kernel, no global spectrogram
         Y = dm.analyze_chunks(y / norm_factor, Tc, hop)
         with torch.cuda.device(device):
             model.dnn.reserve(batch, Y.shape[2], Tc)     # the workspace of a full group, whatever K is
     else:
-        S = torch.unsqueeze(model._forward_transform(model._stft(y / norm_factor)), 0)
+        S = _analyze(model, y / norm_factor, False, pad=False)
         S = torch.nn.functional.pad(S, (0, Tg - S.size(3), 0, 0))
         Y = torch.cat([S[..., k * hop:k * hop + Tc] for k in range(K)], dim=0)
     zg = _chunk_noise(z, noise_key, Y, Tg)

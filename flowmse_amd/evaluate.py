@@ -19,6 +19,10 @@ order (they depend on weights, utterance, seed, solver settings and ``--batch`` 
 
 ``--valid_loss K`` (keyed noise only) adds a ``valid_loss`` column: the flow-matching loss the model is trained on
 (reference ``VFModel._step``, model.py:130-143), on each file's 256-frame validation item, mean over K keyed draws.
+
+Layout: the per-utterance recipe lives once, in ``_enhance`` (``enhance_waveform`` / ``enhance_batch`` / ``enhance_concurrent``
+are it with one group, one group of all, and lanes); ``plan_calls`` lists a run's sampler calls for either noise mode and
+``run_calls`` is the one loop that turns them into wavs and rows.
 """
 import argparse
 import csv
@@ -52,31 +56,67 @@ def mean_std(data):
     return f"{a.mean():.2f} ± {a.std():.2f}" if a.size else "nan"
 
 
+def _fused_ok(model, ys, VF_fn=None):
+    """True when analysis and synthesis of the waveforms ``ys`` run as the library's spectrogram kernels: the model's own
+    field (no ``VF_fn``), device tensors, the released STFT configuration (``SpecTransform.fused_ok``)."""
+    dm = model.data_module
+    return VF_fn is None and hasattr(dm, "fused_ok") and all(dm.fused_ok(y) for y in ys)
+
+
+def _analyze(model, y, fused, pad=True):
+    """Normalised waveform [1, samples] -> compressed spectrogram [1,1,F,T]: STFT + compression + frame padding as one HIP
+    kernel, or the same as torch ops (``pad=False``: the real frames only)."""
+    if fused:
+        return model.data_module.analyze(y)
+    Y = torch.unsqueeze(model._forward_transform(model._stft(y)), 0)
+    return pad_spec(Y) if pad else Y
+
+
+def _synthesize(model, sample, T_orig, norm_factor, fused):
+    """Sampled spectrogram [1,1,F,T] -> 1-D waveform of ``T_orig`` samples, rescaled: decompression + iSTFT + rescale as one
+    HIP kernel, or the same as torch ops."""
+    if fused:
+        return model.data_module.synthesize(sample, T_orig, norm_factor).reshape(-1)
+    return (model.to_audio(sample.squeeze(), T_orig) * norm_factor).reshape(-1)
+
+
+def _enhance(model, ys, groups, lanes=None, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", z=None, VF_fn=None, device=None,
+             noise_keys=None, noise_seed=0, as_tensor=False):
+    """The per-utterance recipe (evaluate.py:107-136) for a list of utterances ``ys`` (float tensors [1, samples_i]):
+    normalise by max|y| (one ``.item()`` each) -> analysis -> sampler -> synthesis.  ``groups``: lists of indices into
+    ``ys``, each an equal-padded-length batch that is sampled as one item.  ``lanes`` None: one ``get_white_box_solver`` call
+    per group, in order; an integer: ONE ``get_white_box_solver_multi`` call on that many lanes.  Either way the priors are
+    drawn in the order of ``groups``.  ``noise_keys``: one key per utterance, in the order of ``ys``.  Returns the waveforms in
+    the order of ``ys``: numpy, or with ``as_tensor`` 1-D tensors left on the compute device."""
+    ys = [y.to(device or y.device) for y in ys]
+    norms = [y.abs().max().item() for y in ys]
+    fused = _fused_ok(model, ys, VF_fn)
+    specs = [_analyze(model, y / n, fused) for y, n in zip(ys, norms)]     # y / max|y| as the reference computes it (evaluate.py:111)
+    Ys = [specs[g[0]] if len(g) == 1 else torch.cat([specs[i] for i in g], dim=0) for g in groups]
+    keys = [None if noise_keys is None else [noise_keys[i] for i in g] for g in groups]
+    field = VF_fn if VF_fn is not None else model
+    kw = dict(T_rev=T_rev, t_eps=t_eps, N=N, noise_seed=noise_seed)
+    if lanes is None:
+        samples = [get_white_box_solver(odesolver, model.ode, field, Y=Y, Y_prior=Y, z=z, noise_keys=k, **kw)()[0]
+                   for Y, k in zip(Ys, keys)]
+    else:
+        samples = get_white_box_solver_multi(odesolver, model.ode, field, Ys, lanes=lanes,
+                                             noise_keys=None if noise_keys is None else keys, **kw)()[0]
+    out = [None] * len(ys)
+    for g, sample in zip(groups, samples):
+        for j, i in enumerate(g):
+            x_hat = _synthesize(model, sample[j:j + 1], ys[i].size(1), norms[i], fused)
+            out[i] = x_hat if as_tensor else x_hat.cpu().numpy()
+    return out
+
+
 def enhance_waveform(model, y, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", z=None, VF_fn=None, device=None,
                      noise_keys=None, noise_seed=0, as_tensor=False):
     """One utterance, evaluate.py:107-136.  y: float tensor [1, samples].  Returns the enhanced waveform (numpy; with
     ``as_tensor`` the same values as a 1-D tensor left on the compute device).
     ``noise_keys`` ([key], see ``flowmse_amd.util.noise.utterance_key``) / ``noise_seed``: keyed prior noise."""
-    device = device or y.device
-    T_orig = y.size(1)
-    norm_factor = y.abs().max().item()
-    dm = model.data_module
-    fused = VF_fn is None and hasattr(dm, "fused_ok") and dm.fused_ok(y.to(device))
-    if fused:                      # STFT + compression + frame padding as one HIP kernel
-        Y = dm.analyze(y.to(device) / norm_factor)       # y / max|y| as the reference computes it (evaluate.py:111)
-    else:
-        y = y / norm_factor
-        Y = torch.unsqueeze(model._forward_transform(model._stft(y.to(device))), 0)
-        Y = pad_spec(Y)
-    sampler = get_white_box_solver(odesolver, model.ode, VF_fn if VF_fn is not None else model, Y=Y, Y_prior=Y,
-                                   T_rev=T_rev, t_eps=t_eps, N=N, z=z, noise_keys=noise_keys,
-                                   noise_seed=noise_seed)
-    sample, _ = sampler()
-    if fused:                      # decompression + iSTFT + rescale as one HIP kernel
-        x_hat = dm.synthesize(sample, T_orig, norm_factor).reshape(-1)
-    else:
-        x_hat = (model.to_audio(sample.squeeze(), T_orig) * norm_factor).reshape(-1)
-    return x_hat if as_tensor else x_hat.cpu().numpy()
+    return _enhance(model, [y], [[0]], None, N, T_rev, t_eps, odesolver, z, VF_fn, device, noise_keys, noise_seed,
+                    as_tensor)[0]
 
 
 def enhance_batch(model, ys, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", noise_keys=None, noise_seed=0, as_tensor=False):
@@ -86,20 +126,8 @@ def enhance_batch(model, ys, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", nois
     the same values as 1-D tensors left on the device).
     ``noise_keys`` (one key per utterance) / ``noise_seed``: keyed prior noise, which follows the utterance and not its
     row or batch."""
-    host = (lambda t: t.reshape(-1)) if as_tensor else (lambda t: t.squeeze().cpu().numpy())
-    norms = [y.abs().max().item() for y in ys]
-    dm = model.data_module
-    fused = hasattr(dm, "fused_ok") and all(dm.fused_ok(y) for y in ys)
-    if fused:                      # STFT + compression + frame padding: one HIP kernel per utterance
-        specs = [dm.analyze(y / n) for y, n in zip(ys, norms)]
-    else:
-        specs = [pad_spec(torch.unsqueeze(model._forward_transform(model._stft(y / n)), 0)) for y, n in zip(ys, norms)]
-    Y = torch.cat(specs, dim=0)
-    sample, _ = get_white_box_solver(odesolver, model.ode, model, Y=Y, Y_prior=Y, T_rev=T_rev, t_eps=t_eps, N=N,
-                                     noise_keys=noise_keys, noise_seed=noise_seed)()
-    if fused:                      # decompression + iSTFT + rescale: one HIP kernel per utterance
-        return [host(dm.synthesize(sample[i:i + 1], y.size(1), n)) for i, (y, n) in enumerate(zip(ys, norms))]
-    return [host(model.to_audio(sample[i, 0], y.size(1)) * n) for i, (y, n) in enumerate(zip(ys, norms))]
+    return _enhance(model, ys, [list(range(len(ys)))], None, N, T_rev, t_eps, odesolver, noise_keys=noise_keys,
+                    noise_seed=noise_seed, as_tensor=as_tensor)
 
 
 def enhance_concurrent(model, ys, lanes, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", groups=None, noise_keys=None,
@@ -112,27 +140,9 @@ def enhance_concurrent(model, ys, lanes, N=5, T_rev=1.0, t_eps=0.03, odesolver="
     utterance's latency goes up.  ys: list of float tensors [1, samples_i] on the target device.  Returns the list of
     numpy waveforms (with ``as_tensor``: 1-D device tensors), in the order of ``ys``.  ``noise_keys`` (one key per
     utterance, in the order of ``ys``) / ``noise_seed``: keyed prior noise."""
-    host = (lambda t: t.reshape(-1)) if as_tensor else (lambda t: t.squeeze().cpu().numpy())
-    norms = [y.abs().max().item() for y in ys]
-    dm = model.data_module
-    fused = hasattr(dm, "fused_ok") and all(dm.fused_ok(y) for y in ys)
-    if fused:                      # STFT + compression + frame padding: one HIP kernel per utterance
-        specs = [dm.analyze(y / n) for y, n in zip(ys, norms)]
-    else:
-        specs = [pad_spec(torch.unsqueeze(model._forward_transform(model._stft(y / n)), 0)) for y, n in zip(ys, norms)]
     groups = [[i] for i in range(len(ys))] if groups is None else [list(g) for g in groups]
-    Ys = [specs[g[0]] if len(g) == 1 else torch.cat([specs[i] for i in g], dim=0) for g in groups]
-    item_keys = None if noise_keys is None else [[noise_keys[i] for i in g] for g in groups]
-    samples, _ = get_white_box_solver_multi(odesolver, model.ode, model, Ys, T_rev=T_rev, t_eps=t_eps, N=N, lanes=lanes,
-                                            noise_keys=item_keys, noise_seed=noise_seed)()
-    out = [None] * len(ys)
-    for g, sample in zip(groups, samples):
-        for j, i in enumerate(g):
-            if fused:              # decompression + iSTFT + rescale: one HIP kernel per utterance
-                out[i] = host(dm.synthesize(sample[j:j + 1], ys[i].size(1), norms[i]))
-            else:
-                out[i] = host(model.to_audio(sample[j, 0], ys[i].size(1)) * norms[i])
-    return out
+    return _enhance(model, ys, groups, lanes, N, T_rev, t_eps, odesolver, noise_keys=noise_keys, noise_seed=noise_seed,
+                    as_tensor=as_tensor)
 
 
 def _write_wav(path, x, sr=16000):
@@ -435,71 +445,84 @@ def _enter_rank(args):
     return rank, world
 
 
-def _main_keyed(args, ap):
-    """Keyed-noise run, as one rank of ``--gpus N`` or in-process at ``--gpus 1``: the same plan and the same calls."""
-    import torch.distributed as dist
-    from flowmse_amd.parallel import gather_rows, plan_shards
-    from flowmse_amd.util.inference import keyed_valid_losses, validation_item
-    from flowmse_amd.util.noise import utterance_key
-    rank, world = _enter_rank(args)
-    seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(8), "little")
-    model, epoch = _load_model(args, ap)
+def plan_calls(noise, batch, streams, lens, world=1, rank=0):
+    """The sampler calls of rank ``rank`` of ``world`` in processing order; host only.  ``lens``: every file's padded frame
+    count.  A call is a list of groups, a group a list of file indices that are sampled as one equal-padded-length batch.
+    keyed: the batches of the WHOLE set, dealt to the ranks unsplit (batch composition does not depend on the world size).
+    torch: at ``batch > 1`` the files grouped by padded frame count, largest first; else the files in order.
+    ``streams > 1``: ``streams * _ITEMS_PER_LANE`` groups per (multi-lane) call; else one group per call."""
+    from flowmse_amd.parallel import batches_by_length, plan_shards
+    if noise == "keyed":
+        groups = [list(ids) for _, ids in plan_shards(lens, world, batch, level=False)[rank]]
+    elif batch > 1:
+        groups = [list(ids) for _, ids in batches_by_length(range(len(lens)), lens, batch)]
+    else:
+        groups = [[i] for i in range(len(lens))]
+    per_call = streams * _ITEMS_PER_LANE if streams > 1 else 1
+    return [groups[k:k + per_call] for k in range(0, len(groups), per_call)]
+
+
+def _sources(args):
+    """``(names, n_samples, load)`` of the run's files in sorted-filename order; ``load(i)`` -> (clean, noisy) as numpy.  The
+    lengths of files on disk come from their headers: the plan needs every length, a file is read when its call comes up."""
     if args.synthetic:
         pairs = _synthetic_pairs(args.synthetic, seconds=args.synthetic_seconds)
-        names = [p[0] for p in pairs]
-        n_samples = [p[2].shape[0] for p in pairs]
+        return [p[0] for p in pairs], [p[2].shape[0] for p in pairs], lambda i: (pairs[i][1], pairs[i][2])
+    clean_dir = os.path.join(args.test_dir, "test", "clean")
+    noisy_dir = os.path.join(args.test_dir, "test", "noisy")
+    names = [os.path.basename(f) for f in sorted(glob.glob(os.path.join(noisy_dir, "*.wav")))]
 
-        def load(i):
-            return pairs[i][1], pairs[i][2]
-    else:
-        clean_dir = os.path.join(args.test_dir, "test", "clean")
-        noisy_dir = os.path.join(args.test_dir, "test", "noisy")
-        names = [os.path.basename(f) for f in sorted(glob.glob(os.path.join(noisy_dir, "*.wav")))]
-        n_samples = [_num_samples(os.path.join(noisy_dir, n)) for n in names]     # headers only: the plan needs every length
+    def load(i):
+        return (_read_wav(os.path.join(clean_dir, names[i]))[0][0].numpy(),
+                _read_wav(os.path.join(noisy_dir, names[i]))[0][0].numpy())
 
-        def load(i):
-            return (_read_wav(os.path.join(clean_dir, names[i]))[0][0].numpy(),
-                    _read_wav(os.path.join(noisy_dir, names[i]))[0][0].numpy())
+    return names, [_num_samples(os.path.join(noisy_dir, n)) for n in names], load
 
+
+def _valid_losses(model, waves, names, seed, draws, batch, device):
+    """``--valid_loss`` of the files of one planned batch: ``waves`` their (clean, noisy) numpy pairs."""
+    from flowmse_amd.util.inference import keyed_valid_losses, validation_item
+    items = [validation_item(model, torch.from_numpy(x)[None].to(device), torch.from_numpy(y)[None].to(device))
+             for x, y in waves]
+    return keyed_valid_losses(model, items, names, seed=seed, draws=draws, batch=batch)
+
+
+def run_calls(args, model, epoch, names, n_samples, load, seed=None, rank=0, world=1, device="cuda"):
+    """The driver loop of both noise modes: ``plan_calls`` -> per call load, ``_enhance`` (utterance keys in keyed mode only),
+    metrics, ``--valid_loss``, one wav per file as its call completes -> rows gathered on rank 0, sorted by file index,
+    ``_write_reports``.  ``seed``: the keyed stream's seed, None in torch mode.  Returns the seconds the loop took."""
+    from flowmse_amd.parallel import gather_rows
+    from flowmse_amd.util.noise import utterance_key
+    keyed = args.noise == "keyed"
     target_dir = args.folder_destination.rstrip("/") + "/"
     os.makedirs(target_dir + "files/", exist_ok=True)
     pesq, stoi = _metric_fns()
-    kw = dict(N=args.N, T_rev=args.reverse_starting_point, t_eps=args.last_eval_point, odesolver=args.odesolver,
-              noise_seed=seed)
-    # the batches of the WHOLE set, dealt to the ranks unsplit: batch composition does not depend on the world size
-    batches = [ids for _, ids in plan_shards([_padded_frames(n) for n in n_samples], world, args.batch, level=False)[rank]]
-    per_call = args.streams * _ITEMS_PER_LANE if args.streams > 1 else 1
     on_device = args.metrics == "device"
+    lanes = args.streams if args.streams > 1 else None
+    calls = plan_calls(args.noise, args.batch, args.streams, [_padded_frames(n) for n in n_samples], world, rank)
     rows, t0 = [], time.time()
-    for k in range(0, len(batches), per_call):
-        chunk = batches[k:k + per_call]
-        flat = [i for g in chunk for i in g]
-        waves = {i: load(i) for i in flat}
-        ys = [torch.from_numpy(waves[i][1])[None].cuda() for i in flat]
-        keys = [utterance_key(names[i]) for i in flat]
-        if args.streams > 1:
-            pos = {i: j for j, i in enumerate(flat)}
-            outs = enhance_concurrent(model, ys, args.streams, groups=[[pos[i] for i in g] for g in chunk],
-                                      noise_keys=keys, as_tensor=on_device, **kw)
-        else:
-            outs = enhance_batch(model, ys, noise_keys=keys, as_tensor=on_device, **kw)
+    for call in calls:
+        flat = [i for g in call for i in g]
+        pos = {i: j for j, i in enumerate(flat)}
+        waves = [load(i) for i in flat]
+        ys = [torch.from_numpy(y)[None].to(device) for _, y in waves]
+        outs = _enhance(model, ys, [[pos[i] for i in g] for g in call], lanes, N=args.N, T_rev=args.reverse_starting_point,
+                        t_eps=args.last_eval_point, odesolver=args.odesolver,
+                        noise_keys=[utterance_key(names[i]) for i in flat] if keyed else None,
+                        noise_seed=seed if keyed else 0, as_tensor=on_device)
         if on_device:
-            metric_rows, outs = _metrics_device(pesq, [(waves[i][0], yd, x_hat) for i, yd, x_hat in zip(flat, ys, outs)])
+            metric_rows, outs = _metrics_device(pesq, [(x, yd, x_hat) for (x, _), yd, x_hat in zip(waves, ys, outs)])
         else:
-            metric_rows = [_metrics(pesq, stoi, waves[i][0], waves[i][1], x_hat) for i, x_hat in zip(flat, outs)]
+            metric_rows = [_metrics(pesq, stoi, x, y, x_hat) for (x, y), x_hat in zip(waves, outs)]
         if args.valid_loss:            # per planned batch, so that the rows of a call do not depend on --gpus or --streams
-            at = {i: j for j, i in enumerate(flat)}
-            for g in chunk:
-                items = [validation_item(model, torch.from_numpy(waves[i][0])[None].cuda(),
-                                         torch.from_numpy(waves[i][1])[None].cuda()) for i in g]
-                vl = keyed_valid_losses(model, items, [names[i] for i in g], seed=seed, draws=args.valid_loss,
-                                        batch=args.batch)
+            for g in call:
+                vl = _valid_losses(model, [waves[pos[i]] for i in g], [names[i] for i in g], seed, args.valid_loss,
+                                   args.batch, device)
                 for i, v in zip(g, vl):
-                    metric_rows[at[i]] = tuple(metric_rows[at[i]]) + (float(v),)
-        for i, x_hat, m in zip(flat, outs, metric_rows):
-            y = waves[i][1]
+                    metric_rows[pos[i]] = tuple(metric_rows[pos[i]]) + (float(v),)
+        for i, (_, y), x_hat, m in zip(flat, waves, outs, metric_rows):
             _write_wav(target_dir + "files/" + names[i], x_hat, 16000)
-            rows.append((i, names[i]) + m + (y.shape[0] // 128 + 1,))
+            rows.append((i, names[i]) + tuple(m) + (y.shape[0] // 128 + 1,))
     rows = gather_rows(rows)
     dt = time.time() - t0
     if rank == 0:
@@ -508,12 +531,9 @@ def _main_keyed(args, ap):
         columns = _COLUMNS + (("valid_loss",) if args.valid_loss else ())
         data = {c: [r[1 + j] for r in rows] for j, c in enumerate(columns)}
         _write_reports(target_dir, data, args, model, epoch, seed)
-        print(f"enhanced {len(names)} utterances ({sum(r[-1] for r in rows)} frames) in {dt:.2f} s on {world} GPU(s), "
-              f"keyed noise seed {seed} -> {target_dir}")
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    return 0
+        where = f" on {world} GPU(s), keyed noise seed {seed}" if keyed else ""
+        print(f"enhanced {len(names)} utterances ({sum(r[-1] for r in rows)} frames) in {dt:.2f} s{where} -> {target_dir}")
+    return dt
 
 
 def main(argv=None):
@@ -523,77 +543,20 @@ def main(argv=None):
         raise ValueError("N_mid should be 0.")          # evaluate.py:124-125
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:           # plain `python -m flowmse_amd.evaluate --gpus N`
         return _spawn_ranks(args, argv)
-    if args.noise == "keyed":
-        return _main_keyed(args, ap)
-
+    keyed = args.noise == "keyed"      # as one rank of ``--gpus N`` or in-process at ``--gpus 1``: the same plan, the same calls
+    rank, world = _enter_rank(args) if keyed else (0, 1)
+    seed = None
+    if keyed:
+        seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(8), "little")
     model, epoch = _load_model(args, ap)
-    if args.synthetic:
-        pairs = _synthetic_pairs(args.synthetic, seconds=args.synthetic_seconds)
-    else:
-        clean_dir = os.path.join(args.test_dir, "test", "clean")
-        noisy_dir = os.path.join(args.test_dir, "test", "noisy")
-        pairs = []
-        for f in sorted(glob.glob(os.path.join(noisy_dir, "*.wav"))):
-            name = os.path.basename(f)
-            pairs.append((name, _read_wav(os.path.join(clean_dir, name))[0][0].numpy(), _read_wav(f)[0][0].numpy()))
-
-    target_dir = args.folder_destination.rstrip("/") + "/"
-    os.makedirs(target_dir + "files/", exist_ok=True)
-    pesq, stoi = _metric_fns()
-    data = {c: [] for c in _COLUMNS}
-    sr = 16000
-    frames, t0 = 0, time.time()
-    from flowmse_amd.parallel import batches_by_length
-    enhanced = {}
-    on_device = args.metrics == "device"
-    metric_rows = {}                   # --metrics device: idx -> row, filled after each sampler call
-
-    def keep(ids, ys, outs):
-        if on_device:
-            rows, outs = _metrics_device(pesq, [(pairs[i][1], y, o) for i, y, o in zip(ids, ys, outs)], sr)
-            metric_rows.update(dict(zip(ids, rows)))
-        enhanced.update(dict(zip(ids, outs)))
-
-    if args.seed is not None:
+    names, n_samples, load = _sources(args)
+    if not keyed and args.seed is not None:
         torch.manual_seed(args.seed)
-    if args.streams > 1:               # utterances (or equal-length batches of them) dealt to concurrent lanes
-        lens = [_padded_frames(p[2].shape[0]) for p in pairs]
-        items = [ids for _, ids in batches_by_length(range(len(pairs)), lens, args.batch)] if args.batch > 1 \
-            else [[i] for i in range(len(pairs))]
-        per_call = args.streams * _ITEMS_PER_LANE
-        for k in range(0, len(items), per_call):
-            chunk = items[k:k + per_call]
-            flat = [i for g in chunk for i in g]
-            pos = {i: j for j, i in enumerate(flat)}
-            ys = [torch.from_numpy(pairs[i][2])[None].cuda() for i in flat]
-            outs = enhance_concurrent(model, ys, args.streams,
-                                      N=args.N, T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
-                                      odesolver=args.odesolver, groups=[[pos[i] for i in g] for g in chunk],
-                                      as_tensor=on_device)
-            keep(flat, ys, outs)
-    elif args.batch > 1:               # group by padded frame count, largest first
-        lens = [_padded_frames(p[2].shape[0]) for p in pairs]
-        for _, ids in batches_by_length(range(len(pairs)), lens, args.batch):
-            ys = [torch.from_numpy(pairs[i][2])[None].cuda() for i in ids]
-            outs = enhance_batch(model, ys, N=args.N,
-                                 T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
-                                 odesolver=args.odesolver, as_tensor=on_device)
-            keep(ids, ys, outs)
-    for idx, (name, x, y) in enumerate(pairs):
-        if idx not in enhanced:
-            yd = torch.from_numpy(y)[None].cuda()
-            keep([idx], [yd], [enhance_waveform(model, yd, N=args.N,
-                                                T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
-                                                odesolver=args.odesolver, as_tensor=on_device)])
-        x_hat = enhanced.pop(idx)
-        frames += y.shape[0] // 128 + 1
-        _write_wav(target_dir + "files/" + name, x_hat, sr)
-        for c, v in zip(_COLUMNS, (name,) + (metric_rows[idx] if on_device else _metrics(pesq, stoi, x, y, x_hat, sr))):
-            data[c].append(v)
-    dt = time.time() - t0
-
-    _write_reports(target_dir, data, args, model, epoch, None)
-    print(f"enhanced {len(pairs)} utterances ({frames} frames) in {dt:.2f} s -> {target_dir}")
+    run_calls(args, model, epoch, names, n_samples, load, seed, rank, world)
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
     return 0
 
 

@@ -97,6 +97,7 @@ def enhance_pooled(model, load, items, write, batch=8, chunk_frames=CHUNK_FRAMES
     ``noise_keys`` / ``noise_frame0``, copies of the sampled rows into the files' ``[C K,1,256,width]`` stacks.  Per
     finished file: one ``flowse_istft_decompress_stacks`` launch.  ``reserve(batch, 256, width)`` once per bucket.
     Returns ``dict(calls=, rows=, fillers=)``: sampler calls made, real rows and filler rows in them."""
+    from flowmse_amd.evaluate import _fused_ok
     from flowmse_amd.sampling import get_white_box_solver
     batch = int(batch)
     if not 1 <= batch <= MAX_BATCH:
@@ -121,7 +122,7 @@ def enhance_pooled(model, load, items, write, batch=8, chunk_frames=CHUNK_FRAMES
             if tuple(y.shape) != (int(C), int(L)) or y.dtype != torch.float32:
                 raise ValueError(f"enhance_pooled: {name}: load() returned {y.dtype} {tuple(y.shape)}, the plan has "
                                  f"float32 {(int(C), int(L))}")
-            if not (hasattr(dm, "fused_ok") and dm.fused_ok(y)):
+            if not _fused_ok(model, [y]):
                 raise RuntimeError("enhance_pooled needs the HIP spectrogram kernels: device tensors and the released STFT "
                                    "configuration (n_fft 510, hop 128, hann, 'exponent')")
             peak = y.abs().max().item()

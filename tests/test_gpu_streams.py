@@ -304,6 +304,21 @@ def test_white_box_solver_multi_routing(tiny, monkeypatch):
         assert torch.equal(g, get_white_box_solver("euler", tiny.ode, tiny, Y, N=4, z=z)()[0])
 
 
+def test_enhance_entries_share_one_core(full):
+    """One 1 s utterance (128 padded frames), N = 1, one key and seed: the three enhance entries give the same bytes, as
+    numpy and as a device tensor."""
+    import numpy as np
+    from flowmse_amd.evaluate import _synthetic_pairs, enhance_batch, enhance_concurrent, enhance_waveform
+    y = torch.from_numpy(_synthetic_pairs(1, seconds=1.0)[0][2])[None].cuda()
+    kw = dict(N=1, noise_keys=[0x912975D344AF26C6], noise_seed=0x1F2E3D4C5B6A7988)
+    one = enhance_waveform(full, y, **kw)
+    assert isinstance(one, np.ndarray) and one.shape == (16000,) and one.dtype == np.float32 and np.isfinite(one).all()
+    assert enhance_batch(full, [y], **kw)[0].tobytes() == one.tobytes()
+    assert enhance_concurrent(full, [y], 1, **kw)[0].tobytes() == one.tobytes()
+    t = enhance_batch(full, [y], as_tensor=True, **kw)[0]
+    assert t.is_cuda and t.dim() == 1 and t.cpu().numpy().tobytes() == one.tobytes()
+
+
 # ---------------------------------------------------------------------------------------------------- 10
 @pytest.mark.timeout(900)
 def test_evaluate_streams_writes_identical_files(tmp_path):
