@@ -19,6 +19,7 @@ FLOWSE_MAX_LEVELS = 8
 FLOWSE_MAX_ATTN = 4
 FLOWSE_MAX_LANES = 4
 FLOWSE_MAX_SPEC_ROWS = 64
+FLOWSE_MAX_DRAWS = 64
 FLOWSE_BYTES_WEIGHTS, FLOWSE_BYTES_OWNED = 0, 1
 FLOWSE_LOSS_MSE, FLOWSE_LOSS_MAE = 0, 1
 
@@ -85,6 +86,7 @@ SIGNATURES = {
     "flowse_istft_decompress_chunks": (_i, [_vp, _i, _i, _i, _f, _f, _fp, _i, _f, _vp]),
     "flowse_stft_compress_rows": (_i, [C.POINTER(flowse_spec_row), _i, _i, _vp, _f, _f, _vp]),
     "flowse_istft_decompress_stacks": (_i, [_vp, _i, _i, _i, _i, _f, _f, _fp, _i, _f, _vp]),
+    "flowse_istft_decompress_ensemble": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _i64, _f, _f, _fp, _i, _f, _fp, _vp]),
     "flowse_resample_num_taps": (_i, [_i, _i]),
     "flowse_resample_taps": (_i, [_i, _i, C.POINTER(_d), _i]),
     "flowse_resample_poly": (_i, [_fp, _i, _i, _i, _i, _fp, _i, _vp]),

@@ -479,6 +479,11 @@ int launch_istft_decompress_chunks(const float* chunks_c64, int K, int Tc, int h
 // the chunk synthesis for S stacks of one geometry in one launch: [S][K][256][Tc] -> [S][Lout]
 int launch_istft_decompress_stacks(const float* chunks_c64, int S, int K, int Tc, int hop, float factor, float exponent,
                                    float* out, int Lout, float scale_out, hipStream_t s);
+// the stack synthesis over D draws per stack: the mean of the draws' linear spectra -> [S][Lout], and (tracks != null,
+// D >= 2) the per-frame deviation and power tracks [S][2][Tg]; row of (s, d, k) = s stack_stride + d draw_stride + k
+int launch_istft_decompress_ensemble(const float* chunks_c64, int S, int D, int K, int Tc, int hop, int64_t stack_stride,
+                                     int64_t draw_stride, float factor, float exponent, float* out, int Lout,
+                                     float scale_out, float* tracks, hipStream_t s);
 // the R rows [R,1,256,Tw] of one sampler call from up to FLOWSE_MAX_SPEC_ROWS signals; `rows`: HOST table
 int launch_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, float* out_c64, float factor, float exponent,
                               hipStream_t s);

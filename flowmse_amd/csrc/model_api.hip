@@ -946,6 +946,18 @@ int flowse_istft_decompress_stacks(const void* chunks_c64, int S, int K, int Tc,
                                           scale_out, static_cast<hipStream_t>(stream));
 }
 
+int flowse_istft_decompress_ensemble(const void* chunks_c64, int S, int D, int K, int Tc, int hop, int64_t stack_stride,
+                                     int64_t draw_stride, float factor, float exponent, float* out, int Lout,
+                                     float scale_out, float* tracks, void* stream) {
+    if (!chunks_c64 || !out) {
+        set_error("flowse_istft_decompress_ensemble: null argument");
+        return ERR_ARG;
+    }
+    return launch_istft_decompress_ensemble(static_cast<const float*>(chunks_c64), S, D, K, Tc, hop, stack_stride,
+                                            draw_stride, factor, exponent, out, Lout, scale_out, tracks,
+                                            static_cast<hipStream_t>(stream));
+}
+
 int flowse_profile_begin(flowse_model* m, int mode) {
     if (!m || (mode != 0 && mode != 1)) {
         set_error("flowse_profile_begin: bad argument");

@@ -128,14 +128,59 @@ __device__ __forceinline__ float2 seam_frame(const float2* __restrict__ chunks, 
     return make_float2(a.x + w * (b.x - a.x), a.y + w * (b.y - a.y));
 }
 
+// spec_back: (|z| / factor)^(1/e) * exp(j arg z)
+__device__ __forceinline__ float2 spec_back_value(float2 z, float factor, float exponent) {
+    z.x /= factor;
+    z.y /= factor;
+    if (exponent != 1.f) {
+        const float mag = sqrtf(z.x * z.x + z.y * z.y);
+        const float s = mag > 0.f ? powf(mag, 1.f / exponent - 1.f) : 0.f;
+        z.x *= s;
+        z.y *= s;
+    }
+    return z;
+}
+
+// Where the rows of draw d of stack b lie: row b stack_rows + d draw_rows (+ chunk k), in rows of NBIN * Tc values.
+// One draw per stack is {1, 1.f, K, 0}.
+struct DrawLayout {
+    int D;
+    float inv_D;
+    int64_t stack_rows, draw_rows;
+};
+
+// The linear STFT value of draw d at (f, t): the seam rule on that draw's compressed rows, then spec_back.
+template <bool SEAM>
+__device__ __forceinline__ float2 draw_value(const float2* __restrict__ spec, int b, int d, int f, int t, int Tpad,
+                                             float factor, float exponent, int K, int Tc, int hop, const DrawLayout& lay) {
+    const float2 z = SEAM ? seam_frame(spec + (b * lay.stack_rows + d * lay.draw_rows) * NBIN * Tc, f, t, K, Tc, hop)
+                          : spec[((int64_t)b * NBIN + f) * Tpad + t];
+    return spec_back_value(z, factor, exponent);
+}
+
+// The mean over the draws, summed in the order d = 0 .. D-1 and multiplied by 1 / D.  D == 1: the draw itself (z * 1.f).
+template <bool SEAM>
+__device__ __forceinline__ float2 mean_value(const float2* __restrict__ spec, int b, int f, int t, int Tpad, float factor,
+                                             float exponent, int K, int Tc, int hop, const DrawLayout& lay) {
+    float2 m = draw_value<SEAM>(spec, b, 0, f, t, Tpad, factor, exponent, K, Tc, hop, lay);
+    for (int d = 1; d < lay.D; ++d) {
+        const float2 z = draw_value<SEAM>(spec, b, d, f, t, Tpad, factor, exponent, K, Tc, hop, lay);
+        m.x += z.x;
+        m.y += z.y;
+    }
+    return make_float2(m.x * lay.inv_D, m.y * lay.inv_D);
+}
+
 // grid (ceil(Lout / 128), B), 256 threads: sample = tid & 127, the two halves split the bins.
-// SEAM: `spec` is B chunk stacks as above, one after the other ([B][K][NBIN][Tc]; T == Tpad == Tg frames each; B == 1 for
-// the chunks of one recording); else [B][NBIN][Tpad].
+// SEAM: `spec` holds B chunk stacks as above, T == Tpad == Tg frames each, of lay.D draws each (DrawLayout; B == 1 and one
+// draw for the chunks of one recording); the frame that is transformed back is the mean of the draws' linear values.
+// else [B][NBIN][Tpad], one draw.
 template <bool SEAM>
 __global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __restrict__ spec, int T, int Tpad,
                                                                float factor, float exponent,
                                                                const float* __restrict__ tab, float* __restrict__ out,
-                                                               int Lout, float scale_out, int K, int Tc, int hop) {
+                                                               int Lout, float scale_out, int K, int Tc, int hop,
+                                                               const DrawLayout lay) {
     constexpr int NF = 5;                               // frames that can overlap a block of HOP samples
     __shared__ float2 Xs[NF][NBIN];
     __shared__ float ct[NFFT], st[NFFT], win[NFFT];
@@ -154,19 +199,7 @@ __global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __r
         const int fr = i / NBIN, f = i - fr * NBIN;
         const int t = t_lo + fr;
         float2 z = make_float2(0.f, 0.f);
-        if (t < T) {
-            z = SEAM ? seam_frame(spec + (int64_t)b * K * NBIN * Tc, f, t, K, Tc, hop)
-                     : spec[((int64_t)b * NBIN + f) * Tpad + t];
-            // spec_back: (|z| / factor)^(1/e) * exp(j arg z)
-            z.x /= factor;
-            z.y /= factor;
-            if (exponent != 1.f) {
-                const float mag = sqrtf(z.x * z.x + z.y * z.y);
-                const float s = mag > 0.f ? powf(mag, 1.f / exponent - 1.f) : 0.f;
-                z.x *= s;
-                z.y *= s;
-            }
-        }
+        if (t < T) z = mean_value<SEAM>(spec, b, f, t, Tpad, factor, exponent, K, Tc, hop, lay);
         Xs[fr][f] = z;
     }
     __syncthreads();
@@ -197,6 +230,42 @@ __global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __r
     if (half == 0 && n < Lout) {
         const float v = part[tid] + part[tid + 128];
         out[(int64_t)b * Lout + n] = env > 1e-11f ? v / env * scale_out : 0.f;
+    }
+}
+
+// Per-frame agreement tracks of an ensemble: grid (ceil(Tg / 64), S), 256 threads = 64 frames (lanes along t, the
+// contiguous axis of a row) x 4 quarters of the bins.  tracks [S][2][Tg]: dev[t] = sum_f sum_d |Z_d - M|^2 / (D - 1), then
+// pow[t] = sum_f |M|^2, with M the mean the iSTFT kernel transforms (the same mean_value).  Two passes over the draws per
+// (f, t): the mean first, the deviations from the finished mean second -- never sum |Z_d|^2 - D |M|^2, which finds a small
+// term by cancellation.  A thread sums its 64 bins in ascending order, the quarters are added in ascending order by one
+// thread: no atomics, the same bits on every call.
+__global__ __launch_bounds__(256) void ensemble_tracks_kernel(const float2* __restrict__ spec, int Tg, float factor,
+                                                              float exponent, float* __restrict__ tracks, int K, int Tc,
+                                                              int hop, const DrawLayout lay) {
+    __shared__ float sdev[4][64], spow[4][64];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int t = blockIdx.x * 64 + lane;
+    float dev = 0.f, pw = 0.f;
+    if (t < Tg) {
+        for (int f = q * 64; f < q * 64 + 64; ++f) {
+            const float2 m = mean_value<true>(spec, b, f, t, Tg, factor, exponent, K, Tc, hop, lay);
+            pw += m.x * m.x + m.y * m.y;
+            for (int d = 0; d < lay.D; ++d) {
+                const float2 z = draw_value<true>(spec, b, d, f, t, Tg, factor, exponent, K, Tc, hop, lay);
+                const float ex = z.x - m.x, ey = z.y - m.y;
+                dev += ex * ex + ey * ey;
+            }
+        }
+    }
+    sdev[q][lane] = dev;
+    spow[q][lane] = pw;
+    __syncthreads();
+    if (q == 0 && t < Tg) {
+        dev = ((sdev[0][lane] + sdev[1][lane]) + sdev[2][lane]) + sdev[3][lane];
+        pw = ((spow[0][lane] + spow[1][lane]) + spow[2][lane]) + spow[3][lane];
+        float* row = tracks + (int64_t)b * 2 * Tg;
+        row[t] = dev / (float)(lay.D - 1);
+        row[(int64_t)Tg + t] = pw;
     }
 }
 
@@ -249,38 +318,72 @@ int launch_istft_decompress(const float* spec_c64, int B, int T, int Tpad, float
     if (rc != OK) return rc;
     hipLaunchKernelGGL(istft_decompress_kernel<false>, dim3((Lout + HOP - 1) / HOP, B), dim3(256), 0, s,
                        reinterpret_cast<const float2*>(spec_c64), T, Tpad, factor, exponent, tab, out, Lout,
-                       scale_out, 0, 0, 0);
+                       scale_out, 0, 0, 0, DrawLayout{1, 1.f, 0, 0});
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }
 
-// S chunk stacks of one geometry, [S][K][NBIN][Tc] -> [S][Lout]; `who` names the entry in the error text
-static int launch_istft_stacks(const char* who, const float* chunks_c64, int S, int K, int Tc, int hop, float factor,
-                               float exponent, float* out, int Lout, float scale_out, hipStream_t s) {
+// S chunk stacks of one geometry and D draws each -> [S][Lout] (and the tracks [S][2][Tg] of the ensemble call); chunk k of
+// draw d of stack s is row s stack_rows + d draw_rows + k.  `who` names the entry in the error text
+static int launch_istft_stacks(const char* who, const float* chunks_c64, int S, int D, int K, int Tc, int hop,
+                               int64_t stack_rows, int64_t draw_rows, float factor, float exponent, float* out, int Lout,
+                               float scale_out, float* tracks, hipStream_t s) {
     const int64_t Tg = (int64_t)(K - 1) * hop + Tc;
     if (S < 1 || S > 65535 || !chunks_ok(K, Tc, hop) || Lout < 1 || Lout > (Tg - 1) * HOP + NFFT - PADC || factor == 0.f) {
         set_error("istft %s: need 1 <= hop <= Tc <= 2 hop, 1 <= K <= 65535, 1 <= S <= 65535, 1 <= Lout <= 128 (Tg - 1) + 255 "
                   "and factor != 0 (got S=%d K=%d Tc=%d hop=%d Lout=%d)", who, S, K, Tc, hop, Lout);
         return ERR_SHAPE;
     }
+    if (D < 1 || D > FLOWSE_MAX_DRAWS || (tracks && D == 1)) {
+        set_error("istft %s: need 1 <= D <= %d, and null tracks at D = 1 (got D=%d tracks=%s)", who, FLOWSE_MAX_DRAWS, D,
+                  tracks ? "given" : "null");
+        return ERR_SHAPE;
+    }
+    // no two of the S D K rows may coincide: the stacks apart by whole draw sets, or the draws apart by whole stack sets;
+    // the bounds keep every element offset far inside 64 bits
+    constexpr int64_t STRIDE_MAX = (int64_t)1 << 31;
+    const bool in_range = stack_rows >= 0 && draw_rows >= 0 && stack_rows <= STRIDE_MAX && draw_rows <= STRIDE_MAX;
+    const bool stack_major = (D == 1 || draw_rows >= K) && (S == 1 || stack_rows >= (D - 1) * draw_rows + K);
+    const bool draw_major = (S == 1 || stack_rows >= K) && (D == 1 || draw_rows >= (S - 1) * stack_rows + K);
+    if (!in_range || !(stack_major || draw_major) ||
+        ((S - 1) * stack_rows + (D - 1) * draw_rows + K) > ((int64_t)1 << 59) / ((int64_t)NBIN * Tc)) {
+        set_error("istft %s: rows s * stack_stride + d * draw_stride + k alias or leave the address range (got S=%d D=%d K=%d "
+                  "stack_stride=%lld draw_stride=%lld)", who, S, D, K, (long long)stack_rows, (long long)draw_rows);
+        return ERR_SHAPE;
+    }
     float* tab = nullptr;
     int rc = ensure_tables(&tab);
     if (rc != OK) return rc;
+    const DrawLayout lay{D, 1.f / (float)D, stack_rows, draw_rows};
     hipLaunchKernelGGL(istft_decompress_kernel<true>, dim3((Lout + HOP - 1) / HOP, S), dim3(256), 0, s,
                        reinterpret_cast<const float2*>(chunks_c64), (int)Tg, (int)Tg, factor, exponent, tab, out, Lout,
-                       scale_out, K, Tc, hop);
+                       scale_out, K, Tc, hop, lay);
     FLOWSE_LAUNCH_CHECK();
+    if (tracks) {
+        hipLaunchKernelGGL(ensemble_tracks_kernel, dim3((unsigned)((Tg + 63) / 64), S), dim3(256), 0, s,
+                           reinterpret_cast<const float2*>(chunks_c64), (int)Tg, factor, exponent, tracks, K, Tc, hop, lay);
+        FLOWSE_LAUNCH_CHECK();
+    }
     return OK;
 }
 
 int launch_istft_decompress_chunks(const float* chunks_c64, int K, int Tc, int hop, float factor, float exponent,
                                    float* out, int Lout, float scale_out, hipStream_t s) {
-    return launch_istft_stacks("chunks", chunks_c64, 1, K, Tc, hop, factor, exponent, out, Lout, scale_out, s);
+    return launch_istft_stacks("chunks", chunks_c64, 1, 1, K, Tc, hop, K, 0, factor, exponent, out, Lout, scale_out, nullptr,
+                               s);
 }
 
 int launch_istft_decompress_stacks(const float* chunks_c64, int S, int K, int Tc, int hop, float factor, float exponent,
                                    float* out, int Lout, float scale_out, hipStream_t s) {
-    return launch_istft_stacks("stacks", chunks_c64, S, K, Tc, hop, factor, exponent, out, Lout, scale_out, s);
+    return launch_istft_stacks("stacks", chunks_c64, S, 1, K, Tc, hop, K, 0, factor, exponent, out, Lout, scale_out, nullptr,
+                               s);
+}
+
+int launch_istft_decompress_ensemble(const float* chunks_c64, int S, int D, int K, int Tc, int hop, int64_t stack_stride,
+                                     int64_t draw_stride, float factor, float exponent, float* out, int Lout,
+                                     float scale_out, float* tracks, hipStream_t s) {
+    return launch_istft_stacks("ensemble", chunks_c64, S, D, K, Tc, hop, stack_stride, draw_stride, factor, exponent, out,
+                               Lout, scale_out, tracks, s);
 }
 
 int launch_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, float* out_c64, float factor, float exponent,

@@ -166,6 +166,39 @@ class SpecTransform:
                                                                _lib.ptr(out), length, float(scale), _lib.current_stream()))
         return out
 
+    def synthesize_ensemble(self, chunks, S, D, hop, length, scale=1.0, *, stack_stride=None, draw_stride=None, tracks=False,
+                            K=None):
+        """``synthesize_stacks`` over ``D`` draws per stack in one kernel (``flowmse_amd.ensemble`` has the definitions): the
+        waveform of the MEAN of the draws' linear spectra, each draw blended and decompressed on its own -> [S, length]; with
+        ``tracks`` also float32 [S, 2, Tg]: per frame the draws' deviation from the mean, then the mean's power.  Chunk k of
+        draw d of stack s is row ``s * stack_stride + d * draw_stride + k`` of ``chunks`` [rows, 1, 256, Tc]; the default is
+        the contiguous [S][D][K] layout (``stack_stride = D K``, ``draw_stride = K``).  ``K`` defaults to
+        ``rows // (S D)``; name it when the rows hold more than the S D K that are read.  ``D == 1`` is ``synthesize_stacks``
+        bit for bit and has no tracks."""
+        from flowmse_amd import _lib
+        chunks = chunks.contiguous()
+        S, D = int(S), int(D)
+        rows, _, F, Tc = chunks.shape
+        if S < 1 or D < 1 or (K is None and rows % (S * D)):
+            raise ValueError(f"synthesize_ensemble: {rows} chunk rows do not make {S} stacks of {D} draws")
+        K = rows // (S * D) if K is None else int(K)
+        if tracks and D < 2:
+            raise ValueError("synthesize_ensemble: the tracks need D >= 2 draws")
+        stack_stride = D * K if stack_stride is None else int(stack_stride)
+        draw_stride = K if draw_stride is None else int(draw_stride)
+        if K < 1 or min(stack_stride, draw_stride) < 0 or (S - 1) * stack_stride + (D - 1) * draw_stride + K > rows:
+            raise ValueError(f"synthesize_ensemble: S={S} D={D} K={K} stack_stride={stack_stride} draw_stride={draw_stride} "
+                             f"reads past the {rows} rows given")
+        out = torch.empty(S, length, dtype=torch.float32, device=chunks.device)
+        Tg = (K - 1) * int(hop) + Tc
+        tr = torch.empty(S, 2, Tg, dtype=torch.float32, device=chunks.device) if tracks else None
+        with torch.cuda.device(chunks.device):
+            _lib.check(_lib.lib.flowse_istft_decompress_ensemble(_lib.ptr(chunks), S, D, K, Tc, int(hop), stack_stride,
+                                                                 draw_stride, float(self.spec_factor),
+                                                                 float(self.spec_abs_exponent), _lib.ptr(out), length,
+                                                                 float(scale), _lib.ptr(tr), _lib.current_stream()))
+        return (out, tr) if tracks else out
+
     # ---- STFT pair ------------------------------------------------------------------------------
     def _stft_args(self, ref):
         return dict(n_fft=self.n_fft, hop_length=self.hop_length, window=self._win(ref), center=True)

@@ -3,7 +3,7 @@
 
     python -m flowmse_amd.enhance --input WAV_OR_DIR --output DIR --ckpt MODEL.ckpt [--N 5] [--batch 8]
                                   [--chunk_frames 256] [--overlap_frames 32] [--noise keyed|torch] [--seed S]
-                                  [--resample [--output_rate 16000|input]] [--pool [--channels first|all]]
+                                  [--resample [--output_rate 16000|input]] [--pool [--channels first|all] [--samples D]]
 
 Unlike ``flowmse_amd.evaluate`` it needs no clean files and reports no metrics.  Every recording goes through
 ``flowmse_amd.chunked.enhance_long``: one that fits a single chunk is enhanced exactly as ``evaluate`` would; a longer
@@ -35,8 +35,17 @@ only.  ``--channels all`` (needs ``--pool``) enhances every channel of a multi-c
 factor per file, and writes a file with the input's channel count; ``--channels first`` (default) reads channel 0, as ever.
 ``--synthetic_channels 1,2,...`` gives the synthetic signals that many channels (channel c > 0: an independent signal at
 half the level of channel 0).
+
+Ensembles.  ``--samples D`` (1..64, needs ``--pool``; ``flowmse_amd.ensemble``) samples every row ``D`` times under the keys
+``draw_key(channel_key, d)`` and writes the MEAN of the ``D`` draws, taken on the linear spectra on the device before the one
+inverse STFT (and before ``--output_rate input`` resamples back).  This is NOT the reference's computation, which draws once.
+``_ensemble.csv`` (``filename,channel,samples,agreement_db``) says per file and channel how far the draws agree -- the mean's
+power over the draws' deviation from it, in dB: high means the model is sure, around 0 dB or below the output is mostly the
+draw.  Draw 0 is the draw of a run without the flag, bit for bit, and ``--samples 1`` is that run.  A file's stack of sampled
+rows is ``D`` times as large (512 KB per chunk and draw at 256 frames).
 """
 import argparse
+import csv
 import glob
 import os
 import time
@@ -45,6 +54,7 @@ import types
 import torch
 
 from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, enhance_long, plan_chunks
+from flowmse_amd.ensemble import samples_arg
 from flowmse_amd.evaluate import _load_model, _seconds_arg, _synthetic_pairs, _write_wav
 from flowmse_amd.pooled import MAX_BATCH, enhance_pooled
 from flowmse_amd.resample import out_len, rational, resample
@@ -107,6 +117,10 @@ def build_parser():
     ap.add_argument("--channels", choices=("first", "all"), default="first",
                     help="first: enhance channel 0 of a multi-channel file (default). all: needs --pool; enhance every "
                          "channel independently and write a file with the input's channel count")
+    ap.add_argument("--samples", type=samples_arg, default=1, metavar="D",
+                    help="needs --pool. Sample every row D times (1..64) under independent keyed streams and write the mean of "
+                         "the draws, with _ensemble.csv: per file and channel the agreement of the draws in dB. Not the "
+                         "reference's computation (it draws once). 1 (default): one draw, the files written without the flag")
     ap.add_argument("--synthetic_channels", type=_channels_arg, default=[1],
                     help="channel counts of the --synthetic signals, a comma list cycled over them (default 1); channel "
                          "c > 0 is an independent signal at half the level of channel 0")
@@ -130,6 +144,8 @@ def parse_args(argv=None, ap=None):
         ap.error(str(e))
     if args.channels == "all" and not args.pool:
         ap.error("--channels all needs --pool")
+    if args.samples > 1 and not args.pool:
+        ap.error(f"--samples {args.samples} needs --pool (the unpooled path draws once)")
     if args.pool and args.noise != "keyed":
         ap.error("--pool --noise torch: pooling needs --noise keyed (the generator's draw order would depend on the folder)")
     if args.pool and args.batch > MAX_BATCH:
@@ -206,7 +222,7 @@ def run_pooled(model, args, names, rates, shapes, read, seed):
     """The ``--pool`` run: ``read(i)`` -> float32 [C, samples] on the host at ``rates[i]`` Hz, ``shapes[i]`` its (samples,
     channels).  Every file is moved to the device, brought to 16 kHz there (all channels in one launch), enhanced by
     ``enhance_pooled`` and written as it completes (``--output_rate input``: resampled back and trimmed first).  Returns
-    the real 16 kHz frames enhanced, channels counted."""
+    the real 16 kHz frames enhanced, channels counted.  ``--samples D > 1``: the mean of D draws, and ``_ensemble.csv``."""
     every = args.channels == "all"
     items = []
     for name, sr, (n, C) in zip(names, rates, shapes):
@@ -225,9 +241,18 @@ def run_pooled(model, args, names, rates, shapes, read, seed):
         x = x_hat.cpu().numpy()
         _write_wav(os.path.join(args.output, names[i]), x[0] if x.shape[0] == 1 else x.T, sr)
 
+    agree = {}
     enhance_pooled(model, load, items, write, batch=args.batch, chunk_frames=args.chunk_frames,
                    overlap_frames=args.overlap_frames, N=args.N, T_rev=args.reverse_starting_point,
-                   t_eps=args.last_eval_point, odesolver=args.odesolver, noise_seed=seed)
+                   t_eps=args.last_eval_point, odesolver=args.odesolver, noise_seed=seed, draws=tuple(range(args.samples)),
+                   agreement=agree.__setitem__)
+    if args.samples > 1:
+        with open(os.path.join(args.output, "_ensemble.csv"), "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(["filename", "channel", "samples", "agreement_db"])
+            for i, name in enumerate(names):
+                for c, db in enumerate(agree[i]):
+                    w.writerow([name, c, args.samples, db])
     return sum(C * (L // 128 + 1) for _, C, L in items)
 
 
@@ -270,6 +295,8 @@ def write_settings(out_dir, args, model, epoch, noise_seed, resampled=()):
         f.write(f"resample: {args.resample}\noutput_rate: {args.output_rate}\n")
         if args.pool:                                              # without the flag the file is what it always was
             f.write(f"pool: {args.pool}\nchannels: {args.channels}\n")
+        if getattr(args, "samples", 1) > 1:
+            f.write(f"samples: {args.samples}\n")
         for name, sr in resampled:
             f.write(f"resampled {name}: {sr} Hz\n")
         f.write(f"seed: {args.seed}\nnoise: {args.noise}\nnoise seed: {noise_seed}\n")

@@ -20,6 +20,9 @@ order (they depend on weights, utterance, seed, solver settings and ``--batch`` 
 ``--valid_loss K`` (keyed noise only) adds a ``valid_loss`` column: the flow-matching loss the model is trained on
 (reference ``VFModel._step``, model.py:130-143), on each file's 256-frame validation item, mean over K keyed draws.
 
+``--samples D`` (keyed noise only; ``flowmse_amd.ensemble``) samples every file ``D`` times and writes and scores the MEAN of
+the draws; an ``agreement_db`` column says how far the draws agree.  NOT the reference's computation, which draws once.
+
 Layout: the per-utterance recipe lives once, in ``_enhance`` (``enhance_waveform`` / ``enhance_batch`` / ``enhance_concurrent``
 are it with one group, one group of all, and lanes); ``plan_calls`` lists a run's sampler calls for either noise mode and
 ``run_calls`` is the one loop that turns them into wavs and rows.
@@ -34,6 +37,7 @@ import time
 import numpy as np
 import torch
 
+from flowmse_amd.ensemble import samples_arg
 from flowmse_amd.sampling import get_white_box_solver, get_white_box_solver_multi
 from flowmse_amd.util.other import pad_spec, read_wav as _read_wav
 
@@ -81,19 +85,30 @@ def _synthesize(model, sample, T_orig, norm_factor, fused):
 
 
 def _enhance(model, ys, groups, lanes=None, N=5, T_rev=1.0, t_eps=0.03, odesolver="euler", z=None, VF_fn=None, device=None,
-             noise_keys=None, noise_seed=0, as_tensor=False):
+             noise_keys=None, noise_seed=0, as_tensor=False, samples=1, agreement=None):
     """The per-utterance recipe (evaluate.py:107-136) for a list of utterances ``ys`` (float tensors [1, samples_i]):
     normalise by max|y| (one ``.item()`` each) -> analysis -> sampler -> synthesis.  ``groups``: lists of indices into
     ``ys``, each an equal-padded-length batch that is sampled as one item.  ``lanes`` None: one ``get_white_box_solver`` call
     per group, in order; an integer: ONE ``get_white_box_solver_multi`` call on that many lanes.  Either way the priors are
     drawn in the order of ``groups``.  ``noise_keys``: one key per utterance, in the order of ``ys``.  Returns the waveforms in
-    the order of ``ys``: numpy, or with ``as_tensor`` 1-D tensors left on the compute device."""
+    the order of ``ys``: numpy, or with ``as_tensor`` 1-D tensors left on the compute device.
+
+    ``samples`` D > 1 (``flowmse_amd.ensemble``): a group of g utterances is sampled as ONE item of g D rows ordered (draw,
+    utterance) -- the same ``Y`` rows repeated, keys ``draw_key(key_i, d)`` -- and every utterance is finished by one
+    ``synthesize_ensemble`` call over its D rows (``draw_stride = g``): the waveform returned is the mean of the draws.
+    ``agreement``: a list that receives ``(index into ys, agreement in dB)`` per utterance.  Keyed noise and the HIP
+    spectrogram kernels only."""
+    from flowmse_amd.ensemble import agreements
+    from flowmse_amd.util.noise import draw_key
+    D = int(samples)
     ys = [y.to(device or y.device) for y in ys]
     norms = [y.abs().max().item() for y in ys]
     fused = _fused_ok(model, ys, VF_fn)
+    if D > 1 and (noise_keys is None or z is not None or not fused):
+        raise ValueError("samples > 1 needs keyed noise (noise_keys, no explicit z) and the HIP spectrogram kernels")
     specs = [_analyze(model, y / n, fused) for y, n in zip(ys, norms)]     # y / max|y| as the reference computes it (evaluate.py:111)
-    Ys = [specs[g[0]] if len(g) == 1 else torch.cat([specs[i] for i in g], dim=0) for g in groups]
-    keys = [None if noise_keys is None else [noise_keys[i] for i in g] for g in groups]
+    Ys = [specs[g[0]] if len(g) * D == 1 else torch.cat([specs[i] for i in g] * D, dim=0) for g in groups]
+    keys = [None if noise_keys is None else [draw_key(noise_keys[i], d) for d in range(D) for i in g] for g in groups]
     field = VF_fn if VF_fn is not None else model
     kw = dict(T_rev=T_rev, t_eps=t_eps, N=N, noise_seed=noise_seed)
     if lanes is None:
@@ -105,7 +120,15 @@ def _enhance(model, ys, groups, lanes=None, N=5, T_rev=1.0, t_eps=0.03, odesolve
     out = [None] * len(ys)
     for g, sample in zip(groups, samples):
         for j, i in enumerate(g):
-            x_hat = _synthesize(model, sample[j:j + 1], ys[i].size(1), norms[i], fused)
+            if D == 1:
+                x_hat = _synthesize(model, sample[j:j + 1], ys[i].size(1), norms[i], fused)
+            else:                  # rows j, j + g, ...: the D draws of utterance i, a one-chunk stack each
+                x_hat, tracks = model.data_module.synthesize_ensemble(
+                    sample[j:j + (D - 1) * len(g) + 1], 1, D, sample.shape[3], ys[i].size(1), norms[i], draw_stride=len(g),
+                    K=1, tracks=True)
+                x_hat = x_hat.reshape(-1)
+                if agreement is not None:
+                    agreement.append((i, agreements(tracks, ys[i].size(1))[0]))
             out[i] = x_hat if as_tensor else x_hat.cpu().numpy()
     return out
 
@@ -182,6 +205,7 @@ def _synthetic_pairs(n, seconds=2.0, sr=16000, seed=0):
     return out
 
 
+MAX_ROWS = 64                    # rows of one sampler call that --batch x --samples may ask for
 MAX_STREAMS = 4                  # FLOWSE_MAX_LANES of the library: one stream per lane, four hardware queues per process
 _ITEMS_PER_LANE = 4              # sampler items per lane and multi-lane call (bounds the spectrograms held on the device)
 
@@ -245,6 +269,13 @@ def build_parser():
                     help="also score every file's validation item (centre crop / pad to 256 frames, as the reference's "
                          "validation set builds it) with the flow-matching loss the model is trained on: a valid_loss column "
                          "with the mean over K keyed draws of (t, z). Needs --noise keyed. 0 = off")
+    ap.add_argument("--samples", type=samples_arg, default=1, metavar="D",
+                    help="sample every file D times under independent keyed streams (draw d of a file uses draw_key(key, d)) "
+                         "and write and score the MEAN of the draws; the CSV gains an agreement_db column (the mean's power "
+                         "over the draws' deviation from it: high = the draws agree). Needs keyed noise (selected when --noise "
+                         "is not given) and --batch x D <= 64. Not the reference's computation (it draws once). D > 1 makes "
+                         "the sampler call D times as wide, and widths select different kernels: draw 0 inside an ensemble "
+                         "equals the single-draw output to rounding only here (bit for bit under enhance --pool). 1 = off")
     ap.add_argument("--gpus", type=int, default=1,
                     help="shard the test set over this many GPUs of this node, one process each (keyed noise only)")
     return ap
@@ -260,8 +291,12 @@ def parse_args(argv=None, ap=None):
         ap.error(f"--batch must be >= 1, got {args.batch}")
     if args.gpus > 1 and args.noise == "torch":
         ap.error("--gpus > 1 needs --noise keyed: a single host random stream has no meaning across ranks")
+    if args.samples > 1 and args.noise == "torch":
+        ap.error(f"--samples {args.samples} needs --noise keyed: the draws are independent streams of the keyed noise")
+    if args.samples > 1 and args.batch * args.samples > MAX_ROWS:    # one draw: --batch is as free as it always was
+        ap.error(f"--batch x --samples must be <= {MAX_ROWS} (the rows of one sampler call), got {args.batch} x {args.samples}")
     if args.noise is None:
-        args.noise = "keyed" if args.gpus > 1 else "torch"
+        args.noise = "keyed" if args.gpus > 1 or args.samples > 1 else "torch"
     if args.valid_loss < 0:
         ap.error(f"--valid_loss must be >= 0, got {args.valid_loss}")
     if args.valid_loss and args.noise != "keyed":
@@ -367,6 +402,8 @@ def _write_reports(target_dir, data, args, model, epoch, noise_seed):
         if "valid_loss" in data:                                   # --valid_loss only: the other files are unchanged
             a = np.asarray(data["valid_loss"], dtype=np.float64)
             f.write(f"valid_loss: {a.mean():.6g} ± {a.std():.6g} \n")
+        if "agreement_db" in data:                                 # --samples D > 1 only
+            f.write("Agreement: {} \n".format(mean_std(data["agreement_db"])))
     with open(os.path.join(target_dir, "_settings.txt"), "w") as f:
         f.write(f"epoch: {epoch}\ncheckpoint file: {args.ckpt}\nodesolver_type: {args.odesolver_type}\n")
         f.write(f"odesolver: {args.odesolver}\nReverse starting point: {args.reverse_starting_point}\n")
@@ -379,6 +416,8 @@ def _write_reports(target_dir, data, args, model, epoch, noise_seed):
             f.write("metrics: device\n")
         if getattr(args, "valid_loss", 0):
             f.write(f"valid_loss draws: {args.valid_loss}\n")
+        if getattr(args, "samples", 1) > 1:
+            f.write(f"samples: {args.samples}\n")
 
 
 _COLUMNS = ("filename", "pesq", "estoi", "si_sdr", "si_sir", "si_sar")
@@ -506,10 +545,12 @@ def run_calls(args, model, epoch, names, n_samples, load, seed=None, rank=0, wor
         pos = {i: j for j, i in enumerate(flat)}
         waves = [load(i) for i in flat]
         ys = [torch.from_numpy(y)[None].to(device) for _, y in waves]
+        agree = []
         outs = _enhance(model, ys, [[pos[i] for i in g] for g in call], lanes, N=args.N, T_rev=args.reverse_starting_point,
                         t_eps=args.last_eval_point, odesolver=args.odesolver,
                         noise_keys=[utterance_key(names[i]) for i in flat] if keyed else None,
-                        noise_seed=seed if keyed else 0, as_tensor=on_device)
+                        noise_seed=seed if keyed else 0, as_tensor=on_device,
+                        **(dict(samples=args.samples, agreement=agree) if args.samples > 1 else {}))
         if on_device:
             metric_rows, outs = _metrics_device(pesq, [(x, yd, x_hat) for (x, _), yd, x_hat in zip(waves, ys, outs)])
         else:
@@ -520,6 +561,8 @@ def run_calls(args, model, epoch, names, n_samples, load, seed=None, rank=0, wor
                                    args.batch, device)
                 for i, v in zip(g, vl):
                     metric_rows[pos[i]] = tuple(metric_rows[pos[i]]) + (float(v),)
+        for j, db in agree:                                        # --samples D > 1: the last column
+            metric_rows[j] = tuple(metric_rows[j]) + (float(db),)
         for i, (_, y), x_hat, m in zip(flat, waves, outs, metric_rows):
             _write_wav(target_dir + "files/" + names[i], x_hat, 16000)
             rows.append((i, names[i]) + tuple(m) + (y.shape[0] // 128 + 1,))
@@ -528,7 +571,7 @@ def run_calls(args, model, epoch, names, n_samples, load, seed=None, rank=0, wor
     if rank == 0:
         rows.sort(key=lambda r: r[0])                              # the global sorted-filename order
         assert [r[0] for r in rows] == list(range(len(names))), "every utterance exactly once"
-        columns = _COLUMNS + (("valid_loss",) if args.valid_loss else ())
+        columns = _COLUMNS + (("valid_loss",) if args.valid_loss else ()) + (("agreement_db",) if args.samples > 1 else ())
         data = {c: [r[1 + j] for r in rows] for j, c in enumerate(columns)}
         _write_reports(target_dir, data, args, model, epoch, seed)
         where = f" on {world} GPU(s), keyed noise seed {seed}" if keyed else ""

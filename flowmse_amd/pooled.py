@@ -23,6 +23,11 @@ Rules (``plan_pool``), all fixed:
 Noise is keyed only: row (file, channel c, chunk k) uses ``channel_key(name, c)`` at the absolute frame ``k hop``, so channel 0
 of a file draws what the unpooled path draws for it.  A file is normalised by ONE factor, ``max|y|`` over all its channels,
 which keeps the level balance between them.
+
+Ensembles (``draws``, ``flowmse_amd.ensemble``; ``enhance --pool --samples D``): the draw is a fourth row coordinate.  A file's
+rows are ordered (channel, draw, chunk), row (file, c, draw d, k) uses ``draw_key(channel_key(name, c), d)`` at the same
+``frame0``, and the file is finished by ONE ``flowse_istft_decompress_ensemble`` launch that writes the mean of its draws.
+``draws=(0,)`` is the plan, the code path and the bytes of a run without the argument.
 """
 import collections
 
@@ -30,11 +35,12 @@ import torch
 
 from flowmse_amd._lib import FLOWSE_MAX_SPEC_ROWS as MAX_BATCH    # the rows one flowse_stft_compress_rows launch builds
 from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, plan_chunks
+from flowmse_amd.ensemble import agreements, check_draws, draw_keys
 from flowmse_amd.util.noise import utterance_key
 
 HOP = 128                        # samples per frame the plan counts in; enhance_pooled checks the data module's against it
 
-Row = collections.namedtuple("Row", "item channel chunk frame0 filler")
+Row = collections.namedtuple("Row", "item channel chunk frame0 filler draw", defaults=(0,))
 Call = collections.namedtuple("Call", "width rows")
 
 
@@ -58,11 +64,13 @@ def file_geometry(L, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES):
     return 1, width, width
 
 
-def plan_pool(items, batch, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES):
+def plan_pool(items, batch, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES, draws=(0,)):
     """The sampler calls of a run, by the rules of the module docstring.  ``items``: list of ``(name, channels, L)``; host
     only.  Returns a list of ``Call(width, rows)`` with ``rows`` a list of exactly ``batch``
-    ``Row(item, channel, chunk, frame0, filler)``, ``item`` the index into ``items``."""
+    ``Row(item, channel, chunk, frame0, filler, draw)``, ``item`` the index into ``items``.  ``draws``: distinct draw
+    indices ``>= 0``; every (channel, chunk) of a file becomes one row per draw, ordered (channel, draw, chunk)."""
     batch = int(batch)
+    draws = check_draws(draws)
     if batch < 1:
         raise ValueError(f"plan_pool: batch must be >= 1, got {batch}")
     plan_chunks(1, Tc, To)                               # the geometry's own checks, before any file is looked at
@@ -72,7 +80,7 @@ def plan_pool(items, batch, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES):
             raise ValueError(f"plan_pool: {name}: need >= 1 channel and >= {2 * HOP} samples, got {channels} x {L}")
         K, hop, width = file_geometry(L, Tc, To)
         rows = buckets.setdefault(width, [])
-        rows.extend(Row(i, c, k, k * hop, False) for c in range(int(channels)) for k in range(K))
+        rows.extend(Row(i, c, k, k * hop, False, d) for c in range(int(channels)) for d in draws for k in range(K))
     calls = []
     for width in sorted(buckets):
         rows = buckets[width]
@@ -84,7 +92,7 @@ def plan_pool(items, batch, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES):
 
 
 def enhance_pooled(model, load, items, write, batch=8, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES, N=5,
-                   T_rev=1.0, t_eps=0.03, odesolver="euler", noise_seed=0):
+                   T_rev=1.0, t_eps=0.03, odesolver="euler", noise_seed=0, draws=(0,), agreement=None):
     """Run ``plan_pool(items, batch, chunk_frames, overlap_frames)`` on the HIP-backed ``model``.
 
     ``items``: list of ``(name, channels, L)``.  ``load(i)`` -> float32 tensor ``[channels, L]`` on the model's device,
@@ -96,16 +104,26 @@ def enhance_pooled(model, load, items, write, batch=8, chunk_frames=CHUNK_FRAMES
     gives).  Per call: one ``flowse_stft_compress_rows`` launch, the unchanged ``get_white_box_solver`` with per-row
     ``noise_keys`` / ``noise_frame0``, copies of the sampled rows into the files' ``[C K,1,256,width]`` stacks.  Per
     finished file: one ``flowse_istft_decompress_stacks`` launch.  ``reserve(batch, 256, width)`` once per bucket.
-    Returns ``dict(calls=, rows=, fillers=)``: sampler calls made, real rows and filler rows in them."""
+    Returns ``dict(calls=, rows=, fillers=)``: sampler calls made, real rows and filler rows in them.
+
+    ``draws`` (distinct draw indices, ``flowmse_amd.ensemble``): every row is sampled once per draw under
+    ``draw_key(channel_key, d)``, the stack is ``[C D K,1,256,width]`` and ``write`` takes the MEAN of the draws, formed by one
+    ``flowse_istft_decompress_ensemble`` launch per finished file.  With two or more draws ``agreement(i, [dB per channel])``
+    (optional) is called before ``write(i, ...)``, from one read-back of the file's tracks.  Every call still has exactly
+    ``batch`` rows, so by the fixed-width property above the rows of draw ``d`` are bit-identical whatever other draws are
+    in the run: ``draws=(0, 1, 2)`` samples exactly the rows of the three runs ``draws=(d,)``, and only the finish differs.
+    ``draws=(0,)`` is the run without the argument: same calls, same launches, same bytes."""
     from flowmse_amd.evaluate import _fused_ok
     from flowmse_amd.sampling import get_white_box_solver
     batch = int(batch)
     if not 1 <= batch <= MAX_BATCH:
         raise ValueError(f"enhance_pooled: batch must be 1..{MAX_BATCH} (the rows of one spectrogram launch), got {batch}")
-    calls = plan_pool(items, batch, chunk_frames, overlap_frames)
+    draws = check_draws(draws)
+    D, dpos = len(draws), {d: j for j, d in enumerate(draws)}
+    calls = plan_pool(items, batch, chunk_frames, overlap_frames, draws)
     geometry = [file_geometry(L, chunk_frames, overlap_frames) for _, _, L in items]
-    keys = [[channel_key(name, c) for c in range(int(C))] for name, C, _ in items]
-    left = [int(C) * g[0] for (_, C, _), g in zip(items, geometry)]         # rows still to come, per file
+    keys = [[draw_keys(channel_key(name, c), draws) for c in range(int(C))] for name, C, _ in items]
+    left = [int(C) * D * g[0] for (_, C, _), g in zip(items, geometry)]         # rows still to come, per file
     n_rows = sum(left)
     dm = model.data_module
     if getattr(dm, "hop_length", None) != HOP:
@@ -127,7 +145,7 @@ def enhance_pooled(model, load, items, write, batch=8, chunk_frames=CHUNK_FRAMES
                                    "configuration (n_fft 510, hop 128, hann, 'exponent')")
             peak = y.abs().max().item()
             K = geometry[row.item][0]
-            stack = torch.empty(int(C) * K, 1, 256, call.width, dtype=torch.complex64, device=y.device)
+            stack = torch.empty(int(C) * D * K, 1, 256, call.width, dtype=torch.complex64, device=y.device)
             opened[row.item] = ((y / peak).contiguous(), peak, stack)
         device = opened[call.rows[0].item][0].device
         if call.width != width:
@@ -136,7 +154,7 @@ def enhance_pooled(model, load, items, write, batch=8, chunk_frames=CHUNK_FRAMES
                 model.dnn.reserve(batch, 256, width)
         Y = dm.analyze_rows([(opened[r.item][0][r.channel], r.frame0, 1.0) for r in call.rows], width)
         sample = get_white_box_solver(odesolver, model.ode, model, Y=Y, Y_prior=Y, T_rev=T_rev, t_eps=t_eps, N=N,
-                                      noise_keys=[keys[r.item][r.channel] for r in call.rows], noise_seed=noise_seed,
+                                      noise_keys=[keys[r.item][r.channel][dpos[r.draw]] for r in call.rows], noise_seed=noise_seed,
                                       noise_frame0=[r.frame0 for r in call.rows])()[0]
         real = [r for r in call.rows if not r.filler]
         r0 = 0
@@ -146,12 +164,19 @@ def enhance_pooled(model, load, items, write, batch=8, chunk_frames=CHUNK_FRAMES
             while r1 < len(real) and real[r1].item == i:
                 r1 += 1
             K = geometry[i][0]
-            s0 = real[r0].channel * K + real[r0].chunk                      # (channel, chunk) order: consecutive in the stack
+            # (channel, draw, chunk) order: consecutive in the stack
+            s0 = (real[r0].channel * D + dpos[real[r0].draw]) * K + real[r0].chunk
             opened[i][2][s0:s0 + r1 - r0].copy_(sample[r0:r1])
             left[i] -= r1 - r0
             if left[i] == 0:
                 _, peak, stack = opened.pop(i)
                 _, C, L = items[i]
-                write(i, dm.synthesize_stacks(stack, int(C), geometry[i][1], int(L), peak))
+                if D == 1:
+                    write(i, dm.synthesize_stacks(stack, int(C), geometry[i][1], int(L), peak))
+                else:
+                    x_hat, tracks = dm.synthesize_ensemble(stack, int(C), D, geometry[i][1], int(L), peak, tracks=True)
+                    if agreement is not None:
+                        agreement(i, agreements(tracks, int(L)))
+                    write(i, x_hat)
             r0 = r1
     return dict(calls=len(calls), rows=n_rows, fillers=len(calls) * batch - n_rows)

@@ -333,6 +333,28 @@ int flowse_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, void* 
 int flowse_istft_decompress_stacks(const void* chunks_c64, int S, int K, int Tc, int hop, float factor, float exponent,
                                    float* out, int Lout, float scale_out, void* stream);
 
+/* ---- ensembles of draws (opt-in: flowmse_amd.ensemble, `--samples D`; NOT the reference's computation, which draws once)
+ * flowse_istft_decompress_ensemble: flowse_istft_decompress_stacks over D draws per stack.  Chunk k of draw d of stack s is
+ * row s * stack_stride + d * draw_stride + k of chunks_c64 (rows of 256 * Tc complex64 values; offsets in 64 bits).  The
+ * linear spectrum of a draw is Z_d = spec_back(seam rule on the draw's compressed rows): the blend is done per draw, before
+ * the decompression.  The call transforms the mean M = (1 / D) sum_d Z_d, summed in fp32 in the order d = 0 .. D - 1:
+ *   out [S][Lout] = istft(M, Lout) * scale_out, over all Tg frames, formed by the code of the stacks call; D = 1 with
+ *   stack_stride = K gives that call's output bit for bit (z * 1 is exact).
+ *   tracks (may be null; must be null for D = 1): float32 [S][2][Tg], for every frame t of the Tg
+ *     tracks[s][0][t] = dev[t] = sum_f sum_d |Z_d[f,t] - M[f,t]|^2 / (D - 1)      (256 bins)
+ *     tracks[s][1][t] = pow[t] = sum_f |M[f,t]|^2
+ *   The deviations are taken from the finished mean in a second pass over the draws (never sum |Z_d|^2 - D |M|^2), each
+ *   sum in a fixed order without atomics: two calls give the same bits.
+ * Two layouts in one signature: stacks [S][D][K] have stack_stride = D K, draw_stride = K; rows ordered (draw, stack) with
+ * K = 1 have stack_stride = 1, draw_stride = S.  D outside 1..FLOWSE_MAX_DRAWS, tracks given at D = 1, negative strides,
+ * strides under which two of the S D K rows coincide, or the shape errors of the stacks call -> FLOWSE_ERR_SHAPE with the
+ * values in flowse_last_error(); null chunks or out -> FLOWSE_ERR_ARG; either is answered before any device call.  The call
+ * allocates nothing and does not synchronise. */
+#define FLOWSE_MAX_DRAWS 64
+int flowse_istft_decompress_ensemble(const void* chunks_c64, int S, int D, int K, int Tc, int hop, int64_t stack_stride,
+                                     int64_t draw_stride, float factor, float exponent, float* out, int Lout,
+                                     float scale_out, float* tracks, void* stream);
+
 /* ---- sample-rate conversion ahead of the STFT and after the iSTFT (opt-in; the reference reads 16 kHz files only) ----
  * Rational-ratio polyphase FIR resampling, zero phase, defined as what scipy.signal.resample_poly(x, up, down) computes
  * with its defaults (window ("kaiser", 5.0), padtype "constant"):
