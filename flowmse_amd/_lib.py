@@ -108,6 +108,7 @@ SIGNATURES = {
     "flowse_op_conv2d_16_ex": (_i, [_fp, _i, _fp, _i, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _i, _i, _f, _i,
                                    _vp, _i64, _vp]),
     "flowse_op_last_conv_route": (C.c_char_p, []),
+    "flowse_op_conv_route": (_i, [_i] * 10 + [C.c_char_p, _i]),
     "flowse_op_resblock_tail_16": (_i, [_fp, _i, _fp, _fp, _fp, _i, _fp, _fp, _fp, _i, _fp, _i, _fp, _fp, _fp, _i, _i, _i, _i, _f,
                                        _i, _vp, _i64, _vp]),
     "flowse_op_pc16_channel_blocks": (_i, [_i]),

@@ -259,11 +259,11 @@ struct ConvArgs {
     const float* bias_x = nullptr;      // [Cout] or null
     // fused GroupNorm statistics of the OUTPUT (optional): per-(sample, pixel tile, channel) sum / sum of squares
     // written to stats[((b * stats_nblk + tile) * Cout + c) * 2 + {0,1}], the layout gn_finalize consumes.
-    // Only honoured when H*W % 128 == 0 and ksplit == 1 (see conv_fused_stats_blocks).
+    // stats_nblk must be the geometry of the kernel that runs (ConvRoute::stats_nblk).
     float* stats = nullptr;
     int stats_nblk = 0;
-    // fused GroupNorm(+SiLU) on the INPUT (optional; only the halo-tile 3x3 kernel applies it, see
-    // conv_supports_fused_gn): A = act((x - mean[b][c]) * scale[b][c] + beta[c]) with c the concat channel index
+    // fused GroupNorm(+SiLU) on the INPUT (optional; only the halo-tile 3x3 kernels apply it, see
+    // ConvRoute::gn_on_load): A = act((x - mean[b][c]) * scale[b][c] + beta[c]) with c the concat channel index
     GnParams gn = {nullptr, nullptr, nullptr};
     int gn_silu = 0;
     // optional bf16 matrix-core path for the halo 3x3 kernel (Cout % 128 == 0): weights pre-split into bf16
@@ -284,10 +284,10 @@ struct ConvArgs {
     int SC1 = 0, SC2 = 0;
     const void* wfrag_sc = nullptr;
     // optional F(4,3) Winograd weights of a 3x3 conv in MFMA fragment order (launch_f43_weights): when set and the
-    // shape qualifies (conv_supports_wino) the fp32 3x3 runs the Winograd kernel (18 transformed taps per channel pair)
+    // shape qualifies (conv_route) the fp32 3x3 runs the Winograd kernel (18 transformed taps per channel pair)
     const float* wino = nullptr;
     // optional F(4,3) x F(2,3) two-dimensional Winograd weights (launch_w2d_weights, 24 transformed taps per channel pair):
-    // when set and the shape qualifies (conv_supports_w2d) the fp32 3x3 runs conv3x3_w2d_kernel -- its fused statistics
+    // when set and the shape qualifies (conv_route) the fp32 3x3 runs conv3x3_w2d_kernel -- its fused statistics
     // come in blocks of 64 pixels (4 x 16 strips: stats_nblk = H W / 64, set by the plan, Builder::conv)
     const float* wino2 = nullptr;
     // optional copy of `w` in MFMA fragment order (launch_smallm_weights): when set and the shape qualifies
@@ -301,15 +301,11 @@ struct ConvArgs {
     // (attention output projection) and the split-K reductions.
     int in_dt = DT_F32, out_dt = DT_F32;
 };
-// K slices of the 16-bit flat kernel for a shape (its own policy: no Winograd alternative, two K steps per stage)
-int conv16_ksplit(int B, int H, int W, int Cin, int Cout, int taps);
-// true when a 3x3 conv with 16-bit operands runs the LDS-halo kernel (fused GroupNorm input possible, statistics of the
-// output fused, H*W/128 partial blocks); otherwise the flat 16-bit kernel (+ split-K) takes it
+// shapes the 16-bit LDS-halo 3x3 kernels take (fused GroupNorm input possible, statistics of the output fused, H*W/128
+// partial blocks): their tiling applies and fills the chip
 bool conv16_uses_halo(int B, int H, int W, int C1, int C2, int Cout, int taps);
 void pc16_set_channel_blocks(int mode);                                           // flowse_op_pc16_channel_blocks
 bool conv16_uses_pc(int B, int H, int W, int C1, int C2, int Cout, int taps);     // ... and the producer / consumer form of it (needs ConvArgs::wfrag)
-// number of per-sample partial-statistics blocks the 16-bit conv path writes for this shape (0 = none)
-int conv16_stats_blocks(int B, int H, int W, int Cin, int Cout, int taps);
 // elementwise storage conversion (n elements, n % 4 == 0)
 int launch_convert(const void* src, int src_dt, void* dst, int dst_dt, int64_t n, hipStream_t s);
 // F(4,3) Winograd weight transform along the kernel's vertical axis, packed [Cout][9][Cin] -> fragment order, on device
@@ -323,10 +319,8 @@ inline int64_t conv_wino_numel(int Cout, int Cin) { return (int64_t)Cout * 18 * 
 // F(4,3) x F(2,3) weight transform, packed [Cout][9][Cin] -> fragment order [Cout/32][h][Cin/32][6][4][64][4], on device
 int launch_w2d_weights(const float* w_packed, int Cout, int Cin, float* out, hipStream_t s);
 inline int64_t conv_w2d_numel(int Cout, int Cin) { return (int64_t)Cout * 24 * Cin; }
-// conv_w2d_shape_ok: the two-dimensional Winograd kernel can run this shape (launch_conv takes it whenever
-// ConvArgs::wino2 is set); conv_supports_w2d: ... and the policy wants it (enough blocks to fill the chip): the plan's test
+// the two-dimensional Winograd kernel can run this shape (whether it should: conv_route)
 bool conv_w2d_shape_ok(int B, int H, int W, int C1, int C2, int Cout, int taps);
-bool conv_supports_w2d(int B, int H, int W, int C1, int C2, int Cout, int taps);
 // the kernel itself, for a caller that asks for it by name (flowse_op_conv3x3_w2d): checks its own preconditions
 int launch_w2d(const ConvArgs& a, hipStream_t s);
 // small-M kernel (conv_smallm.hip): shapes it takes (<= 2048 pixels in the batch, channel counts multiples of 32; honours
@@ -339,22 +333,49 @@ int conv_smallm_stats_blocks(int B, int H, int W);
 bool conv1x1_stream_ok(int B, int H, int W, int C1, int C2, int Cout, int taps);
 int conv1x1_stream_stats_blocks(int B, int H, int W);
 bool conv_w2d_enabled();                   // FLOWSE_W2D (read once): the model handle keeps the 2-D weights and uses the kernel
-bool conv_supports_wino(int B, int H, int W, int C1, int C2, int Cout, int taps);
 // whole-K F(4,3) launches of this shape use 128-channel blocks (conv3x3_f43_kernel<GN, false, 2>)
 bool conv_f43_wide(int B, int H, int W, int Cout);
 // host helper: split fp32 conv weights [Cout][Cin][3][3] into the packed bf16 planes described above
 void pack_conv_bf16(const float* w, int Cout, int Cin, int terms, uint16_t* dst, bool f16 = false);
 inline int64_t conv_bf16_numel(int Cout, int Cin, int terms) { return (int64_t)Cout * 9 * Cin * (terms == 1 ? 1 : 2); }
-bool conv_supports_bf16(int B, int H, int W, int C1, int C2, int Cout, int taps);
-// true when launch_conv will run the LDS-halo 3x3 kernel for this shape (the only one that can normalise its
-// input on the fly)
-bool conv_supports_fused_gn(int B, int H, int W, int C1, int C2, int Cout, int taps);
 // true when the 4-output-channel 3x3 heads run the dedicated v_mfma_f32_4x4x1 kernel (fused GroupNorm input ok)
 bool conv_supports_head4(int B, int H, int W, int C1, int C2, int Cout, int taps);
-// number of per-sample partial blocks a conv writes when stats fusion applies to this shape, else 0
-int conv_fused_stats_blocks(int B, int H, int W, int Cin, int Cout, int taps);
-// with_reduce = false: a split-K launch only writes the partial slices (the caller runs launch_splitk_reduce)
+// ---- conv routing: which kernel a convolution runs, over how many K slices, and in what geometry it leaves its GroupNorm
+// statistics.  conv_route is the one policy: a pure host function of the shape, of what the caller can offer and of the
+// environment hooks read at load.  The plan asks once per conv and stores the answer (Builder::conv); launch_conv asks
+// for a ConvArgs somebody filled by hand (the per-op entries).  Choices inside a family stay with its launcher.
+struct ConvShape { int in_dt, out_dt, B, H, W, C1, C2, Cout, taps; };
+struct ConvOffer {
+    // weight copies next to the packed fp32 `w`: ConvArgs::wino / wino2 / wsm / wfrag / wq (with its terms, wq_f16)
+    bool wino = false, wino2 = false, wsm = false, wfrag = false, wq = false;
+    int terms = 0;
+    bool wq_f16 = false;
+    bool slab = false;      // a split-K slab (ConvArgs::partial) may be used
+    bool gn = false;        // the input is normalised on load (ConvArgs::gn)
+    bool bias2 = false, stats = false;   // ConvArgs::bias2 / ::stats are present
+    bool fold = false;      // a folded 1x1 shortcut rides along (ConvArgs::sc1 / wfrag_sc)
+};
+// one value per launcher launch_conv can reach; conv_kernel_name: the prefix that launcher records (conv_note_route)
+enum ConvKernel { CK_HEAD4, CK_HEAD4_16, CK_SMALLM, CK_1X1_STREAM, CK_W2D, CK_F43, CK_F43_SPLITK, CK_HALO, CK_HALO_BF16X3,
+                  CK_HALO16, CK_PC16, CK_SMALLM16B, CK_FLAT, CK_FLAT_SPLITK, CK_FLAT16, CK_FLAT16_SPLITK, CK_NONE };
+const char* conv_kernel_name(ConvKernel k);
+struct ConvRoute {
+    ConvKernel kernel = CK_NONE;
+    int ksplit = 1;              // K slices (> 1 only when a slab was offered)
+    bool reduce = false;         // a separate reduction launch follows (launch_splitk_reduce[_gn])
+    int stats_nblk = 0;          // statistics blocks per sample the kernel (or its reduction) writes; 0: it cannot
+    bool gn_on_load = false;     // the kernel can normalise its input on load
+    double issued = 1.0;         // issued / nominal FLOPs as the plan counts them: 1/3, 1/2, 3 or 1
+    int err = OK;                // != OK: no kernel takes the request; err_text is launch_conv's message
+    const char* err_text = "";
+};
+ConvRoute conv_route(const ConvShape& q, const ConvOffer& o);
+int conv_shape_check(const ConvShape& q);      // the argument checks of launch_conv that the shape alone decides
+// validate, route, switch.  with_reduce = false: a split-K launch only writes the partial slices (the caller runs
+// launch_splitk_reduce)
 int launch_conv(const ConvArgs& a, hipStream_t s, bool with_reduce = true);
+// the switch alone, for a caller that kept the route of these arguments (a.ksplit = r.ksplit)
+int launch_conv_routed(const ConvArgs& a, const ConvRoute& r, hipStream_t s, bool with_reduce = true);
 int launch_splitk_reduce(const ConvArgs& a, hipStream_t s);
 // What the calling thread's last convolution launch ran: every conv launcher records its kernel family -- the small-image
 // launchers the instance -- next to the launch itself (a host-side store: nothing of it is captured into a graph).
@@ -371,12 +392,6 @@ const char* conv_last_route();
 bool conv_reduce_gn_ok(int B, int HW, int Cout);
 int launch_splitk_reduce_gn(const ConvArgs& a, const float* gamma, const float* beta, float eps, int silu, int apply,
                             float* gn_mean, float* gn_scale, hipStream_t s);
-// number of K slices launch_conv will use for this shape (1 = no split) and the partial-buffer size in floats
-int conv_ksplit(int B, int H, int W, int Cin, int Cout, int taps);
-// flat pixels per statistics block of a split-K conv's output
-int conv_splitk_stats_group(int HW);
-// true when this 3x3 shape runs as slices of the F(4,3) kernel
-bool conv_splitk_is_wino(int B, int H, int W, int Cin, int Cout, int taps);
 // true when the 4-channel input conv runs on the matrix cores (then it also emits fused GroupNorm statistics,
 // H*W/128 partial blocks per sample)
 bool conv_cin4_uses_mfma(int B, int H, int W, int Cout, int taps);

@@ -413,39 +413,13 @@ __global__ __launch_bounds__(256, 2) void conv_flat16_kernel(ConvArgs a) {
     conv_epilogue<2, 2, 2, 2, OT>(a, acc, smem, m0, n0, M, HW, split);
 }
 
-// 16-bit path policies.  The halo kernel takes a 3x3 when its tiling applies and yields at least ~one block per two
-// CUs; everything else goes to the flat kernel, sliced along K (two-step stages, >= 2 stages per slice) until ~512
-// blocks exist.
+// The 16-bit halo kernels take a 3x3 when their tiling applies and yields at least ~one block per two CUs; everything else
+// goes to the small-image or the flat kernel (conv_route, conv_dispatch.hip).
 bool conv16_uses_halo(int B, int H, int W, int C1, int C2, int Cout, int taps) {
     if (taps != 9 || (H & 7) || (W & 15) || (C1 % KC) || (C2 % KC) || (Cout % 128)) return false;
     const int64_t cmax = C1 > C2 ? C1 : C2;
     if ((int64_t)(9 * W + 18) * cmax * 4 >= (1LL << 31) || (int64_t)Cout * 9 * (C1 + C2) * 4 >= (1LL << 31)) return false;
     return ((int64_t)B * H * W / 128) * (Cout / 128) >= 128;
-}
-
-int conv16_ksplit(int B, int H, int W, int Cin, int Cout, int taps) {
-    if (conv16_smallm_ok(B, H, W, Cin, 0, Cout, taps)) return 1;        // K is split inside the block (conv16_smallm.hip)
-    const int64_t M = (int64_t)B * H * W;
-    const int64_t tiles = ((M + 127) / 128) * ((Cout + 127) / 128);
-    const int stages = ((Cin / KC) * taps + 1) / 2;
-    if (tiles >= 256 || stages < 4) return 1;
-    int64_t ks = (512 + tiles - 1) / tiles;           // (swept in round 4: 128 ... 1024 blocks, 2 / 4 stages per slice: flat,
-    if (ks > stages / 2) ks = stages / 2;             //  profiles/r04_policy_sweep.md)
-    if (ks < 1) ks = 1;
-    const int per = (int)((stages + ks - 1) / ks);
-    return (int)((stages + per - 1) / per);
-}
-
-int conv16_stats_blocks(int B, int H, int W, int Cin, int Cout, int taps) {
-    const int HW = H * W;
-    if (Cout & 3) return 0;
-    if (taps == 9 && conv16_uses_halo(B, H, W, Cin, 0, Cout, taps)) return HW / 128;     // C1/C2 split is irrelevant here
-    if (conv16_smallm_ok(B, H, W, Cin, 0, Cout, taps)) return conv16_smallm_stats_blocks(B, H, W);
-    if (conv16_ksplit(B, H, W, Cin, Cout, taps) != 1) {
-        const int PB = sk_pixels_per_block(HW);
-        return ((HW % PB) == 0 && Cout / 4 <= 256) ? HW / PB : 0;
-    }
-    return (HW % 128) == 0 ? HW / 128 : 0;
 }
 
 int launch_flat16(const ConvArgs& a, hipStream_t s) {
@@ -548,11 +522,6 @@ void pack_conv_bf16(const float* w, int Cout, int Cin, int terms, uint16_t* dst,
                     if (planes == 2) row[32 + k] = bf16_rne(v - bf16_to_f(hi));
                 }
             }
-}
-
-bool conv_supports_bf16(int B, int H, int W, int C1, int C2, int Cout, int taps) {
-    return (Cout % 128) == 0 && conv_supports_fused_gn(B, H, W, C1, C2, Cout, taps) &&
-           conv_ksplit(B, H, W, C1 + C2, Cout, taps) == 1;              // the 16-bit kernel has no split form
 }
 
 template <int TERMS, bool F16 = false>

@@ -20,11 +20,11 @@ constexpr int LDS_ROW = 36;     // floats per LDS tile row (KC + 4 pad)
 // ---- launchers / policies shared between the conv_*.hip translation units (dispatch: conv_dispatch.hip)
 bool conv_small_m(int64_t M, int Cout);
 bool conv_force_generic();                 // FLOWSE_FORCE_GENERIC_CONV=1 (test hook): the generic flat kernel only
-int f43_plan(int B, int H, int W, int Cin, int Cout, int taps);   // 0: not an F(4,3) shape, 1: whole K, >= 2: slices of chunks
 inline int sk_pixels_per_block(int HW) { return HW <= 8 ? HW : HW <= 1024 ? 8 : HW <= 4096 ? 32 : 64; }
 int launch_flat_fp32(const ConvArgs& a, hipStream_t s);        // conv_flat.hip: flat fp32 kernels (1x1, small 3x3, split-K slices)
 int launch_halo_fp32(const ConvArgs& a, hipStream_t s);        // conv_halo.hip: direct LDS-halo 3x3 (exact fmaf chain)
 int launch_head4(const ConvArgs& a, hipStream_t s);            // conv_halo.hip: 3x3 to four output channels
+bool conv_head4_widens();                                      // FLOWSE_HEAD4_FP32=1: 16-bit inputs run the fp32 head kernel ("head4")
 int launch_f43(const ConvArgs& a, hipStream_t s);              // conv_f43.hip: F(4,3) Winograd 3x3 (whole K or slices)
 int launch_1x1_stream(const ConvArgs& a, hipStream_t s);       // conv_1x1.hip: fp32 1x1 on large images, every wave its own GEMM
 int launch_smallm(const ConvArgs& a, hipStream_t s);           // conv_smallm.hip: <= 2048 pixels, K split inside the block

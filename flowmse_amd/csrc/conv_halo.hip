@@ -494,6 +494,7 @@ bool conv_supports_head4(int B, int H, int W, int C1, int C2, int Cout, int taps
 
 // FLOWSE_HEAD4_FP32=1: the 16-bit modes widen the heads' input and run the fp32 kernel, as in rounds 2-4 (A-B hook)
 static const bool g_head4_fp32 = getenv("FLOWSE_HEAD4_FP32") != nullptr;
+bool conv_head4_widens() { return g_head4_fp32; }
 int launch_head4(const ConvArgs& a, hipStream_t s) {
     const int grid = a.B * (a.H >> 4) * (a.W >> 4);
     const size_t lds = (size_t)(18 * 18 + 36) * LDS_ROW * sizeof(float);

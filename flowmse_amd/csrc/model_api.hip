@@ -1029,11 +1029,25 @@ int flowse_upfirdn2d(const float* input, const float* kernel, int planes, int in
                                  pad_y0, pad_y1, out, out_h, out_w, static_cast<hipStream_t>(stream));
 }
 
+// The route of an fp32 conv for a per-op entry whose scratch can hold what `o` names (a view of conv_route)
+static ConvRoute op_route_f32(int B, int H, int W, int C1, int C2, int Cout, int taps, ConvOffer o) {
+    return conv_route(ConvShape{DT_F32, DT_F32, B, H, W, C1, C2, Cout, taps}, o);
+}
+static ConvOffer op_offer_scratch() {            // flowse_op_conv2d's scratch: the fragment-order weight copy, or the slab
+    ConvOffer o;
+    o.wsm = o.slab = true;
+    return o;
+}
+static ConvOffer op_offer_f43() {                // flowse_op_conv3x3_f43's scratch: the F(4,3) weights and the slab
+    ConvOffer o;
+    o.wino = o.slab = true;
+    return o;
+}
+
 int64_t flowse_op_conv2d_scratch_floats(int B, int H, int W, int Cin, int Cout, int taps) {
-    if (conv_smallm_ok(B, H, W, Cin, 0, Cout, taps) || conv1x1_stream_ok(B, H, W, Cin, 0, Cout, taps))
-        return (int64_t)Cout * taps * Cin;                                                  // fragment-order weight copy
-    const int ks = conv_ksplit(B, H, W, Cin, Cout, taps);
-    return ks > 1 ? (int64_t)ks * B * H * W * Cout : 0;
+    const ConvRoute r = op_route_f32(B, H, W, Cin, 0, Cout, taps, op_offer_scratch());
+    if (r.kernel == CK_SMALLM || r.kernel == CK_1X1_STREAM) return (int64_t)Cout * taps * Cin;   // fragment-order weight copy
+    return r.ksplit > 1 ? (int64_t)r.ksplit * B * H * W * Cout : 0;
 }
 
 int flowse_op_conv2d(const float* in1, int C1, const float* in2, int C2, const float* w, const float* bias,
@@ -1046,19 +1060,18 @@ int flowse_op_conv2d(const float* in1, int C1, const float* in2, int C2, const f
     ConvArgs c = conv_args(in1, C1, in2, in2 ? C2 : 0, w, bias, bias2, bias2_stride, res, out, B, H, W, Cout, taps, scale);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (C1 == 4 && !in2) return launch_conv_cin4(c, s);
-    if (splitk_scratch && conv1x1_stream_ok(B, H, W, c.C1, c.C2, Cout, taps)) {   // the model handle's kernel for this shape
-        const int rc = launch_smallm_weights(w, Cout, taps, c.C1 + c.C2, splitk_scratch, s, false);
-        if (rc != OK) return rc;
-        c.wsm = splitk_scratch;
-    } else if (splitk_scratch && conv_smallm_ok(B, H, W, c.C1, c.C2, Cout, taps)) {
-        const bool t16 = conv_smallm_tile16(B, H, W);
-        const int rc = launch_smallm_weights(w, Cout, taps, c.C1 + c.C2, splitk_scratch, s, t16);
-        if (rc != OK) return rc;
-        c.wsm = splitk_scratch;
-        c.wsm16 = t16 ? splitk_scratch : nullptr;
-    } else if (splitk_scratch) {
-        c.ksplit = conv_ksplit(B, H, W, c.C1 + c.C2, Cout, taps);
-        c.partial = c.ksplit > 1 ? splitk_scratch : nullptr;
+    if (splitk_scratch) {                            // the model handle's kernel for this shape
+        const ConvRoute r = op_route_f32(B, H, W, c.C1, c.C2, Cout, taps, op_offer_scratch());
+        if (r.kernel == CK_SMALLM || r.kernel == CK_1X1_STREAM) {
+            const bool t16 = r.kernel == CK_SMALLM && conv_smallm_tile16(B, H, W);
+            const int rc = launch_smallm_weights(w, Cout, taps, c.C1 + c.C2, splitk_scratch, s, t16);
+            if (rc != OK) return rc;
+            c.wsm = splitk_scratch;
+            c.wsm16 = t16 ? splitk_scratch : nullptr;
+        } else {
+            c.ksplit = r.ksplit;
+            c.partial = c.ksplit > 1 ? splitk_scratch : nullptr;
+        }
     }
     return launch_conv(c, s);
 }
@@ -1091,7 +1104,7 @@ int flowse_op_conv3x3_gn(const float* in1, int C1, const float* in2, int C2, con
         return ERR_ARG;
     }
     if (!in2) C2 = 0;
-    if (!conv_supports_fused_gn(B, H, W, C1, C2, Cout, 9)) {
+    if (!op_route_f32(B, H, W, C1, C2, Cout, 9, ConvOffer()).gn_on_load) {
         set_error("flowse_op_conv3x3_gn: shape B=%d H=%d W=%d C=%d+%d Cout=%d not covered by the halo kernel", B, H, W,
                   C1, C2, Cout);
         return ERR_SHAPE;
@@ -1112,7 +1125,8 @@ static int op_conv3x3_winograd(const float* in1, int C1, const float* in2, int C
         return ERR_ARG;
     }
     if (!in2) C2 = 0;
-    if (two_d ? !conv_w2d_shape_ok(B, H, W, C1, C2, Cout, 9) : !conv_supports_wino(B, H, W, C1, C2, Cout, 9)) {
+    const ConvRoute r = op_route_f32(B, H, W, C1, C2, Cout, 9, op_offer_f43());
+    if (two_d ? !conv_w2d_shape_ok(B, H, W, C1, C2, Cout, 9) : (r.kernel != CK_F43 && r.kernel != CK_F43_SPLITK)) {
         set_error("flowse_op_conv3x3_%s: shape B=%d H=%d W=%d C=%d+%d Cout=%d not covered by the Winograd kernel",
                   two_d ? "w2d" : "f43", B, H, W, C1, C2, Cout);
         return ERR_SHAPE;
@@ -1125,7 +1139,7 @@ static int op_conv3x3_winograd(const float* in1, int C1, const float* in2, int C
     ConvArgs c = conv_args(in1, C1, in2, C2, w, bias, bias2, bias2_stride, res, out, B, H, W, Cout, 9, scale);
     if (two_d) c.wino2 = wf;
     else c.wino = wf;
-    const int ks = two_d ? 1 : conv_ksplit(B, H, W, C, Cout, 9);
+    const int ks = two_d ? 1 : r.ksplit;
     if (ks > 1) {                           // same split plan as the model handle uses for this shape
         c.ksplit = ks;
         c.partial = wf + conv_wino_numel(Cout, C);
@@ -1141,7 +1155,7 @@ static int op_conv3x3_winograd(const float* in1, int C1, const float* in2, int C
 }
 
 int64_t flowse_op_conv3x3_f43_scratch_floats(int B, int H, int W, int C, int Cout) {
-    const int ks = conv_ksplit(B, H, W, C, Cout, 9);                   // > 1: F(4,3) runs split over K (small images)
+    const int ks = op_route_f32(B, H, W, C, 0, Cout, 9, op_offer_f43()).ksplit;   // > 1: F(4,3) runs split over K (small images)
     return flowse_op_group_norm_scratch_floats(B, H * W, C) + conv_wino_numel(Cout, C) +
            (ks > 1 ? (int64_t)ks * B * H * W * Cout : 0);
 }
@@ -1182,12 +1196,18 @@ static int op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
     if (!in2) C2 = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t M = (int64_t)B * H * W, C = C1 + C2;
-    // (the LDS-halo kernels store the operands' type only: an fp32-output launch of their shapes runs the flat kernel)
-    const bool halo = !out_f32 && conv16_uses_halo(B, H, W, C1, C2, Cout, taps);
     // the progressive-output heads (C -> 4, ncsnpp.py:345-366): 16-bit input, fp32 residual (the pyramid) and fp32 output, as
     // in the model -- conv3x3_head4_16_kernel
     const bool head = Cout == 4 && taps == 9 && !in2 && conv_supports_head4(B, H, W, C1, 0, Cout, taps);
-    const int ks = (halo || head) ? 1 : conv16_ksplit(B, H, W, (int)C, Cout, taps);
+    const bool direct = head || out_f32;                   // fp32 res / out, used in place
+    // (the LDS-halo kernels store the operands' type only: an fp32-output launch of their shapes runs the flat kernel)
+    ConvOffer offer;                                       // the scratch holds the 16-bit weights, their fragment-order copy, the slab
+    offer.wq = offer.wfrag = offer.slab = true;
+    offer.terms = 1;
+    offer.wq_f16 = dt == DT_F16;
+    offer.bias2 = bias2 != nullptr;
+    const ConvRoute r = conv_route(ConvShape{dt, direct ? DT_F32 : dt, B, H, W, C1, C2, Cout, taps}, offer);
+    const int ks = r.ksplit;
     const int64_t nw = ((int64_t)Cout * taps * C + 3) & ~(int64_t)3;
     // the carver's round-up per sub-buffer, upper bound over the optional ones
     const auto up = Carver::up;
@@ -1197,7 +1217,7 @@ static int op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
         set_error("flowse_op_conv2d_16: scratch needs %lld bytes", (long long)need);
         return ERR_ARG;
     }
-    if (gn_mean && !halo && !head) {
+    if (gn_mean && !r.gn_on_load) {
         set_error("flowse_op_conv2d_16: fused GroupNorm input only on LDS-halo shapes");
         return ERR_SHAPE;
     }
@@ -1207,7 +1227,6 @@ static int op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
     void* wq = cv.take(2 * nw);
     const bool frag = (taps == 9 && conv16_uses_pc(B, H, W, C1, C2, Cout, taps)) || conv16_smallm_ok(B, H, W, C1, C2, Cout, taps);
     void* wfrag = frag ? cv.take(2 * nw) : nullptr;
-    const bool direct = head || out_f32;                   // fp32 res / out, used in place
     void* r16 = res && !direct ? cv.take(2 * M * Cout) : nullptr;
     void* o16 = direct ? nullptr : cv.take(2 * M * Cout);
     float* part = ks > 1 ? static_cast<float*>(cv.take(4 * (int64_t)ks * M * Cout)) : nullptr;
@@ -1264,6 +1283,36 @@ int flowse_op_conv2d_16_ex(const float* in1, int C1, const float* in2, int C2, c
 }
 
 const char* flowse_op_last_conv_route(void) { return conv_last_route(); }
+
+int flowse_op_conv_route(int in_dt, int out_dt, int B, int H, int W, int C1, int C2, int Cout, int taps, int offer_bits,
+                         char* text, int cap) {
+    if (!text || cap < 64 || in_dt < DT_F32 || in_dt > DT_F16 || (out_dt != DT_F32 && out_dt != in_dt) || B < 1 || H < 1 || W < 1) {
+        set_error("flowse_op_conv_route: bad argument");
+        return ERR_ARG;
+    }
+    const ConvShape q{in_dt, out_dt, B, H, W, C1, C2, Cout, taps};
+    ConvOffer o;
+    o.wino = offer_bits & FLOWSE_OFFER_WINO; o.wino2 = offer_bits & FLOWSE_OFFER_WINO2; o.wsm = offer_bits & FLOWSE_OFFER_WSM;
+    o.wfrag = offer_bits & FLOWSE_OFFER_WFRAG; o.wq = offer_bits & FLOWSE_OFFER_WQ;
+    o.terms = !o.wq ? 0 : (offer_bits & FLOWSE_OFFER_WQ_SPLIT3) ? 3 : 1;
+    o.wq_f16 = offer_bits & FLOWSE_OFFER_WQ_F16;
+    o.slab = offer_bits & FLOWSE_OFFER_SLAB; o.gn = offer_bits & FLOWSE_OFFER_GN; o.bias2 = offer_bits & FLOWSE_OFFER_BIAS2;
+    o.stats = offer_bits & FLOWSE_OFFER_STATS; o.fold = offer_bits & FLOWSE_OFFER_FOLD;
+    int err = conv_shape_check(q);
+    ConvRoute r;
+    if (err == OK) {
+        r = conv_route(q, o);
+        if ((err = r.err) != OK) set_error("%s", r.err_text);
+    }
+    if (err != OK) {
+        snprintf(text, cap, "error %d", err);
+        return OK;
+    }
+    const char* issued = r.issued == 0.5 ? "1/2" : r.issued == 3.0 ? "3" : r.issued == 1.0 ? "1" : "1/3";
+    snprintf(text, cap, "%s ks=%d reduce=%d stats=%d gn=%d issued=%s", conv_kernel_name(r.kernel), r.ksplit, r.reduce ? 1 : 0,
+             r.stats_nblk, r.gn_on_load ? 1 : 0, issued);
+    return OK;
+}
 
 // Tail of ResnetBlockBigGANpp in 16-bit storage as ONE launch of the producer / consumer kernel:
 //   out = (conv3x3(act(GroupNorm(h)); w1) + b1 + conv1x1(cat[x1, x2]; w2) + b2) * scale       (layerspp.py:265-274)

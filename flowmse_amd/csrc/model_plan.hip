@@ -215,16 +215,33 @@ struct Builder {
         }, 8.0 * Bn * HW * (C1 + C2), (double)(dt_size(idt) + dt_size(odt)) * Bn * HW * (C1 + C2));
         return o;
     }
-    // Split of a conv's reduction dimension over blocks (1: unsplit) -- the one place the plan asks.  (C1, C2): the parts of
-    // a concat input, as the kernel predicates take them.
-    int ksplit(int dt, int H, int W, int C1, int C2, int Cout, int taps) const {
-        if (dt == DT_F32) return conv_ksplit(B, H, W, C1 + C2, Cout, taps);
-        return (conv_supports_head4(B, H, W, C1, C2, Cout, taps) || conv16_uses_halo(B, H, W, C1, C2, Cout, taps))
-                   ? 1 : conv16_ksplit(B, H, W, C1 + C2, Cout, taps);
+    // What the weight set holds for the conv weight at packed offset w, read as storage type idt (wq_off: its bf16 planes)
+    ConvOffer offer(int idt, int64_t w, int taps, int64_t wq_off) const {
+        const WeightSet& ws = *m->wt;
+        ConvOffer of;
+        if (idt != DT_F32) {                             // [Cout][taps][Cin] in the storage type, + the fragment-order copy
+            of.wq = true;
+            of.terms = 1;
+            of.wq_f16 = idt == DT_F16;
+            of.wfrag = ws.frag_offs.count(w) != 0;
+        } else {
+            of.wino = taps == 9 && ws.wino_of.count(w) != 0;
+            of.wino2 = taps == 9 && ws.wino2_of.count(w) != 0;
+            of.wsm = ws.wsm_offs.count(w) != 0;
+            of.wq = !m->storage16() && wq_off >= 0 && ws.precision != 0 && taps == 9;
+            of.terms = !of.wq ? 0 : ws.precision == 1 ? 3 : 1;
+            of.wq_f16 = of.wq && ws.precision == 3;
+        }
+        of.slab = true;                                  // the arena has room for one
+        return of;
     }
-    // true when a conv of this shape runs split over K with the separate (two-pass) reduction launch
-    bool sk_two_pass(int dt, int H, int W, int Cin, int Cout, int taps) const {
-        return ksplit(dt, H, W, Cin, 0, Cout, taps) > 1;
+    // The route Builder::conv will get for a conv of this shape on weight w: resblock plans its fusions from it -- split over K
+    // (.ksplit > 1), normalising on load (.gn_on_load), on the producer / consumer kernel (.kernel == CK_PC16).  (C1, C2): the
+    // parts of a concat input.
+    ConvRoute predict(int dt, int H, int W, int C1, int C2, int Cout, int taps, int64_t w) const {
+        ConvOffer of = offer(dt, w, taps, -1);           // (the bf16 planes change neither of the three)
+        of.stats = Cout >= 16;
+        return conv_route(ConvShape{dt, Cout > 4 ? m->wt->act_dt : DT_F32, B, H, W, C1, C2, Cout, taps}, of);
     }
     // conv: out (new tensor unless `out_is_res`), res optional
     Tn conv(const ConvReq& q) {
@@ -247,7 +264,26 @@ struct Builder {
             set_error("internal: a second per-channel bias and a Dense row on one conv (%s)", label.c_str());
             failed = true;
         }
-        const int ks = cin4 ? 1 : ksplit(a.dt, H, Wd, C1, C2, Cout, taps);
+        const int idt = a.dt;
+        const int want_odt = out_is_res ? res->dt : out_dt >= 0 ? out_dt : (Cout > 4 ? M->wt->act_dt : DT_F32);   // = alloc()'s choice below
+        const bool in16 = idt != DT_F32;                 // 16-bit storage: the 16-bit matrix-core kernels take it
+        const bool has_gin = gin != nullptr, has_fold = fold != nullptr;
+        // The one routing question of this conv, asked once: the offer is what the weight set holds for this weight.  The
+        // answer says which kernel runs, over how many K slices and where its statistics go; the launch closure keeps it.
+        ConvRoute rt;                                    // (the 4-channel input kernels: launch_conv_cin4, never split)
+        if (!cin4) {
+            ConvOffer of = offer(idt, w, taps, wq_off);
+            of.gn = has_gin;
+            of.bias2 = dense_row0 >= 0 || bias_sc >= 0;
+            of.stats = !(out_is_res || Cout < 16 || no_stats);
+            of.fold = has_fold;
+            rt = conv_route(ConvShape{idt, want_odt, Bn, H, Wd, C1, C2, Cout, taps}, of);
+            if (rt.err != OK) {
+                set_error("internal: no kernel takes %s@%dx%d (%s)", label.c_str(), H, Wd, rt.err_text);
+                failed = true;
+            }
+        }
+        const int ks = rt.ksplit;
         // a deferred reduction leaves no output tensor: decide before anything is allocated
         if (defer && !(ks > 1 && !res && dense_row0 < 0)) defer = nullptr;
         if ((extra || gnf) && !(ks > 1)) {
@@ -262,33 +298,13 @@ struct Builder {
         if (!defer) o = out_is_res ? *res : alloc(a.H, a.W, Cout, out_dt);
         const size_t a_off = a.off, b_off = b2 ? b2->off : 0, o_off = o.off, r_off = res ? res->off : 0;
         const bool has2 = b2 != nullptr, hasres = res != nullptr;
-        const int idt = a.dt, odt = o.dt;
-        const bool in16 = idt != DT_F32;                 // 16-bit storage: the 16-bit matrix-core kernels take it
-        int st_nblk = (cin4 || out_is_res || Cout < 16) ? 0
-                      : in16 ? (conv16_uses_halo(Bn, H, Wd, C1, C2, Cout, taps) ? H * Wd / 128
-                                                                                 : conv16_stats_blocks(Bn, H, Wd, C1 + C2, Cout, taps))
-                             : conv_fused_stats_blocks(Bn, H, Wd, C1 + C2, Cout, taps);
+        const int odt = o.dt;                            // (a deferred conv has no output tensor: fp32, as its slices are)
+        // statistics of the output: the geometry of the kernel that runs
+        int st_nblk = (cin4 || out_is_res || Cout < 16) ? 0 : rt.stats_nblk;
         if (cin4 && !out_is_res && C1 == 4 && !has2 && conv_cin4_uses_mfma(Bn, H, Wd, Cout, taps)) st_nblk = H * Wd / 128;
         // Combine (conv1x1 4 -> C, in place on `res`, any storage type): the kernel leaves the statistics of the updated tensor
         if (cin4 && out_is_res && taps == 1 && C1 == 4 && !has2 && idt == DT_F32 && Cout >= 16)
             st_nblk = conv_cin4_stats_blocks(Bn, H, Wd, Cout);
-        // conv_ksplit / conv_fused_stats_blocks judge the small-M kernel by the TOTAL channel count; a concat whose parts are
-        // not 32-aligned (not in the released net) runs the unsplit flat kernel instead: its statistics geometry applies
-        const bool use_smallm = !in16 && !cin4 && M->wt->wsm_offs.count(w) && conv_smallm_ok(Bn, H, Wd, C1, C2, Cout, taps);
-        if (!in16 && !cin4 && !use_smallm && st_nblk > 0 && conv_smallm_ok(Bn, H, Wd, C1 + C2, 0, Cout, taps))
-            st_nblk = (H * Wd) % 128 == 0 ? H * Wd / 128 : 0;
-        const bool use_stream = !in16 && !cin4 && ks == 1 && M->wt->wsm_offs.count(w) && conv1x1_stream_ok(Bn, H, Wd, C1, C2, Cout, taps);
-        if (!in16 && !cin4 && !use_stream && st_nblk > 0 && conv1x1_stream_ok(Bn, H, Wd, C1 + C2, 0, Cout, taps))
-            st_nblk = (H * Wd) % 128 == 0 ? H * Wd / 128 : 0;
-        if (in16 && !cin4 && st_nblk > 0 && conv16_smallm_ok(Bn, H, Wd, C1 + C2, 0, Cout, taps) &&
-            !(M->wt->frag_offs.count(w) && conv16_smallm_ok(Bn, H, Wd, C1, C2, Cout, taps)))
-            st_nblk = (H * Wd) % 128 == 0 ? H * Wd / 128 : 0;
-        // the two-dimensional Winograd kernel takes this launch: statistics in 4 x 16 pixel strips
-        const auto w2_it = M->wt->wino2_of.find(w);
-        const int64_t wino2_off = (!in16 && taps == 9 && !cin4 && ks == 1 && w2_it != M->wt->wino2_of.end() &&
-                                   !(wq_off >= 0 && M->wt->precision != 0) && conv_supports_fused_gn(Bn, H, Wd, C1, C2, Cout, taps) &&
-                                   conv_supports_w2d(Bn, H, Wd, C1, C2, Cout, taps)) ? w2_it->second : -1;
-        if (wino2_off >= 0 && st_nblk > 0) st_nblk = H * Wd / 64;
         if (defer || gnf) st_nblk = 0;                   // no output here / the statistics are finished inside the reduction
         if (no_stats) st_nblk = 0;                       // nobody normalises this tensor (the shortcut: a residual only)
         if (out_is_res && o.st_nblk > 0) {               // updated in place: the producer's statistics are stale
@@ -300,19 +316,18 @@ struct Builder {
             o.st_off = arena.alloc((size_t)Bn * st_nblk * Cout * 2 * sizeof(float));
         }
         const size_t st_off = o.st_off;
-        const bool has_gin = gin != nullptr;
         const GnBuf gbuf = has_gin ? *gin : GnBuf();
-        const bool use_bf16 = !M->storage16() && wq_off >= 0 && M->wt->precision != 0 && taps == 9 &&
-                              conv_supports_bf16(Bn, H, Wd, C1, C2, Cout, taps);
+        // the optional weight copies the route's kernel reads
+        const ConvKernel kn = rt.kernel;
+        const bool use_wq = !in16 && (kn == CK_HALO_BF16X3 || kn == CK_HALO16);
+        const bool use_wfrag = kn == CK_PC16 || kn == CK_SMALLM16B;
+        const int64_t wino_off = (kn == CK_F43 || kn == CK_F43_SPLITK) ? M->wt->wino_of.at(w) : -1;
+        const int64_t wino2_off = kn == CK_W2D ? M->wt->wino2_of.at(w) : -1;
         const int terms = M->wt->precision == 1 ? 3 : 1;
-        const auto wino_it = M->wt->wino_of.find(w);
-        const int64_t wino_off = (!in16 && taps == 9 && !cin4 && wino_it != M->wt->wino_of.end() &&
-                                  conv_supports_wino(Bn, H, Wd, C1, C2, Cout, taps)) ? wino_it->second : -1;
         const size_t part_off = ks > 1 ? arena.alloc((size_t)ks * Bn * H * Wd * Cout * sizeof(float)) : 0;
         const size_t table_off = M_table_off;     // by value: the Builder dies before the plan runs
         const bool has_extra = extra != nullptr && extra->valid;
         const SkPartial xp = has_extra ? *extra : SkPartial();
-        const bool has_fold = fold != nullptr;
         const size_t f1_off = has_fold ? fold->s1->off : 0, f2_off = has_fold && fold->s2 ? fold->s2->off : 0;
         const int FC1 = has_fold ? fold->s1->C : 0, FC2 = has_fold && fold->s2 ? fold->s2->C : 0;
         const int64_t fold_w = has_fold ? fold->w : -1, fold_b = has_fold ? fold->bias : -1;
@@ -365,21 +380,18 @@ struct Builder {
             c.out_dt = odt;
             if (in16) {                                   // [Cout][taps][Cin] in the storage type: same offsets as d_w
                 c.wq = M->wt->d_w16 + w;
-                if (M->wt->frag_offs.count(w)) c.wfrag = M->wt->d_wfrag + w;
+                if (use_wfrag) c.wfrag = M->wt->d_wfrag + w;
                 c.terms = 1;
                 c.wq_f16 = idt == DT_F16 ? 1 : 0;
-            } else if (use_bf16) {
+            } else if (use_wq) {
                 c.wq = M->wt->d_wq + wq_off;
                 c.terms = terms;
                 c.wq_f16 = M->wt->precision == 3 ? 1 : 0;
             }
             if (wino_off >= 0) c.wino = M->wt->d_wino + wino_off;
             if (wino2_off >= 0) c.wino2 = M->wt->d_wino2 + wino2_off;
-            if (use_smallm) {
-                c.wsm = M->wt->d_wsm + w;
-                c.wsm16 = M->wt->d_wsm16 + w;
-            }
-            if (use_stream) c.wsm = M->wt->d_wsm + w;
+            if (kn == CK_SMALLM || kn == CK_1X1_STREAM) c.wsm = M->wt->d_wsm + w;
+            if (kn == CK_SMALLM) c.wsm16 = M->wt->d_wsm16 + w;
             return c;
         };
         const double flops = 2.0 * Bn * H * Wd * (double)Cout * (taps * (C1 + C2) + (FC1 + FC2));
@@ -389,10 +401,11 @@ struct Builder {
         const double part_bytes = 4.0 * ks * (double)Bn * H * Wd * Cout;
         op(full_label, [=](hipStream_t s) {
             const ConvArgs c = make_args();
-            return cin4 ? launch_conv_cin4(c, s) : launch_conv(c, s, false);
+            return cin4 ? launch_conv_cin4(c, s) : launch_conv_routed(c, rt, s, false);
         }, flops, in_bytes + (ks > 1 ? part_bytes : out_bytes),
-           has_gin && Cout > 64 && ks == 1 && (wino2_off >= 0 || wino_off < 0 || conv_f43_wide(Bn, H, Wd, Cout)),
-           wino2_off >= 0 ? flops / 3.0 : wino_off >= 0 ? flops * 0.5 : (use_bf16 && terms == 3) ? 3.0 * flops : flops);
+           // the roofline's kernel: a whole-K 3x3 that normalises on load -- of those counted at half the FLOPs (the F(4,3)
+           // weights), only the launches that use 128-channel blocks
+           has_gin && Cout > 64 && ks == 1 && (rt.issued != 0.5 || conv_f43_wide(Bn, H, Wd, Cout)), flops * rt.issued);
         if (defer) {                                     // the consumer's reduction sums these slices (ConvArgs::partial2)
             defer->part_off = part_off;
             defer->ks = ks;
@@ -477,11 +490,9 @@ struct Builder {
     Tn resblock(const Module& mod, const Tn& x1, const Tn* x2) {
         const float rs2 = 0.70710678118654752440f;
         Tn h1, xs;
-        auto fusable_shape = [&](int dt, int H, int W, int C, int c2) {   // Conv(act(GroupNorm(t))) as one kernel for this shape?
-            return dt != DT_F32 ? conv16_uses_halo(B, H, W, C, c2, mod.out_ch, 9)
-                                : conv_supports_fused_gn(B, H, W, C, c2, mod.out_ch, 9);
-        };
-        auto fusable = [&](const Tn& t, int c2) { return fusable_shape(t.dt, t.H, t.W, t.C, c2); };
+        // Conv_0 / Conv_1 on (predicted or existing) tensors: does Conv(act(GroupNorm(t))) run as one kernel?
+        auto conv0_route = [&](const Tn& t, int c2) { return predict(t.dt, t.H, t.W, t.C, c2, mod.out_ch, 9, mod.w_c0); };
+        auto conv1_route = [&](int dt, int H, int W) { return predict(dt, H, W, mod.out_ch, 0, mod.out_ch, 9, mod.w_c1); };
         // output geometry of the block (Conv_0 already runs at the resampled size)
         const int Ho = mod.up ? 2 * x1.H : mod.down ? x1.H / 2 : x1.H, Wo = mod.up ? 2 * x1.W : mod.down ? x1.W / 2 : x1.W;
         // Small images run split over K with a separate reduction launch.  Two of those launches disappear here:
@@ -493,17 +504,16 @@ struct Builder {
         gf.w_gamma = mod.w_gn1_g;
         gf.w_beta = mod.w_gn1_b;
         gf.silu = true;
-        gf.apply = !fusable_shape(m->wt->act_dt, Ho, Wo, mod.out_ch, 0);
+        const ConvRoute c1_plan = conv1_route(m->wt->act_dt, Ho, Wo);       // Conv_1 as predicted: its input does not exist yet
+        gf.apply = !c1_plan.gn_on_load;
         SkPartial sp;
-        const bool merge_sc = mod.shortcut && sk_two_pass(x1.dt, Ho, Wo, mod.out_ch, mod.out_ch, 9) &&
-                              sk_two_pass(x1.dt, Ho, Wo, mod.in_ch, mod.out_ch, 1);
+        const bool merge_sc = mod.shortcut && conv1_route(x1.dt, Ho, Wo).ksplit > 1 &&
+                              predict(x1.dt, Ho, Wo, mod.in_ch, 0, mod.out_ch, 1, mod.w_c2).ksplit > 1;
         // 16-bit storage, Conv_1 on the producer / consumer kernel: the shortcut Conv_2(x) runs as extra K steps of Conv_1's
         // launch (ConvArgs::sc1) -- no launch, no round trip of its output through HBM, one read of x less
         const int xc2 = (!mod.up && !mod.down && x2) ? x2->C : 0;
         const bool fold_sc = mod.shortcut && m->wt->act_dt != DT_F32 && !merge_sc && !getenv("FLOWSE_NO_SCFOLD") &&
-                             m->wt->frag_offs.count(mod.w_c1) && m->wt->frag_offs.count(mod.w_c2) &&
-                             conv16_uses_pc(B, Ho, Wo, mod.out_ch, 0, mod.out_ch, 9) &&
-                             fusable_shape(m->wt->act_dt, Ho, Wo, mod.out_ch, 0) && (x1.C % 32) == 0 && (xc2 % 32) == 0 &&
+                             m->wt->frag_offs.count(mod.w_c2) && c1_plan.kernel == CK_PC16 && (x1.C % 32) == 0 && (xc2 % 32) == 0 &&
                              x1.C + xc2 >= 96 && x1.dt == m->wt->act_dt;
         // fp32 up blocks whose shortcut is a launch of its own: Conv_2 has no spatial extent and upsample_2d filters every
         // channel alike, so W . up(x) = up(W . x) -- the 1x1 runs BEFORE the upsampling, on a quarter of the pixels, and the
@@ -533,7 +543,7 @@ struct Builder {
                 if (merge_sc) r.defer = &sp;
                 xs = conv(r);
             }
-            if (fusable(x1, x2 ? x2->C : 0)) {
+            if (conv0_route(x1, x2 ? x2->C : 0).gn_on_load) {
                 // Conv_0(act(GroupNorm_0(x))) in one kernel: the normalised tensor never reaches HBM
                 GnBuf g0 = gn(x1, x2, mod.w_gn0_g, mod.w_gn0_b);
                 ConvReq r = conv0("conv0_3x3_gn", x1);
@@ -583,8 +593,9 @@ struct Builder {
         //    own reduction launch now;
         //  * per-channel mean / scale from Conv_0's reduction are only of use to a Conv_1 that normalises on load -- else
         //    they are released and GroupNorm_1 is materialised below.
-        if (sp.valid && !sk_two_pass(h1.dt, h1.H, h1.W, h1.C, mod.out_ch, 9)) xs = reduce_deferred(sp, h1.H, h1.W, mod.out_ch);
-        if (gf.done && !gf.apply && !fusable(h1, 0)) {
+        const ConvRoute c1 = predict(h1.dt, h1.H, h1.W, h1.C, 0, mod.out_ch, 9, mod.w_c1);
+        if (sp.valid && !(c1.ksplit > 1)) xs = reduce_deferred(sp, h1.H, h1.W, mod.out_ch);
+        if (gf.done && !gf.apply && !c1.gn_on_load) {
             gn_release(gf.g);
             gf.done = false;
         }
@@ -599,11 +610,12 @@ struct Builder {
         }
         const ScFold* fold = fold_sc ? &fo : nullptr;
         const int64_t bias_sc = sc_low ? mod.w_c2_b : -1;   // Conv_2's bias, left out of the low-resolution 1x1
-        if (fold && ((gf.done && gf.apply) || !fusable(h1, 0) || !conv16_uses_pc(B, h1.H, h1.W, h1.C, 0, mod.out_ch, 9) ||
+        if (fold && ((gf.done && gf.apply) || c1.kernel != CK_PC16 ||
                      getenv("FLOWSE_SCFOLD_LATE"))) {          // (the variable: test hook that forces this branch)
-            // The fold was planned from PREDICTED shapes / types and the shortcut launch skipped; the Conv_1 that exists does not
-            // take it (the two predicates agree today: this is the safety net for a policy that drifts).  The shortcut runs
-            // now, as its own launch, and rides as Conv_1's residual: a little slower, never an unusable model.
+            // The fold was planned from the PREDICTED tensor and the shortcut launch skipped; the Conv_1 that exists does not
+            // take it: the same conv_route answered both times, so only a tensor type or shape that differs from the predicted
+            // one gets here (or Conv_0's reduction that already applied GroupNorm_1).  The shortcut runs now, as its own
+            // launch, and rides as Conv_1's residual: a little slower, never an unusable model.
             ConvReq r = shortcut(*fo.s1);
             r.b2 = fo.s2;
             xs = conv(r);
@@ -623,7 +635,7 @@ struct Builder {
         if (gf.done && gf.apply) {                       // h1 already is act(GroupNorm_1(Conv_0(.)))
             out = conv(conv1("conv1_3x3", h1));
             release(h1);
-        } else if (fusable(h1, 0)) {
+        } else if (c1.gn_on_load) {
             GnBuf g1 = gf.done ? gf.g : gn(h1, nullptr, mod.w_gn1_g, mod.w_gn1_b);
             ConvReq r = conv1(fold ? "conv1_3x3_gn_sc" : "conv1_3x3_gn", h1);
             r.gin = &g1;
@@ -793,8 +805,7 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
         const Module& pcv = next();
         // 16-bit h: the dedicated 4-channel head kernel reads it directly; small images materialise act(GN(h)) in fp32
         // and run the fp32 kernels
-        const bool pfuse = h.dt != DT_F32 ? conv_supports_head4(B, h.H, h.W, h.C, 0, 4, 9)
-                                          : conv_supports_fused_gn(B, h.H, h.W, h.C, 0, 4, 9);
+        const bool pfuse = bd.predict(h.dt, h.H, h.W, h.C, 0, 4, 9, pcv.w_a).gn_on_load;
         GnBuf g;
         if (pfuse) g = bd.gn(h, nullptr, gnm.w_a, gnm.w_a_b);
         Tn ph = pfuse ? h : bd.gn_norm(h, nullptr, gnm.w_a, gnm.w_a_b, true, DT_F32);

@@ -533,6 +533,31 @@ int flowse_op_conv2d_16_ex(const float* in1, int C1, const float* in2, int C2, c
  * from the shape a second time; a host-side, thread-local record ("" before the first launch): replaying a captured
  * graph does not change it.  The pointer stays valid for the thread's lifetime; the text changes with the next launch. */
 const char* flowse_op_last_conv_route(void);
+/* What a convolution of this shape WOULD run: the library's one routing decision (the plan of a model handle and every
+ * per-op entry go through it), as one line of text.  Host only: no HIP call, works with no GPU present.  in_dt / out_dt:
+ * storage types (0 fp32, 1 bf16, 2 half; out_dt = in_dt or 0); (C1, C2): the parts of a concat input; offer_bits: what
+ * the caller could hand to the launch, FLOWSE_OFFER_* below.  Writes
+ *   "<kernel> ks=<K slices> reduce=<0|1> stats=<blocks per sample> gn=<0|1> issued=<1/3|1/2|1|3>"
+ * -- kernel: the family flowse_op_last_conv_route reports after that launch ("smallm" / "smallm16b" without the instance);
+ * reduce: a separate reduction launch follows; stats: geometry of the fused GroupNorm statistics (0: none); gn: the kernel
+ * can normalise its input on load; issued: issued / nominal FLOPs as the profile counts them -- or "error <status>" for a
+ * request no kernel takes (flowse_last_error has launch_conv's text).  cap >= 64. */
+enum {
+    FLOWSE_OFFER_WINO = 1,        /* F(4,3) weights */
+    FLOWSE_OFFER_WINO2 = 2,       /* F(4,3) x F(2,3) weights */
+    FLOWSE_OFFER_WSM = 4,         /* fp32 fragment-order copy (small-image and streaming 1x1 kernels) */
+    FLOWSE_OFFER_WFRAG = 8,       /* 16-bit fragment-order copy (producer / consumer and 16-bit small-image kernels) */
+    FLOWSE_OFFER_WQ = 16,         /* 16-bit weights: one plane ... */
+    FLOWSE_OFFER_WQ_SPLIT3 = 32,  /* ... or the split-bf16 pair (with FLOWSE_OFFER_WQ) */
+    FLOWSE_OFFER_WQ_F16 = 64,     /* the planes hold IEEE half */
+    FLOWSE_OFFER_SLAB = 128,      /* a split-K slab may be used */
+    FLOWSE_OFFER_GN = 256,        /* the input is normalised on load */
+    FLOWSE_OFFER_BIAS2 = 512,     /* a per-sample bias is present */
+    FLOWSE_OFFER_STATS = 1024,    /* fused statistics of the output are asked for */
+    FLOWSE_OFFER_FOLD = 2048      /* a folded 1x1 shortcut rides along */
+};
+int flowse_op_conv_route(int in_dt, int out_dt, int B, int H, int W, int C1, int C2, int Cout, int taps, int offer_bits,
+                         char* text, int cap);
 /* Tail of ResnetBlockBigGANpp (layerspp.py:265-274) in 16-bit storage as ONE launch of the producer / consumer kernel:
  *   out = (conv3x3(act(GroupNorm(h)); w1) + b1 + conv1x1(cat[x1, x2]; w2) + b2) * scale
  * The 1x1 shortcut Conv_2(x) runs as extra K steps of Conv_1's launch (the form the 16-bit model modes use wherever

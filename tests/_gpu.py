@@ -68,7 +68,7 @@ def conv2d_16(x1, w, dt, bias=None, x2=None, bias2=None, res=None, scale=1.0, ou
     mean, scl, beta = (t.contiguous().cuda() for t in gn) if gn is not None else (None, None, None)
     out = torch.empty(B, H, W, Cout, device="cuda")
     M = B * H * W
-    ksmax = max(1, (Cin // 32 * taps + 1) // 4)            # K slices: at most half the two-step stages (conv16_ksplit)
+    ksmax = max(1, (Cin // 32 * taps + 1) // 4)            # K slices: at most half the two-step stages (flat16_ksplit)
     nbytes = 2 * (M * Cin + 2 * Cout * taps * Cin + 2 * M * Cout) + 4 * ksmax * M * Cout + 4096
     scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     _lib.check(L.flowse_op_conv2d_16_ex(_lib.ptr(a1), C1, _lib.ptr(a2), C2, _lib.ptr(wp), _lib.ptr(bb), _lib.ptr(b2),
