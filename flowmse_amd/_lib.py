@@ -87,6 +87,8 @@ SIGNATURES = {
     "flowse_stft_compress_rows": (_i, [C.POINTER(flowse_spec_row), _i, _i, _vp, _f, _f, _vp]),
     "flowse_istft_decompress_stacks": (_i, [_vp, _i, _i, _i, _i, _f, _f, _fp, _i, _f, _vp]),
     "flowse_istft_decompress_ensemble": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _i64, _f, _f, _fp, _i, _f, _fp, _vp]),
+    "flowse_stft_compress_window": (_i, [_fp, _i64, _i64, _f, _i64, _i, _i64, _vp, _f, _f, _vp]),
+    "flowse_istft_decompress_window": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i64, _f, _f, _fp, _i64, _i64, _f, _vp]),
     "flowse_resample_num_taps": (_i, [_i, _i]),
     "flowse_resample_taps": (_i, [_i, _i, C.POINTER(_d), _i]),
     "flowse_resample_poly": (_i, [_fp, _i, _i, _i, _i, _fp, _i, _vp]),

@@ -502,6 +502,13 @@ int launch_istft_decompress_ensemble(const float* chunks_c64, int S, int D, int 
 // the R rows [R,1,256,Tw] of one sampler call from up to FLOWSE_MAX_SPEC_ROWS signals; `rows`: HOST table
 int launch_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, float* out_c64, float factor, float exponent,
                               hipStream_t s);
+// the same per-frame and per-sample code on a WINDOW of a recording that is still arriving (flowmse_amd.live): one row of
+// frames [frame0, frame0 + Tc) from the samples [s0, s0 + n); the output samples [e0, e0 + n_out) from chunks k-2, k-1, k
+int launch_stft_compress_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t frame0, int Tc,
+                                int64_t L_total, float* out_c64, float factor, float exponent, hipStream_t s);
+int launch_istft_decompress_window(const float* prev2_c64, const float* prev_c64, const float* cur_c64, int64_t k, int Tc,
+                                   int hop, int last, int64_t L, float factor, float exponent, float* out, int64_t e0,
+                                   int64_t n_out, float scale_out, hipStream_t s);
 // out = y + sigma * z   (complex64 as float pairs)
 int launch_axpy(const float* y, const float* z, float sigma, int64_t n, float* out, hipStream_t s);
 // out = y + sigma * z (y != null) or out = z (y == null), z = the keyed Philox noise of noise.hip; [B,1,F,T] complex64,

@@ -958,6 +958,28 @@ int flowse_istft_decompress_ensemble(const void* chunks_c64, int S, int D, int K
                                             static_cast<hipStream_t>(stream));
 }
 
+int flowse_stft_compress_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t frame0, int Tc,
+                                int64_t L_total, void* out_c64, float factor, float exponent, void* stream) {
+    if (!buf || !out_c64) {
+        set_error("flowse_stft_compress_window: null argument");
+        return ERR_ARG;
+    }
+    return launch_stft_compress_window(buf, s0, n, scale_in, frame0, Tc, L_total, static_cast<float*>(out_c64), factor,
+                                       exponent, static_cast<hipStream_t>(stream));
+}
+
+int flowse_istft_decompress_window(const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k, int Tc,
+                                   int hop, int last, int64_t L, float factor, float exponent, float* out, int64_t e0,
+                                   int64_t n_out, float scale_out, void* stream) {
+    if (!cur_c64 || !out) {
+        set_error("flowse_istft_decompress_window: null argument");
+        return ERR_ARG;
+    }
+    return launch_istft_decompress_window(static_cast<const float*>(prev2_c64), static_cast<const float*>(prev_c64),
+                                          static_cast<const float*>(cur_c64), k, Tc, hop, last, L, factor, exponent, out,
+                                          e0, n_out, scale_out, static_cast<hipStream_t>(stream));
+}
+
 int flowse_profile_begin(flowse_model* m, int mode) {
     if (!m || (mode != 0 && mode != 1)) {
         set_error("flowse_profile_begin: bad argument");

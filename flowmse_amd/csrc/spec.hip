@@ -49,10 +49,12 @@ static int ensure_tables(float** out) {
 
 // One frame by one block of 256 threads = 256 bins: frame t of `sig` (L samples, T = L / 128 + 1 frames) to *dst; frames
 // t >= T are the zero padding of pad_spec.  Every STFT kernel below is this function, so a frame's value depends on
-// (samples, scale_in, t) only -- not on the kernel, the row or the batch that asked for it.  Sample indices in 64 bits.
-__device__ __forceinline__ void stft_frame(const float* __restrict__ sig, int L, float scale_in,
-                                           const float* __restrict__ tab, float2* __restrict__ dst, int t, int T,
-                                           float factor, float exponent) {
+// (samples, scale_in, t) only -- not on the kernel, the row or the batch that asked for it.  Sample and frame indices in
+// 64 bits.  `sig` points at sample s0 of the signal (0: the whole signal; > 0: a window of it, whose caller has checked
+// that every index this frame reads lies inside the window).
+__device__ __forceinline__ void stft_frame(const float* __restrict__ sig, int64_t L, float scale_in,
+                                           const float* __restrict__ tab, float2* __restrict__ dst, int64_t t, int64_t T,
+                                           float factor, float exponent, int64_t s0 = 0) {
     __shared__ float xw[NFFT], ct[NFFT], st[NFFT];
     const int f = threadIdx.x;
     if (t >= T) {
@@ -60,10 +62,10 @@ __device__ __forceinline__ void stft_frame(const float* __restrict__ sig, int L,
         return;
     }
     for (int n = threadIdx.x; n < NFFT; n += 256) {
-        int64_t j = (int64_t)t * HOP + n - PADC;       // centre=True, reflect padding
+        int64_t j = t * HOP + n - PADC;                // centre=True, reflect padding
         if (j < 0) j = -j;
-        if (j >= L) j = 2 * ((int64_t)L - 1) - j;
-        xw[n] = sig[j] * scale_in * tab[n];
+        if (j >= L) j = 2 * (L - 1) - j;
+        xw[n] = sig[j - s0] * scale_in * tab[n];
         ct[n] = tab[NFFT + n];
         st[n] = tab[2 * NFFT + n];
     }
@@ -116,14 +118,22 @@ __global__ __launch_bounds__(256) void stft_compress_rows_kernel(const SpecRowTa
 // Frame t of a recording held as K chunks [K][NBIN][Tc] that start `hop` frames apart (To = Tc - hop <= hop frames of
 // overlap, so at most two chunks cover a frame): chunk k = min(t / hop, K - 1) at j = t - k hop; in the first To frames
 // of every chunk but the first, the linear cross-fade  a + w (b - a),  w = (j + 0.5) / To,  from the previous chunk's
-// tail a to this chunk's head b -- on the compressed value, before spec_back.
-__device__ __forceinline__ float2 seam_frame(const float2* __restrict__ chunks, int f, int t, int K, int Tc, int hop) {
+// tail a to this chunk's head b -- on the compressed value, before spec_back.  `rows(k)` is chunk k's [NBIN][Tc]: StackRows
+// for a contiguous stack, WindowRows for the chunks a live session still holds.
+struct StackRows {
+    const float2* base;
+    int Tc;
+    __device__ __forceinline__ const float2* operator()(int k) const { return base + (int64_t)k * NBIN * Tc; }
+};
+
+template <class Rows>
+__device__ __forceinline__ float2 seam_frame(const Rows& rows, int f, int t, int K, int Tc, int hop) {
     int k = t / hop;
     if (k > K - 1) k = K - 1;
     const int j = t - k * hop, To = Tc - hop;
-    const float2 b = chunks[((int64_t)k * NBIN + f) * Tc + j];
+    const float2 b = rows(k)[(int64_t)f * Tc + j];
     if (k == 0 || j >= To) return b;
-    const float2 a = chunks[((int64_t)(k - 1) * NBIN + f) * Tc + j + hop];
+    const float2 a = rows(k - 1)[(int64_t)f * Tc + j + hop];
     const float w = ((float)j + 0.5f) / (float)To;
     return make_float2(a.x + w * (b.x - a.x), a.y + w * (b.y - a.y));
 }
@@ -153,7 +163,8 @@ struct DrawLayout {
 template <bool SEAM>
 __device__ __forceinline__ float2 draw_value(const float2* __restrict__ spec, int b, int d, int f, int t, int Tpad,
                                              float factor, float exponent, int K, int Tc, int hop, const DrawLayout& lay) {
-    const float2 z = SEAM ? seam_frame(spec + (b * lay.stack_rows + d * lay.draw_rows) * NBIN * Tc, f, t, K, Tc, hop)
+    const float2 z = SEAM ? seam_frame(StackRows{spec + (b * lay.stack_rows + d * lay.draw_rows) * NBIN * Tc, Tc}, f, t, K, Tc,
+                                       hop)
                           : spec[((int64_t)b * NBIN + f) * Tpad + t];
     return spec_back_value(z, factor, exponent);
 }
@@ -171,24 +182,22 @@ __device__ __forceinline__ float2 mean_value(const float2* __restrict__ spec, in
     return make_float2(m.x * lay.inv_D, m.y * lay.inv_D);
 }
 
-// grid (ceil(Lout / 128), B), 256 threads: sample = tid & 127, the two halves split the bins.
-// SEAM: `spec` holds B chunk stacks as above, T == Tpad == Tg frames each, of lay.D draws each (DrawLayout; B == 1 and one
-// draw for the chunks of one recording); the frame that is transformed back is the mean of the draws' linear values.
-// else [B][NBIN][Tpad], one draw.
-template <bool SEAM>
-__global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __restrict__ spec, int T, int Tpad,
-                                                               float factor, float exponent,
-                                                               const float* __restrict__ tab, float* __restrict__ out,
-                                                               int Lout, float scale_out, int K, int Tc, int hop,
-                                                               const DrawLayout lay) {
+// The HOP output samples [n0, n0 + 128) by one block of 256 threads: sample = tid & 127, the two halves split the bins.
+// Every inverse-STFT kernel below is this function, so a sample's value depends on the frames over it only -- not on the
+// kernel or the block that asked for it.  frames(t, f): the linear value of frame t at bin f, asked only for t < frames.T
+// (the frames >= frames.T take no part in the overlap-add).  Sample n is stored at out[n - n_lo] if n_lo <= n < n_hi.
+// Sample and frame indices in 64 bits.
+template <class Frames>
+__device__ __forceinline__ void istft_gather(const Frames& frames, const float* __restrict__ tab, float* __restrict__ out,
+                                             int64_t n0, int64_t n_lo, int64_t n_hi, float scale_out) {
     constexpr int NF = 5;                               // frames that can overlap a block of HOP samples
     __shared__ float2 Xs[NF][NBIN];
     __shared__ float ct[NFFT], st[NFFT], win[NFFT];
     __shared__ float part[256];
-    const int b = blockIdx.y, n0 = blockIdx.x * HOP;
     const int tid = threadIdx.x;
+    const int64_t T = frames.T;
     // frame t covers output samples [128 t - 255, 128 t + 254]
-    int t_lo = (n0 - (NFFT - 1 - PADC) + HOP - 1) / HOP;          // ceil((n0 - 254) / 128), may be negative
+    int64_t t_lo = (n0 - (NFFT - 1 - PADC) + HOP - 1) / HOP;      // ceil((n0 - 254) / 128), may be negative
     if (n0 - (NFFT - 1 - PADC) < 0) t_lo = 0;
     for (int i = tid; i < NFFT; i += 256) {
         win[i] = tab[i];
@@ -197,18 +206,20 @@ __global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __r
     }
     for (int i = tid; i < NF * NBIN; i += 256) {
         const int fr = i / NBIN, f = i - fr * NBIN;
-        const int t = t_lo + fr;
+        const int64_t t = t_lo + fr;
         float2 z = make_float2(0.f, 0.f);
-        if (t < T) z = mean_value<SEAM>(spec, b, f, t, Tpad, factor, exponent, K, Tc, hop, lay);
+        if (t < T) z = frames(t, f);
         Xs[fr][f] = z;
     }
     __syncthreads();
-    const int n = n0 + (tid & 127), half = tid >> 7;
+    const int64_t n = n0 + (tid & 127);
+    const int half = tid >> 7;
     float acc = 0.f, env = 0.f;
     for (int fr = 0; fr < NF; ++fr) {
-        const int t = t_lo + fr;
-        const int k = n + PADC - t * HOP;               // position inside frame t
-        if (t >= T || k < 0 || k >= NFFT) continue;
+        const int64_t t = t_lo + fr;
+        const int64_t kk = n + PADC - t * HOP;          // position inside frame t
+        if (t >= T || kk < 0 || kk >= NFFT) continue;
+        const int k = (int)kk;
         const float w = win[k];
         env = fmaf(w, w, env);
         // irfft: 1/N [Re X0 + (-1)^k Re X_{N/2} + 2 sum_{f=1}^{N/2-1} (Re X_f cos - Im X_f sin)(2 pi f k / N)]
@@ -227,10 +238,76 @@ __global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __r
     }
     part[tid] = acc;
     __syncthreads();
-    if (half == 0 && n < Lout) {
+    if (half == 0 && n >= n_lo && n < n_hi) {
         const float v = part[tid] + part[tid + 128];
-        out[(int64_t)b * Lout + n] = env > 1e-11f ? v / env * scale_out : 0.f;
+        out[n - n_lo] = env > 1e-11f ? v / env * scale_out : 0.f;
     }
+}
+
+// grid (ceil(Lout / 128), B), 256 threads.
+// SEAM: `spec` holds B chunk stacks as above, T == Tpad == Tg frames each, of lay.D draws each (DrawLayout; B == 1 and one
+// draw for the chunks of one recording); the frame that is transformed back is the mean of the draws' linear values.
+// else [B][NBIN][Tpad], one draw.
+template <bool SEAM>
+struct SpecFrames {
+    const float2* spec;
+    int64_t T;
+    int b, Tpad, K, Tc, hop;
+    float factor, exponent;
+    DrawLayout lay;
+    __device__ __forceinline__ float2 operator()(int64_t t, int f) const {
+        return mean_value<SEAM>(spec, b, f, (int)t, Tpad, factor, exponent, K, Tc, hop, lay);
+    }
+};
+
+template <bool SEAM>
+__global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __restrict__ spec, int T, int Tpad,
+                                                               float factor, float exponent,
+                                                               const float* __restrict__ tab, float* __restrict__ out,
+                                                               int Lout, float scale_out, int K, int Tc, int hop,
+                                                               const DrawLayout lay) {
+    const int b = blockIdx.y;
+    istft_gather(SpecFrames<SEAM>{spec, T, b, Tpad, K, Tc, hop, factor, exponent, lay}, tab, out + (int64_t)b * Lout,
+                 (int64_t)blockIdx.x * HOP, 0, Lout, scale_out);
+}
+
+// The chunks a live session holds when chunk k has been sampled: c[i] = chunk m + i of the recording, m = max(k - 2, 0),
+// as rows of a stack whose frame 0 is the recording's frame m hop.  Chunk m is read as the head of that stack -- WITHOUT
+// the blend into chunk m - 1 -- so the host admits only frames that do not need it: [t_lo, t_hi), checked there against
+// the seam rule.  Frames outside that range are read as zero; no sample that is stored lies under one.
+struct WindowRows {
+    const float2* c[3];
+    __device__ __forceinline__ const float2* operator()(int k) const { return k == 0 ? c[0] : (k == 1 ? c[1] : c[2]); }
+};
+
+struct WindowFrames {
+    WindowRows rows;
+    int64_t T;                                          // frames >= T take no part: Tg after the last chunk, else none
+    int64_t base, t_lo, t_hi;                           // base = m hop
+    int Kw, Tc, hop;                                    // Kw: chunks of the local stack (one more while the recording is open)
+    float factor, exponent;
+    __device__ __forceinline__ float2 operator()(int64_t t, int f) const {
+        if (t < t_lo || t >= t_hi) return make_float2(0.f, 0.f);
+        // mean_value of one draw multiplies by 1.f, which is exact
+        return spec_back_value(seam_frame(rows, f, (int)(t - base), Kw, Tc, hop), factor, exponent);
+    }
+};
+
+// grid (blocks of 128 samples that meet [e0, e0 + n_out)), 256 threads: out[i] = sample e0 + i of the recording
+__global__ __launch_bounds__(256) void istft_decompress_window_kernel(const WindowFrames frames,
+                                                                      const float* __restrict__ tab,
+                                                                      float* __restrict__ out, int64_t e0, int64_t n_out,
+                                                                      float scale_out) {
+    istft_gather(frames, tab, out, (e0 / HOP + blockIdx.x) * HOP, e0, e0 + n_out, scale_out);
+}
+
+// grid (Tc), 256 threads = 256 bins: frames [frame0, frame0 + Tc) of a recording of which `buf` holds the samples from s0 on
+__global__ __launch_bounds__(256) void stft_compress_window_kernel(const float* __restrict__ buf, int64_t s0, int64_t L,
+                                                                   float scale_in, const float* __restrict__ tab,
+                                                                   float2* __restrict__ out, int64_t frame0, int64_t T,
+                                                                   int Tc, float factor, float exponent) {
+    stft_frame(buf, L, scale_in, tab, out + (int64_t)threadIdx.x * Tc + blockIdx.x, frame0 + blockIdx.x, T, factor,
+               exponent, s0);
 }
 
 // Per-frame agreement tracks of an ensemble: grid (ceil(Tg / 64), S), 256 threads = 64 frames (lanes along t, the
@@ -411,6 +488,109 @@ int launch_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, float*
     if (rc != OK) return rc;
     hipLaunchKernelGGL(stft_compress_rows_kernel, dim3(Tw, R), dim3(256), 0, s, t, tab, reinterpret_cast<float2*>(out_c64),
                        Tw, factor, exponent);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+// ---- windows of a recording that is still arriving (flowmse_amd.live) -------------------------------------------------
+constexpr int64_t WINDOW_MAX = (int64_t)1 << 40;        // frames and chunk indices: every product below stays in 64 bits
+
+int launch_stft_compress_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t frame0, int Tc,
+                                int64_t L_total, float* out_c64, float factor, float exponent, hipStream_t s) {
+    const bool closed = L_total >= 0;
+    if (s0 < 0 || n < 1 || s0 > WINDOW_MAX * HOP || n > WINDOW_MAX * HOP || frame0 < 0 || frame0 > WINDOW_MAX || Tc < 1 ||
+        Tc > (1 << 23) || L_total < -1 || (closed && (L_total <= PADC || s0 + n > L_total))) {
+        set_error("stft window: need s0 >= 0, n >= 1, 0 <= frame0 <= 2^40, 1 <= Tc <= 2^23 and L_total = -1 or 255 < "
+                  "s0 + n <= L_total (got s0=%lld n=%lld frame0=%lld Tc=%d L_total=%lld)", (long long)s0, (long long)n,
+                  (long long)frame0, Tc, (long long)L_total);
+        return ERR_SHAPE;
+    }
+    // the frames that read samples: [frame0, t_end); those >= T = L_total / 128 + 1 of a closed recording are zero
+    const int64_t T = closed ? L_total / HOP + 1 : INT64_MAX / 4;
+    const int64_t t_end = frame0 + Tc < T ? frame0 + Tc : T;
+    if (t_end > frame0) {
+        const int64_t j_lo = frame0 * HOP - PADC, j_hi = (t_end - 1) * HOP + (NFFT - 1 - PADC);   // before reflection
+        if (j_lo < 0 && s0 != 0) {
+            set_error("stft window: frame %lld reflects about sample 0 and needs samples [0, %lld], the window starts at "
+                      "s0=%lld", (long long)frame0, (long long)-j_lo, (long long)s0);
+            return ERR_SHAPE;
+        }
+        int64_t need_lo = j_lo < 0 ? 0 : j_lo, need_hi = j_hi;
+        if (j_lo < 0 && -j_lo > need_hi) need_hi = -j_lo;
+        if (closed && j_hi >= L_total) {                // reflected about the last sample: 2 (L - 1) - j for j in [L, j_hi]
+            const int64_t r_lo = 2 * (L_total - 1) - j_hi;
+            if (r_lo < need_lo) need_lo = r_lo;
+            need_hi = L_total - 1;
+        }
+        if (need_lo < s0 || need_hi >= s0 + n) {
+            set_error("stft window: frames [%lld, %lld) need samples [%lld, %lld], the window holds [%lld, %lld) "
+                      "(L_total=%lld)", (long long)frame0, (long long)t_end, (long long)need_lo, (long long)need_hi,
+                      (long long)s0, (long long)(s0 + n), (long long)L_total);
+            return ERR_SHAPE;
+        }
+    }
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(stft_compress_window_kernel, dim3(Tc), dim3(256), 0, s, buf, s0, closed ? L_total : INT64_MAX / 4,
+                       scale_in, tab, reinterpret_cast<float2*>(out_c64), frame0, T, Tc, factor, exponent);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+int launch_istft_decompress_window(const float* prev2_c64, const float* prev_c64, const float* cur_c64, int64_t k, int Tc,
+                                   int hop, int last, int64_t L, float factor, float exponent, float* out, int64_t e0,
+                                   int64_t n_out, float scale_out, hipStream_t s) {
+    if (k < 0 || k > WINDOW_MAX || Tc < 1 || Tc > (1 << 23) || hop < 1 || hop > Tc || 2 * (int64_t)hop < Tc || e0 < 0 ||
+        n_out < 1 || n_out > ((int64_t)1 << 30) || e0 > WINDOW_MAX * HOP || factor == 0.f) {
+        set_error("istft window: need 0 <= k <= 2^40, 1 <= hop <= Tc <= 2 hop, Tc <= 2^23, e0 >= 0, 1 <= n_out <= 2^30 and "
+                  "factor != 0 (got k=%lld Tc=%d hop=%d e0=%lld n_out=%lld)", (long long)k, Tc, hop, (long long)e0,
+                  (long long)n_out);
+        return ERR_SHAPE;
+    }
+    const int64_t Tg = k * hop + Tc, To = Tc - hop;
+    if (last && (e0 + n_out > L || L > (Tg - 1) * HOP + NFFT - PADC)) {
+        set_error("istft window: after the last chunk need e0 + n_out <= L <= 128 (Tg - 1) + 255 (got e0=%lld n_out=%lld "
+                  "L=%lld Tg=%lld)", (long long)e0, (long long)n_out, (long long)L, (long long)Tg);
+        return ERR_SHAPE;
+    }
+    // the frames over the samples [e0, e0 + n_out): the index range of istft_gather for one sample, over all of them
+    const int64_t t_first = e0 <= NFFT - 1 - PADC ? 0 : (e0 - (NFFT - 1 - PADC) + HOP - 1) / HOP;
+    int64_t t_last = (e0 + n_out - 1 + PADC) / HOP;
+    if (last && t_last > Tg - 1) t_last = Tg - 1;
+    // the chunks the seam rule reads for them
+    const int64_t c_hi = last && t_last / hop > k ? k : t_last / hop;
+    int64_t c_lo = last && t_first / hop > k ? k : t_first / hop;
+    if (c_lo > 0 && t_first - c_lo * hop < To) c_lo -= 1;
+    const int64_t m = k >= 2 ? k - 2 : 0;
+    if (c_hi > k || c_lo < m || (c_lo <= k - 1 && !prev_c64) || (c_lo <= k - 2 && !prev2_c64)) {
+        set_error("istft window: samples [%lld, %lld) lie under frames [%lld, %lld], which the seam rule takes from chunks "
+                  "%lld..%lld; given are chunk k=%lld%s%s%s", (long long)e0, (long long)(e0 + n_out), (long long)t_first,
+                  (long long)t_last, (long long)c_lo, (long long)c_hi, (long long)k,
+                  (k >= 1 && prev_c64) ? ", k-1" : "", (k >= 2 && prev2_c64) ? ", k-2" : "",
+                  last ? " (the last)" : " (not the last: frames from (k+1) hop on wait for chunk k+1)");
+        return ERR_SHAPE;
+    }
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    WindowFrames fr;
+    const float2* given[3] = {reinterpret_cast<const float2*>(prev2_c64), reinterpret_cast<const float2*>(prev_c64),
+                              reinterpret_cast<const float2*>(cur_c64)};
+    const int held = (int)(k - m) + 1;                  // chunks m .. k
+    for (int i = 0; i < 3; ++i) fr.rows.c[i] = i < held ? given[3 - held + i] : nullptr;
+    fr.T = last ? Tg : INT64_MAX / 4;
+    fr.base = m * hop;
+    fr.t_lo = t_first;
+    fr.t_hi = t_last + 1;
+    fr.Kw = held + (last ? 0 : 1);
+    fr.Tc = Tc;
+    fr.hop = hop;
+    fr.factor = factor;
+    fr.exponent = exponent;
+    const int64_t blocks = (e0 + n_out - 1) / HOP - e0 / HOP + 1;
+    hipLaunchKernelGGL(istft_decompress_window_kernel, dim3((unsigned)blocks), dim3(256), 0, s, fr, tab, out, e0, n_out,
+                       scale_out);
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

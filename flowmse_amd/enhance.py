@@ -43,6 +43,17 @@ inverse STFT (and before ``--output_rate input`` resamples back).  This is NOT t
 power over the draws' deviation from it, in dB: high means the model is sure, around 0 dB or below the output is mostly the
 draw.  Draw 0 is the draw of a run without the flag, bit for bit, and ``--samples 1`` is that run.  A file's stack of sampled
 rows is ``D`` times as large (512 KB per chunk and draw at 256 frames).
+
+Live.  ``--live --ckpt MODEL.ckpt`` (``flowmse_amd.live``) reads raw mono 16 kHz PCM from stdin (``--live_pcm s16le|f32le``),
+``--live_block`` samples at a time, and writes the enhanced PCM to stdout in the same format as soon as it is final, flushed
+after every block: ``arecord -t raw -f S16_LE -r 16000 | python -m flowmse_amd.enhance --live --ckpt m.ckpt | aplay ...``.  The
+bytes are those of the chunked file mode at ``--batch 1`` for the finished recording under the noise key of the name
+``live``, when ``--live_norm`` is the recording's peak; ``--live_norm first`` (default) takes the peak of the samples that
+make the first chunk ready.  The output trails the input by at most ``128 chunk_frames + 382`` samples (2.07 s at the default
+256 frames, 0.54 s at 64) plus the sampler's compute time.  Nothing but PCM goes to stdout; messages go to stderr.  The
+file-mode options that make no sense on one open stream (``--input``, ``--output``, ``--pool``, ``--resample``, ``--samples``
+> 1, ``--channels all``, ``--noise torch``) are refused by name.  ``--synthetic 1`` stands in for a checkpoint (synthetic
+weights); stdin is still the signal.
 """
 import argparse
 import csv
@@ -56,6 +67,7 @@ import torch
 from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, enhance_long, plan_chunks
 from flowmse_amd.ensemble import samples_arg
 from flowmse_amd.evaluate import _load_model, _seconds_arg, _synthetic_pairs, _write_wav
+from flowmse_amd.live import PCM_FORMATS, pcm_decode, pcm_encode
 from flowmse_amd.pooled import MAX_BATCH, enhance_pooled
 from flowmse_amd.resample import out_len, rational, resample
 from flowmse_amd.util.noise import utterance_key
@@ -78,7 +90,8 @@ def build_parser():
     ap = argparse.ArgumentParser(description="Enhance noisy 16 kHz recordings of any length (no clean files, no metrics); "
                                              "with --resample, recordings at other sample rates too.")
     ap.add_argument("--input", type=str, default=None, help="a wav file, or a directory whose *.wav are enhanced")
-    ap.add_argument("--output", type=str, required=True, help="directory for the enhanced wavs and _settings.txt")
+    ap.add_argument("--output", type=str, default=None,
+                    help="directory for the enhanced wavs and _settings.txt (required unless --live)")
     ap.add_argument("--ckpt", type=str, default=None)
     ap.add_argument("--synthetic", type=int, default=0, help="run on this many synthetic signals with synthetic weights")
     ap.add_argument("--synthetic_seconds", type=_seconds_arg, default=[2.0],
@@ -124,12 +137,58 @@ def build_parser():
     ap.add_argument("--synthetic_channels", type=_channels_arg, default=[1],
                     help="channel counts of the --synthetic signals, a comma list cycled over them (default 1); channel "
                          "c > 0 is an independent signal at half the level of channel 0")
+    ap.add_argument("--live", action="store_true",
+                    help="enhance raw mono 16 kHz PCM from stdin to stdout as it arrives (flowmse_amd.live): the bytes of the "
+                         "chunked file mode at --batch 1, at most 128 chunk_frames + 382 samples behind the input")
+    ap.add_argument("--live_pcm", choices=tuple(PCM_FORMATS), default="s16le",
+                    help="needs --live. Sample format of stdin and stdout (default s16le; output rounded to nearest, saturated)")
+    ap.add_argument("--live_block", type=int, default=2048, metavar="N",
+                    help="needs --live. Samples read from stdin per push (default 2048); stdout is flushed after each")
+    ap.add_argument("--live_norm", type=_live_norm_arg, default="first", metavar="FLOAT|first",
+                    help="needs --live. The peak the signal is normalised by: a positive number (the recording's max|y| gives "
+                         "the file mode's bytes), or 'first' (default): the peak of the samples that make the first chunk ready")
     return ap
+
+
+def _live_norm_arg(v):
+    if v == "first":
+        return v
+    try:
+        f = float(v)
+    except ValueError:
+        f = -1.0
+    if not 0.0 < f < float("inf"):
+        raise argparse.ArgumentTypeError(f"--live_norm takes a positive number or 'first', got {v!r}")
+    return f
+
+
+def _check_live(args, ap):
+    """``--live`` reads one open stream: every option that names files, pools rows or draws unkeyed noise is refused."""
+    for given, name in ((args.input is not None, "--input"), (args.output is not None, "--output"), (args.pool, "--pool"),
+                        (args.resample, "--resample"), (args.samples > 1, f"--samples {args.samples}"),
+                        (args.channels == "all", "--channels all"), (args.noise != "keyed", f"--noise {args.noise}")):
+        if given:
+            ap.error(f"--live does not take {name}: it enhances one mono 16 kHz stream from stdin to stdout with keyed noise")
+    if args.live_block < 1:
+        ap.error(f"--live_block must be >= 1, got {args.live_block}")
+    if not args.synthetic and not args.ckpt:
+        ap.error("--live needs --ckpt (or --synthetic 1 for synthetic weights)")
+    if args.N < 1:
+        ap.error(f"--N must be >= 1, got {args.N}")
+    try:
+        plan_chunks(1, args.chunk_frames, args.overlap_frames)
+    except ValueError as e:
+        ap.error(str(e))
+    return args
 
 
 def parse_args(argv=None, ap=None):
     ap = ap or build_parser()
     args = ap.parse_args(argv)
+    if args.live:
+        return _check_live(args, ap)
+    if args.output is None:
+        ap.error("the following arguments are required: --output")
     if args.synthetic < 0:
         ap.error(f"--synthetic must be >= 0, got {args.synthetic}")
     if not args.synthetic and not (args.input and args.ckpt):
@@ -302,9 +361,43 @@ def write_settings(out_dir, args, model, epoch, noise_seed, resampled=()):
         f.write(f"seed: {args.seed}\nnoise: {args.noise}\nnoise seed: {noise_seed}\n")
 
 
+def run_live(args, ap):
+    """The ``--live`` run: PCM blocks from stdin through one ``LiveEnhancer`` to stdout, flushed after every push.  Returns
+    the samples written."""
+    import sys
+    from flowmse_amd.live import LiveEnhancer
+    stdin, stdout = sys.stdin.buffer, sys.stdout.buffer
+    text_out, sys.stdout = sys.stdout, sys.stderr                  # nothing but PCM may reach stdout
+    try:
+        model, _ = _load_model(types.SimpleNamespace(synthetic=args.synthetic, ckpt=args.ckpt, test_dir="stdin",
+                                                     precision=args.precision), ap)
+        seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(8), "little")
+        live = LiveEnhancer(model, norm=args.live_norm, key=utterance_key("live"), seed=seed, chunk_frames=args.chunk_frames,
+                            overlap_frames=args.overlap_frames, N=args.N, T_rev=args.reverse_starting_point,
+                            t_eps=args.last_eval_point, odesolver=args.odesolver)
+        print(f"live: keyed noise seed {seed}, {args.live_pcm}, blocks of {args.live_block}, at most "
+              f"{live.latency_samples} samples ({live.latency_samples / SAMPLE_RATE:.2f} s) behind the input", file=sys.stderr)
+        width, t0 = PCM_FORMATS[args.live_pcm], time.time()
+        while True:
+            data = stdin.read(args.live_block * width)
+            if not data:
+                break
+            stdout.write(pcm_encode(live.push(pcm_decode(data, args.live_pcm)), args.live_pcm))
+            stdout.flush()
+        stdout.write(pcm_encode(live.finish(), args.live_pcm))
+        stdout.flush()
+        print(f"live: enhanced {live.samples_out} samples in {time.time() - t0:.2f} s", file=sys.stderr)
+        return live.samples_out
+    finally:
+        sys.stdout = text_out
+
+
 def main(argv=None):
     ap = build_parser()
     args = parse_args(argv, ap)
+    if args.live:
+        run_live(args, ap)
+        return 0
     if args.synthetic:
         signals = synthetic_signals(args.synthetic, args.synthetic_seconds, args.synthetic_channels, args.synthetic_rate)
         names = [p[0] for p in signals]

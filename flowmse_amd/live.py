@@ -1,0 +1,308 @@
+"""Live enhancement: a recording is enhanced while it arrives, and the bytes are those of the finished file.
+
+``LiveEnhancer`` takes the samples of ONE recording in pushes of any sizes and returns enhanced samples as soon as they
+are final.  **Contract:** the concatenation of everything ``push`` and ``finish`` returned is, bit for bit, what
+``chunked.enhance_long(model, y, chunk_frames, overlap_frames, batch=1, noise_key=key, noise_seed=seed, ...)`` returns
+for the whole recording ``y`` with the same solver, ``N``, ``T_rev``, ``t_eps`` and precision, when the enhancer's
+``norm`` equals the recording's ``max|y|``.  That includes a recording that fits one chunk (``K = 1``), which
+``enhance_long`` hands to ``enhance_waveform`` with ``T`` padded to a multiple of 64.  "Live" is not "streams": ``--streams``
+and the HIP-stream lanes of ``flowmse_amd.parallel`` are concurrent sampler calls and have nothing to do with this module.
+
+Why it holds.  Chunk ``k`` of ``enhance_long`` depends on ``Tc`` frames of input and nothing after them; the seam rule looks
+back one chunk; the keyed noise is addressed at absolute frames; a frame's value depends on (samples, scale, t) only and a
+sample's value on the frames over it only.  The two window entries of the library (``flowse_stft_compress_window``,
+``flowse_istft_decompress_window``) run the per-frame and per-sample device code of the chunk calls on what is held here.
+
+Schedule (``n_fft = 510``, ``hop_length = 128``, ``center=True``; ``hop = Tc - To`` is the chunk hop in frames).  Checked
+against the index ranges of the kernels (``stft_frame`` reads ``[128 t - 255, 128 t + 254]``, reflected at both ends;
+``istft_gather`` puts frame ``t`` over the output samples ``[128 t - 255, 128 t + 254]``):
+
+* Frame ``t`` is computable without right padding once ``128 t + 255`` samples have arrived.
+* Chunk ``k`` (frames ``[k hop, k hop + Tc)``) is ready at ``n_k = 128 (k hop + Tc - 1) + 255`` samples.  A chunk that
+  became ready this way is never the recording's last: ``L >= n_k`` gives ``L // 128 + 1 > k hop + Tc`` frames.
+* Once chunk ``k`` is sampled and is not the last, frames ``< (k + 1) hop`` are final and so are the output samples
+  ``s < E_k = 128 (k + 1) hop - 255``; the samples ``[E_{k-1}, E_k)`` (``E_{-1} = 0``) are emitted then.  They lie under
+  frames from ``k hop - 3`` on.  With ``Tc - 2 To >= 3`` those are plain frames of chunk ``k - 1``, and chunks ``k - 1`` and
+  ``k`` suffice.  With ``To = Tc / 2`` (the only other geometry ``plan_chunks`` admits: ``Tc - 2 To`` is a multiple of 4)
+  frames ``k hop - 3 .. k hop - 1`` are BLENDED frames of chunk ``k - 1``, whose other half is chunk ``k - 2``: then two
+  previous chunks are kept, and the window entry takes all three.
+* Worst algorithmic latency ``n_k - E_{k-1} = 128 Tc + 382`` samples (``latency_samples``): 2.07 s at ``Tc = 256``, 0.54 s at
+  ``Tc = 64``.  The sampler's compute time comes on top.
+* After chunk ``k`` the samples before ``128 (k + 1) hop - 256`` are dropped (clamped at 0).  One more than chunk ``k + 1``
+  reads while the recording is open: if it ends at a multiple of 128 exactly one frame past chunk ``k`` (possible at
+  ``To = 0``), that frame's right reflection reads sample ``L - 256``.
+
+``finish()`` fixes ``L`` (``L > 255``, as every call of the package requires) and ``K = plan_chunks(L // 128 + 1, Tc, To)[0]``,
+samples the chunks that were waiting for samples that never came -- one or two, in order, at batch width 1, now with the
+right reflection and the zero frames ``>= T`` of ``flowse_stft_compress_chunks`` -- and emits ``[E_{last emitted}, L)``.
+
+State: the sample buffer (one linear device tensor whose capacity follows the largest push), one or two previous chunks
+(512 KB each at ``Tc = 256``) and nothing else; every push returns all it produced, so no output is ever pending.
+``norm`` must be known before the first chunk: a positive float (a capture device's full scale, say), or ``"first"`` =
+``max|y|`` over the samples ``[0, n_0)`` that make chunk 0 ready (the whole recording if it ends earlier; 1.0 if that is 0)
+-- a value that depends on the signal alone, not on the push sizes, read back from the device once.  With a float ``norm``
+the host waits for the device only in the copy of the emitted samples, with ``as_tensor=True`` never (beyond what one
+``enhance_long`` sampler call does).
+
+Out of scope: rows of several sessions pooled into one sampler call, ``--streams`` lanes, several GPUs, resampling,
+several channels, noise that is not keyed, and any CPU or oracle path -- the oracle composition is ``enhance_long``'s, and
+this module is pinned to ``enhance_long``.
+"""
+import numpy as np
+import torch
+
+from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, plan_chunks
+
+HOP, PADC = 128, 255                # hop_length and n_fft // 2 of the released STFT, the only one the kernels cover
+KEEP = PADC + 1                     # samples kept before the next chunk's first frame centre (module docstring)
+
+
+def _ready_at(k, Tc, hop):
+    """``n_k``: the sample count at which chunk ``k`` is ready."""
+    return HOP * (k * hop + Tc - 1) + PADC
+
+
+def live_plan(n_samples, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES, finished=False):
+    """``(chunks_ready, samples_final)`` after ``n_samples`` samples of a recording (module docstring): how many chunks a
+    ``LiveEnhancer`` has sampled and how many output samples it has returned.  ``finished``: the recording has ended at
+    ``n_samples`` -- all ``K`` chunks, all samples.  Host arithmetic only; geometry errors are ``plan_chunks``'."""
+    n = int(n_samples)
+    if n < 0:
+        raise ValueError(f"live_plan: n_samples must be >= 0, got {n}")
+    _, hop, _ = plan_chunks(1, Tc, To)
+    if finished:
+        return plan_chunks(n // HOP + 1, Tc, To)[0], n
+    n0 = _ready_at(0, int(Tc), hop)
+    if n < n0:
+        return 0, 0
+    ready = (n - n0) // (HOP * hop) + 1
+    return ready, HOP * ready * hop - PADC
+
+
+PCM_FORMATS = {"s16le": 2, "f32le": 4}                    # bytes per sample
+
+
+def pcm_decode(data, fmt):
+    """Raw little-endian mono PCM -> float32 samples.  ``s16le``: value / 32768; ``f32le``: the values themselves.  Bytes
+    past the last whole sample are ignored."""
+    width = PCM_FORMATS[fmt]
+    data = data[:len(data) - len(data) % width]
+    if fmt == "f32le":
+        return np.frombuffer(data, dtype="<f4").astype(np.float32)
+    return np.frombuffer(data, dtype="<i2").astype(np.float32) / np.float32(32768.0)
+
+
+def pcm_encode(x, fmt):
+    """float32 samples -> raw little-endian mono PCM.  ``s16le``: ``x * 32768`` rounded to nearest (ties to even) and
+    saturated to [-32768, 32767], so that decode -> encode returns the bytes; a sample that is not finite becomes 0.
+    ``f32le``: the values themselves."""
+    x = np.asarray(x, dtype=np.float32)
+    if fmt == "f32le":
+        return x.astype("<f4").tobytes()
+    if fmt != "s16le":
+        raise KeyError(fmt)
+    v = np.rint(x.astype(np.float64) * 32768.0)
+    v = np.where(np.isfinite(v), v, 0.0)
+    return np.clip(v, -32768.0, 32767.0).astype("<i2").tobytes()
+
+
+def latency_samples(Tc=CHUNK_FRAMES):
+    """Worst algorithmic latency ``max_k (n_k - E_{k-1}) = 128 Tc + 382`` samples; it does not depend on the overlap."""
+    return HOP * int(Tc) + 382
+
+
+class LiveEnhancer:
+    """One recording, enhanced as it arrives (module docstring).  ``model``: a HIP-backed ``VFModel`` on ``device`` (default:
+    the current one); ``key`` / ``seed``: the keyed noise stream, as ``enhance_long``'s ``noise_key`` / ``noise_seed``;
+    ``norm``: a positive float or ``"first"``.  The precision is the model's (``model.dnn.set_precision``)."""
+
+    def __init__(self, model, *, norm, key, seed=0, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES, N=5, T_rev=1.0,
+                 t_eps=0.03, odesolver="euler", device=None):
+        _, self.hop, _ = plan_chunks(1, chunk_frames, overlap_frames)
+        self.Tc, self.To = int(chunk_frames), int(overlap_frames)
+        if key is None:
+            raise ValueError("LiveEnhancer: key is required (keyed noise only; util.noise.utterance_key makes one)")
+        if isinstance(norm, str):
+            if norm != "first":
+                raise ValueError(f"LiveEnhancer: norm is a positive float or 'first', got {norm!r}")
+        elif not (float(norm) > 0.0 and np.isfinite(float(norm))):
+            raise ValueError(f"LiveEnhancer: norm is a positive float or 'first', got {norm!r}")
+        dm = getattr(model, "data_module", None)
+        dnn = getattr(model, "dnn", None)
+        if not (torch.cuda.is_available() and callable(getattr(model, "rk_sample_", None)) and hasattr(dnn, "reserve")):
+            raise RuntimeError("flowmse_amd.live runs on the MI355X HIP kernels only: a HIP-backed VFModel on a 'cuda' device "
+                               "(there is no CPU fallback)")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"flowmse_amd.live runs on the MI355X HIP kernels only, got device {self.device} (there is no "
+                               "CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if not (hasattr(dm, "fused_ok") and dm.fused_ok(torch.empty(0, device=self.device))):
+            raise RuntimeError("flowmse_amd.live needs the HIP spectrogram kernels: the released STFT configuration (n_fft 510, "
+                               "hop 128, hann, 'exponent')")
+        self.model, self._dm = model, dm
+        self._norm_arg = norm if isinstance(norm, str) else float(norm)
+        self._solver = dict(N=int(N), T_rev=T_rev, t_eps=t_eps)
+        self._odesolver, self._seed = odesolver, int(seed)
+        self._keep_two = self.Tc - 2 * self.To < 3          # To = Tc / 2: the emitted range reaches a blended frame of chunk k-1
+        with torch.cuda.device(self.device):
+            dnn.reserve(1, 256, self.Tc)
+        self._buf = torch.empty(0, dtype=torch.float32, device=self.device)
+        self.reset(key)
+
+    # ---- public state -----------------------------------------------------------------------------------------
+    @property
+    def latency_samples(self):
+        return latency_samples(self.Tc)
+
+    def state_bytes(self):
+        """Device bytes this object holds between pushes: the sample buffer (its capacity) and the previous chunks.  No
+        output is pending between calls.  The model's workspace is the model's (``reserve(1, 256, Tc)``)."""
+        kept = [c for c in (self._prev, self._prev2) if c is not None]
+        return self._buf.numel() * 4 + sum(c.numel() * 8 for c in kept)
+
+    def reset(self, key=None):
+        """Forget the recording (the buffer keeps its capacity); ``key``: the next recording's, default the same one."""
+        if key is not None:
+            self.key = int(key)
+        self.samples_in = self.samples_out = 0
+        self._s0 = self._n = 0                              # the buffer holds samples [s0, s0 + n) of the recording
+        self._k = 0                                         # next chunk to sample
+        self._prev = self._prev2 = None
+        self._finished = False
+        self.norm = None if isinstance(self._norm_arg, str) else self._norm_arg
+
+    # ---- feeding ----------------------------------------------------------------------------------------------
+    def push(self, samples, as_tensor=False):
+        """Append ``samples`` (float32, 1-D or [1, n], n >= 0: numpy, CPU tensor or device tensor) and return the enhanced
+        samples that became final: float32 numpy (possibly empty), or with ``as_tensor`` a 1-D device tensor."""
+        if self._finished:
+            raise RuntimeError("LiveEnhancer.push after finish(): call reset() to start another recording")
+        self._append(samples)
+        out = []
+        with torch.cuda.device(self.device):
+            while self.samples_in >= _ready_at(self._k, self.Tc, self.hop):
+                out.append(self._chunk(self._k, None))
+        return self._deliver(out, as_tensor)
+
+    def finish(self, as_tensor=False):
+        """The recording has ended: sample what was waiting and return the remaining samples up to ``L = samples_in``."""
+        if self._finished:
+            raise RuntimeError("LiveEnhancer.finish called twice: call reset() to start another recording")
+        L = self.samples_in
+        if L <= PADC:
+            raise ValueError(f"LiveEnhancer.finish: a recording needs more than {PADC} samples (n_fft // 2 of the centred "
+                             f"STFT), got {L}")
+        K = plan_chunks(L // HOP + 1, self.Tc, self.To)[0]
+        out = []
+        with torch.cuda.device(self.device):
+            if K == 1:                                      # chunk 0 never became ready: enhance_waveform's one padded row
+                out.append(self._single(L))
+            else:
+                while self._k < K:
+                    out.append(self._chunk(self._k, L, last=self._k == K - 1))
+        self._finished = True
+        self._prev = self._prev2 = None
+        self._s0 += self._n
+        self._n = 0
+        return self._deliver(out, as_tensor)
+
+    # ---- internals --------------------------------------------------------------------------------------------
+    def _append(self, samples):
+        if isinstance(samples, np.ndarray):
+            samples = torch.from_numpy(np.ascontiguousarray(samples))
+        if not torch.is_tensor(samples) or samples.dtype != torch.float32:
+            raise TypeError("LiveEnhancer.push takes float32 samples (numpy array or tensor), got "
+                            f"{getattr(samples, 'dtype', type(samples).__name__)}")
+        if samples.dim() == 2 and samples.size(0) == 1:
+            samples = samples[0]
+        if samples.dim() != 1:
+            raise ValueError(f"LiveEnhancer.push takes one channel, 1-D or [1, n], got {tuple(samples.shape)}")
+        n = samples.numel()
+        if n == 0:
+            return
+        if self._n + n > self._buf.numel():                 # grow once per new largest push; contents move to the front
+            grown = torch.empty(self._n + n, dtype=torch.float32, device=self.device)
+            grown[:self._n] = self._buf[:self._n]
+            self._buf = grown
+        self._buf[self._n:self._n + n] = samples.to(self.device)
+        self._n += n
+        self.samples_in += n
+
+    def _normalised(self, lo, hi):
+        """Samples [lo, hi) of the recording divided by ``norm`` as ``enhance_long`` divides them: on the device, one
+        elementwise torch division by the Python float."""
+        if self.norm is None:                               # norm="first": the peak of [0, n_0), or of all there is
+            n0 = min(_ready_at(0, self.Tc, self.hop), self.samples_in)
+            peak = self._buf[:n0].abs().max().item()
+            self.norm = peak if peak > 0.0 else 1.0
+        return self._buf[lo - self._s0:hi - self._s0] / self.norm
+
+    def _sample(self, Y, frame0):
+        from flowmse_amd.sampling import get_white_box_solver
+        kw = dict(noise_keys=[self.key], noise_seed=self._seed)
+        if frame0 is not None:
+            kw["noise_frame0"] = [frame0]
+        return get_white_box_solver(self._odesolver, self.model.ode, self.model, Y=Y, Y_prior=Y, **self._solver, **kw)()[0]
+
+    def _stft(self, lo, hi, frame0, Tc, L_total):
+        from flowmse_amd import _lib
+        win = self._normalised(lo, hi)
+        Y = torch.empty(1, 1, 256, Tc, dtype=torch.complex64, device=self.device)
+        _lib.check(_lib.lib.flowse_stft_compress_window(_lib.ptr(win), lo, hi - lo, 1.0, frame0, Tc, L_total, _lib.ptr(Y),
+                                                        float(self._dm.spec_factor), float(self._dm.spec_abs_exponent),
+                                                        _lib.current_stream()))
+        return Y
+
+    def _istft(self, prev2, prev, cur, k, Tc, hop, last, L, e0, e1):
+        from flowmse_amd import _lib
+        out = torch.empty(e1 - e0, dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib.flowse_istft_decompress_window(_lib.ptr(prev2), _lib.ptr(prev), _lib.ptr(cur), k, Tc, hop,
+                                                           int(last), L, float(self._dm.spec_factor),
+                                                           float(self._dm.spec_abs_exponent), _lib.ptr(out), e0, e1 - e0,
+                                                           float(self.norm), _lib.current_stream()))
+        return out
+
+    def _chunk(self, k, L, last=False):
+        """Sample chunk ``k`` (``L`` None: the recording is open) and return the samples that became final with it."""
+        Tc, hop = self.Tc, self.hop
+        lo = max(HOP * k * hop - PADC, 0)
+        hi = _ready_at(k, Tc, hop) if L is None else min(_ready_at(k, Tc, hop), L)
+        if L is not None:                                   # the right reflection may read one sample before the first frame
+            lo = max(min(lo, L - KEEP), self._s0)
+        cur = self._sample(self._stft(lo, hi, k * hop, Tc, -1 if L is None else L), k * hop)
+        e0 = self.samples_out
+        e1 = L if last else HOP * (k + 1) * hop - PADC
+        out = self._istft(self._prev2, self._prev, cur, k, Tc, hop, last, L if last else 0, e0, e1)
+        self.samples_out = e1
+        self._prev2, self._prev = (self._prev if self._keep_two else None), cur
+        self._k = k + 1
+        self._drop(max(HOP * (k + 1) * hop - KEEP, 0))
+        return out
+
+    def _single(self, L):
+        """K = 1: one row of ``T`` padded to a multiple of 64, the keyed stream from frame 0, every padded frame in the
+        overlap-add -- ``enhance_waveform``'s computation through the window entries."""
+        Tpad = -(-(L // HOP + 1) // 64) * 64
+        cur = self._sample(self._stft(0, L, 0, Tpad, L), None)
+        out = self._istft(None, None, cur, 0, Tpad, Tpad, True, L, 0, L)
+        self.samples_out = L
+        self._k = 1
+        return out
+
+    def _drop(self, upto):
+        """Forget the samples before ``upto``: the rest moves to the front of the same buffer."""
+        cut = min(upto, self._s0 + self._n) - self._s0
+        if cut <= 0:
+            return
+        rest = self._buf[cut:self._n].clone()
+        self._buf[:rest.numel()] = rest
+        self._s0 += cut
+        self._n -= cut
+
+    def _deliver(self, out, as_tensor):
+        if not out:
+            return torch.empty(0, dtype=torch.float32, device=self.device) if as_tensor else np.empty(0, dtype=np.float32)
+        x = out[0] if len(out) == 1 else torch.cat(out)
+        return x if as_tensor else x.cpu().numpy()

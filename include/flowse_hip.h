@@ -333,6 +333,32 @@ int flowse_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, void* 
 int flowse_istft_decompress_stacks(const void* chunks_c64, int S, int K, int Tc, int hop, float factor, float exponent,
                                    float* out, int Lout, float scale_out, void* stream);
 
+/* ---- windows of a recording that is still arriving (opt-in: flowmse_amd.live, `enhance --live`) ------------------
+ * The chunk calls above on what a live session holds: a window of the samples and the last chunks it sampled.  Stateless;
+ * all sample, frame and chunk indices are 64-bit.  Both calls only enqueue on `stream`; they allocate nothing and do not
+ * synchronise.  Null buf / out_c64 / cur_c64 / out -> FLOWSE_ERR_ARG; every FLOWSE_ERR_SHAPE below is answered before any
+ * launch, with the values in flowse_last_error(), and leaves the output untouched.
+ * flowse_stft_compress_window: buf float32 [n] holds samples [s0, s0 + n) of the recording -> the ONE row complex64
+ * [1,1,256,Tc] of frames [frame0, frame0 + Tc), computed by the per-frame code of the calls above: with frame0 = k hop it is
+ * row k of flowse_stft_compress_chunks on the whole recording, bit for bit.  L_total = -1 while the recording is open: no
+ * right reflection, no zero frames.  L_total >= 0 (> 255, >= s0 + n) once it has ended: frames >= L_total / 128 + 1 are
+ * zero and the frames over the end reflect about sample L_total - 1, as in every other call.  A sample index a frame needs
+ * that lies outside the window -> FLOWSE_ERR_SHAPE: the reflection about sample 0 (frames 0 and 1) needs s0 == 0, an open
+ * recording needs 128 (frame0 + Tc - 1) + 254 < s0 + n.
+ * flowse_istft_decompress_window: the output samples [e0, e0 + n_out) of flowse_istft_decompress_chunks on the whole stack,
+ * bit for bit, from the chunks k-2 (prev2_c64), k-1 (prev_c64) and k (cur_c64), each complex64 [1,256,Tc]; a chunk the range
+ * does not read may be null.  last != 0: chunk k is the recording's last (K = k + 1, Tg = k hop + Tc) and L its length,
+ * e0 + n_out <= L <= 128 (Tg - 1) + 255; last == 0: L is not read, and frames from (k + 1) hop on are not final (they wait
+ * for chunk k + 1).  The samples [128 k hop - 255, 128 (k + 1) hop - 255) that become final with chunk k lie under frames
+ * from k hop - 3 on; the seam rule takes those from chunks k - 1 and k when Tc - 2 To >= 3, and from chunk k - 2 as well
+ * when To = Tc / 2 (frames k hop - 3 .. k hop - 1 are then blended frames of chunk k - 1).  A range under a frame that needs
+ * a chunk other than those given -> FLOWSE_ERR_SHAPE.  1 <= hop <= Tc <= 2 hop, k <= 2^40, 1 <= n_out <= 2^30. */
+int flowse_stft_compress_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t frame0, int Tc,
+                                int64_t L_total, void* out_c64, float factor, float exponent, void* stream);
+int flowse_istft_decompress_window(const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k, int Tc,
+                                   int hop, int last, int64_t L, float factor, float exponent, float* out, int64_t e0,
+                                   int64_t n_out, float scale_out, void* stream);
+
 /* ---- ensembles of draws (opt-in: flowmse_amd.ensemble, `--samples D`; NOT the reference's computation, which draws once)
  * flowse_istft_decompress_ensemble: flowse_istft_decompress_stacks over D draws per stack.  Chunk k of draw d of stack s is
  * row s * stack_stride + d * draw_stride + k of chunks_c64 (rows of 256 * Tc complex64 values; offsets in 64 bits).  The
