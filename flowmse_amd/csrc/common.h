@@ -8,8 +8,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-struct flowse_spec_row;   // include/flowse_hip.h
-
 namespace flowse {
 
 // status codes of the C ABI (include/flowse_hip.h)
@@ -480,41 +478,5 @@ int launch_linear(const float* in, int B, int K, const float* W, const float* bi
 int launch_head(const float* pyr4, const float* t, const float* Wout /*[2][4]*/, const float* bout /*[2]*/,
                 int B, int F, int T, int mode, const float* x_c64, float dt, float* out_c64, hipStream_t s,
                 const CallBlock* cb = nullptr);
-// fused STFT + compression (-> complex64 [B,1,256,Tpad], frames >= T zeroed) and decompression + iSTFT
-int launch_stft_compress(const float* sig, int B, int L, float scale_in, float* out_c64, int T, int Tpad, float factor,
-                         float exponent, hipStream_t s);
-int launch_istft_decompress(const float* spec_c64, int B, int T, int Tpad, float factor, float exponent, float* out,
-                            int Lout, float scale_out, hipStream_t s);
-// the same pair for ONE recording held as K chunks [K,1,256,Tc] that start `hop` frames apart: chunk rows are slices of
-// the recording's spectrogram (frames past L / 128 + 1 zero); synthesis cross-fades the Tc - hop shared frames
-int launch_stft_compress_chunks(const float* sig, int L, float scale_in, float* out_c64, int K, int Tc, int hop,
-                                float factor, float exponent, hipStream_t s);
-int launch_istft_decompress_chunks(const float* chunks_c64, int K, int Tc, int hop, float factor, float exponent,
-                                   float* out, int Lout, float scale_out, hipStream_t s);
-// the chunk synthesis for S stacks of one geometry in one launch: [S][K][256][Tc] -> [S][Lout]
-int launch_istft_decompress_stacks(const float* chunks_c64, int S, int K, int Tc, int hop, float factor, float exponent,
-                                   float* out, int Lout, float scale_out, hipStream_t s);
-// the stack synthesis over D draws per stack: the mean of the draws' linear spectra -> [S][Lout], and (tracks != null,
-// D >= 2) the per-frame deviation and power tracks [S][2][Tg]; row of (s, d, k) = s stack_stride + d draw_stride + k
-int launch_istft_decompress_ensemble(const float* chunks_c64, int S, int D, int K, int Tc, int hop, int64_t stack_stride,
-                                     int64_t draw_stride, float factor, float exponent, float* out, int Lout,
-                                     float scale_out, float* tracks, hipStream_t s);
-// the R rows [R,1,256,Tw] of one sampler call from up to FLOWSE_MAX_SPEC_ROWS signals; `rows`: HOST table
-int launch_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, float* out_c64, float factor, float exponent,
-                              hipStream_t s);
-// the same per-frame and per-sample code on a WINDOW of a recording that is still arriving (flowmse_amd.live): one row of
-// frames [frame0, frame0 + Tc) from the samples [s0, s0 + n); the output samples [e0, e0 + n_out) from chunks k-2, k-1, k
-int launch_stft_compress_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t frame0, int Tc,
-                                int64_t L_total, float* out_c64, float factor, float exponent, hipStream_t s);
-int launch_istft_decompress_window(const float* prev2_c64, const float* prev_c64, const float* cur_c64, int64_t k, int Tc,
-                                   int hop, int last, int64_t L, float factor, float exponent, float* out, int64_t e0,
-                                   int64_t n_out, float scale_out, hipStream_t s);
-// out = y + sigma * z   (complex64 as float pairs)
-int launch_axpy(const float* y, const float* z, float sigma, int64_t n, float* out, hipStream_t s);
-// out = y + sigma * z (y != null) or out = z (y == null), z = the keyed Philox noise of noise.hip; [B,1,F,T] complex64,
-// T even, 16-byte aligned pointers, keys: B device words; frame0 (may be null): B device words, the even absolute frame
-// each row starts at
-int launch_keyed_noise(const float* y, const uint64_t* keys, const int32_t* frame0, uint64_t seed, float sigma, float* out,
-                       int B, int F, int T, hipStream_t s);
 
 }  // namespace flowse

@@ -243,20 +243,18 @@ int flowse_fm_loss(flowse_model* m, const void* x0, const void* y, const float* 
     float* xt = reinterpret_cast<float*>(m->d_fm.p);
     float* v = reinterpret_cast<float*>(m->d_fm.p + state);
     double* partial = reinterpret_cast<double*>(m->d_fm.p + 2 * state);
-    hipStream_t caller = static_cast<hipStream_t>(stream), s = nullptr;
-    rc = enter_stream(m, caller, &s);
-    if (rc != OK) return rc;
     const float* x0f = static_cast<const float*>(x0);
     const float* yf = static_cast<const float*>(y);
     const float* zf = static_cast<const float*>(z);
-    rc = launch_fm_pair(x0f, yf, t_dev, zf, keys_dev, seed, sigma_min, sigma_max, xt, nullptr, B, F, T, s);
-    if (rc == OK) rc = launch_set_call(m->d_call, CallBlock{xt, yf, t_dev, v, 1, 0.f}, s);
-    if (rc == OK) rc = exec_plan(m, p, s);
-    if (rc == OK)
-        rc = launch_fm_loss_rows(v, x0f, yf, zf, keys_dev, seed, sigma_min, sigma_max, loss_type == FLOWSE_LOSS_MAE, out,
-                                 partial, B, F, T, s);
-    const int rc2 = leave_stream(m, caller, s);
-    return rc != OK ? rc : rc2;
+    return on_handle_stream(m, stream, [&](hipStream_t s) {
+        rc = launch_fm_pair(x0f, yf, t_dev, zf, keys_dev, seed, sigma_min, sigma_max, xt, nullptr, B, F, T, s);
+        if (rc == OK) rc = launch_set_call(m->d_call, CallBlock{xt, yf, t_dev, v, 1, 0.f}, s);
+        if (rc == OK) rc = exec_plan(m, p, s);
+        if (rc == OK)
+            rc = launch_fm_loss_rows(v, x0f, yf, zf, keys_dev, seed, sigma_min, sigma_max, loss_type == FLOWSE_LOSS_MAE,
+                                     out, partial, B, F, T, s);
+        return rc;
+    });
 }
 
 }  // extern "C"

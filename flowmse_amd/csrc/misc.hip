@@ -1,4 +1,6 @@
-// Small HBM-bound / latency-bound kernels around the network body.
+// Small HBM-bound / latency-bound kernels around the network body, and the C-ABI entries of the prior sample
+// (flowse_prior_sample, flowse_axpy).
+#include "../../include/flowse_hip.h"
 #include "common.h"
 
 namespace flowse {
@@ -208,10 +210,30 @@ __global__ __launch_bounds__(256) void axpy_kernel(const float* __restrict__ y, 
         out[i] = y[i] + __fmul_rn(z[i], sigma);
 }
 
-int launch_axpy(const float* y, const float* z, float sigma, int64_t n, float* out, hipStream_t s) {
+// out = y + sigma * z   (complex64 as float pairs)
+static int launch_axpy(const float* y, const float* z, float sigma, int64_t n, float* out, hipStream_t s) {
     hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n)), dim3(256), 0, s, y, z, sigma, n, out);
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }
 
 }  // namespace flowse
+
+using namespace flowse;
+
+extern "C" {
+
+int flowse_prior_sample(const void* y, const void* z, float sigma, void* x_out, int64_t numel_complex, void* stream) {
+    if (!y || !z || !x_out || numel_complex < 0) {
+        set_error("flowse_prior_sample: bad argument");
+        return ERR_ARG;
+    }
+    return launch_axpy(static_cast<const float*>(y), static_cast<const float*>(z), sigma, 2 * numel_complex,
+                       static_cast<float*>(x_out), static_cast<hipStream_t>(stream));
+}
+
+int flowse_axpy(const void* x, const void* k, float dt, void* out, int64_t numel_complex, void* stream) {
+    return flowse_prior_sample(x, k, dt, out, numel_complex, stream);
+}
+
+}  // extern "C"

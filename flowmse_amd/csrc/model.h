@@ -1,4 +1,5 @@
-// Internal types of the model handle: NCSN++ module list, parameter table, launch plan (model_*.hip).
+// Internal types of the model handle: NCSN++ module list, parameter table, launch plan (model_*.hip), and the six
+// functions through which the entries that live beside their kernels reach the handle (at the end).
 #pragma once
 #include <cmath>
 #include <cstdarg>
@@ -250,10 +251,27 @@ int storage_type_for(const flowse_model* m);
 // model_plan.hip
 int build_plan(flowse_model* m, Plan* plan, int B, int F, int T);
 int build_block_plan(flowse_model* m, Plan* plan, int B, int H, int W, int C1);
-// model_api.hip: plan lookup / execution and the stream fence shared by every C-ABI sampler
+// model_api.hip, the handle proper: life cycle, weight upload, plan lookup and execution, the stream fence, the profiler.
+// These six functions are all that the entries of the other files (rk_fixed.hip, rk45.hip, fmloss.hip) see of it:
+// get_plan also grows the workspace (it may synchronise the device); exec_plan may replay a captured graph, run_plan
+// always issues plain launches; ensure_stream makes the handle's internal stream and its two fence events.
 int get_plan(flowse_model* m, int B, int F, int T, Plan** out);
 int exec_plan(flowse_model* m, Plan* p, hipStream_t s);
+int run_plan(flowse_model* m, Plan* p, hipStream_t s);
+int ensure_stream(flowse_model* m);
 int enter_stream(flowse_model* m, hipStream_t caller, hipStream_t* work);
 int leave_stream(flowse_model* m, hipStream_t caller, hipStream_t work);
+
+// The stream scope of one C-ABI call: body(s) runs between enter_stream and leave_stream, on the stream enter_stream
+// chose.  Returns the body's error if there is one, otherwise leave_stream's.  Whatever may synchronise or allocate
+// (get_plan, every reserve) belongs before the scope.
+template <class Fn>
+inline int on_handle_stream(flowse_model* m, void* stream, Fn body) {
+    hipStream_t caller = static_cast<hipStream_t>(stream), s = nullptr;
+    if (const int rc = enter_stream(m, caller, &s)) return rc;
+    const int rc = body(s);
+    const int rc2 = leave_stream(m, caller, s);
+    return rc != OK ? rc : rc2;
+}
 
 }  // namespace flowse

@@ -9,6 +9,11 @@
 //   words (0, 1) -> the value at the even frame t, words (2, 3) -> the value at t + 1
 //   u1 = ((w_a >> 9) + 0.5) * 2^-23 in (0, 1),  u2 = (w_b >> 8) * 2^-24 in [0, 1)      (both exact in fp32)
 //   z  = sqrtf(-logf(u1)) * (cospif(2 u2) + i sinpif(2 u2))                                (E|z|^2 = 1)
+//
+// The four keyed entries of the C ABI (flowse_prior_sample_keyed[_at], flowse_op_keyed_noise[_at]) are at the end.
+#include <vector>
+
+#include "../../include/flowse_hip.h"
 #include "noise.h"
 
 namespace flowse {
@@ -47,8 +52,11 @@ static void launch_one(unsigned blocks, hipStream_t s, const float* y, const uin
                        keys, frame0, lo, hi, sigma, F, Th, n, reinterpret_cast<float4*>(out));
 }
 
-int launch_keyed_noise(const float* y, const uint64_t* keys, const int32_t* frame0, uint64_t seed, float sigma, float* out,
-                       int B, int F, int T, hipStream_t s) {
+// out = y + sigma * z (y != null) or out = z (y == null), z = the keyed Philox noise of noise.hip; [B,1,F,T] complex64,
+// T even, 16-byte aligned pointers, keys: B device words; frame0 (may be null): B device words, the even absolute frame
+// each row starts at
+static int launch_keyed_noise(const float* y, const uint64_t* keys, const int32_t* frame0, uint64_t seed, float sigma,
+                              float* out, int B, int F, int T, hipStream_t s) {
     const int Th = T / 2;
     const int64_t n = (int64_t)B * F * Th;
     int64_t blocks = (n + 255) / 256;
@@ -64,3 +72,70 @@ int launch_keyed_noise(const float* y, const uint64_t* keys, const int32_t* fram
 }
 
 }  // namespace flowse
+
+using namespace flowse;
+
+extern "C" {
+
+static int keyed_args_ok(const char* who, const void* y, bool need_y, const uint64_t* keys, const void* out, int B, int F,
+                         int T) {
+    if ((need_y && !y) || !keys || !out || B <= 0 || F <= 0 || T <= 0 || (T & 1)) {
+        set_error("%s: bad argument (null pointer, B / F / T <= 0 or odd T; got B=%d F=%d T=%d)", who, B, F, T);
+        return ERR_ARG;
+    }
+    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15) {
+        set_error("%s: y and the output must be 16-byte aligned", who);
+        return ERR_ARG;
+    }
+    return OK;
+}
+
+int flowse_prior_sample_keyed(const void* y, const uint64_t* keys_dev, uint64_t seed, float sigma, void* x_out, int B, int F,
+                              int T, void* stream) {
+    if (const int rc = keyed_args_ok("flowse_prior_sample_keyed", y, true, keys_dev, x_out, B, F, T)) return rc;
+    return launch_keyed_noise(static_cast<const float*>(y), keys_dev, nullptr, seed, sigma, static_cast<float*>(x_out), B,
+                              F, T, static_cast<hipStream_t>(stream));
+}
+
+int flowse_op_keyed_noise(const uint64_t* keys_dev, uint64_t seed, void* z_out_c64, int B, int F, int T, void* stream) {
+    if (const int rc = keyed_args_ok("flowse_op_keyed_noise", nullptr, false, keys_dev, z_out_c64, B, F, T)) return rc;
+    return launch_keyed_noise(nullptr, keys_dev, nullptr, seed, 0.f, static_cast<float*>(z_out_c64), B, F, T,
+                              static_cast<hipStream_t>(stream));
+}
+
+// The frame offsets of the *_at calls are read back and checked here, on the host side of the call (one stream
+// synchronisation): an odd offset would pair the Philox words of a frame differently than the offset-free stream does.
+static int frame0_ok(const char* who, const int32_t* frame0_dev, int B, int T, hipStream_t s) {
+    if (!frame0_dev) {
+        set_error("%s: null frame0_dev", who);
+        return ERR_ARG;
+    }
+    std::vector<int32_t> h((size_t)B);
+    FLOWSE_HIP(hipMemcpyAsync(h.data(), frame0_dev, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    FLOWSE_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b)
+        if (h[b] < 0 || (h[b] & 1) || h[b] > INT32_MAX - T) {
+            set_error("%s: frame0[%d] = %d must be even, >= 0 and <= INT32_MAX - T", who, b, (int)h[b]);
+            return ERR_ARG;
+        }
+    return OK;
+}
+
+int flowse_prior_sample_keyed_at(const void* y, const uint64_t* keys_dev, const int32_t* frame0_dev, uint64_t seed,
+                                 float sigma, void* x_out, int B, int F, int T, void* stream) {
+    if (const int rc = keyed_args_ok("flowse_prior_sample_keyed_at", y, true, keys_dev, x_out, B, F, T)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = frame0_ok("flowse_prior_sample_keyed_at", frame0_dev, B, T, s)) return rc;
+    return launch_keyed_noise(static_cast<const float*>(y), keys_dev, frame0_dev, seed, sigma, static_cast<float*>(x_out),
+                              B, F, T, s);
+}
+
+int flowse_op_keyed_noise_at(const uint64_t* keys_dev, const int32_t* frame0_dev, uint64_t seed, void* z_out_c64, int B,
+                             int F, int T, void* stream) {
+    if (const int rc = keyed_args_ok("flowse_op_keyed_noise_at", nullptr, false, keys_dev, z_out_c64, B, F, T)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = frame0_ok("flowse_op_keyed_noise_at", frame0_dev, B, T, s)) return rc;
+    return launch_keyed_noise(nullptr, keys_dev, frame0_dev, seed, 0.f, static_cast<float*>(z_out_c64), B, F, T, s);
+}
+
+}  // extern "C"

@@ -274,9 +274,7 @@ extern "C" int flowse_rk45_sample(flowse_model* m, void* x_inout, const void* y,
     if (rc == OK) rc = m->d_rk45.reserve(rk45_bytes(n), true);
     if (rc != OK) return rc;
     Rk45State st = carve(m->d_rk45, n);
-    hipStream_t caller = static_cast<hipStream_t>(stream), s = nullptr;
-    rc = enter_stream(m, caller, &s);
-    if (rc != OK) return rc;
+    hipStream_t s = nullptr;                                     // the stream scope at the end sets it, then runs solve()
 
     const float* const yy = static_cast<const float*>(y);
     float2* const x = static_cast<float2*>(x_inout);
@@ -419,15 +417,17 @@ extern "C" int flowse_rk45_sample(flowse_model* m, void* x_inout, const void* y,
         }
     };
 
-    rc = solve();
-    if (rc == OK) {
-        hipLaunchKernelGGL(dp_output_kernel, dim3(grid_of(n)), dim3(256), 0, s, st.y, x, n);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = hip_fail(e, "kernel launch", __FILE__, __LINE__);
-    }
-    *nfev_out = nfev;
-    *status_out = status;
-    *n_accepted = nacc;
-    const int rc2 = leave_stream(m, caller, s);
-    return rc != OK ? rc : rc2;
+    return on_handle_stream(m, stream, [&](hipStream_t work) {
+        s = work;
+        rc = solve();
+        if (rc == OK) {
+            hipLaunchKernelGGL(dp_output_kernel, dim3(grid_of(n)), dim3(256), 0, s, st.y, x, n);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) rc = hip_fail(e, "kernel launch", __FILE__, __LINE__);
+        }
+        *nfev_out = nfev;
+        *status_out = status;
+        *n_accepted = nacc;
+        return rc;
+    });
 }

@@ -346,8 +346,22 @@ __global__ __launch_bounds__(256) void ensemble_tracks_kernel(const float2* __re
     }
 }
 
-int launch_stft_compress(const float* sig, int B, int L, float scale_in, float* out_c64, int T, int Tpad, float factor,
-                         float exponent, hipStream_t s) {
+}  // namespace flowse
+
+using namespace flowse;
+
+// ================================================================================================ C ABI
+// Each entry: the null check (ERR_ARG), the shape checks (ERR_SHAPE), the launch.
+extern "C" {
+
+// fused STFT + compression (-> complex64 [B,1,256,Tpad], frames >= T zeroed) and decompression + iSTFT
+int flowse_stft_compress(const float* sig, int B, int L, float scale_in, void* out_c64, int T, int Tpad, float factor,
+                         float exponent, void* stream) {
+    if (!sig || !out_c64) {
+        set_error("flowse_stft_compress: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (L <= PADC || T != L / HOP + 1 || Tpad < T || B < 1 || B > 65535) {
         set_error("stft: need L > %d, T == L / %d + 1 (got L=%d T=%d Tpad=%d B=%d)", PADC, HOP, L, T, Tpad, B);
         return ERR_SHAPE;
@@ -367,8 +381,15 @@ static bool chunks_ok(int K, int Tc, int hop) {
            (int64_t)(K - 1) * hop + Tc <= (1 << 23);
 }
 
-int launch_stft_compress_chunks(const float* sig, int L, float scale_in, float* out_c64, int K, int Tc, int hop,
-                                float factor, float exponent, hipStream_t s) {
+// the same pair for ONE recording held as K chunks [K,1,256,Tc] that start `hop` frames apart: chunk rows are slices of
+// the recording's spectrogram (frames past L / 128 + 1 zero); synthesis cross-fades the Tc - hop shared frames
+int flowse_stft_compress_chunks(const float* sig, int L, float scale_in, void* out_c64, int K, int Tc, int hop, float factor,
+                                float exponent, void* stream) {
+    if (!sig || !out_c64) {
+        set_error("flowse_stft_compress_chunks: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
     const int T = L / HOP + 1;
     if (L <= PADC || !chunks_ok(K, Tc, hop) || (int64_t)(K - 1) * hop + Tc < T) {
         set_error("stft chunks: need L > %d, 1 <= hop <= Tc <= 2 hop, 1 <= K <= 65535 and (K - 1) hop + Tc >= L / %d + 1 "
@@ -384,8 +405,13 @@ int launch_stft_compress_chunks(const float* sig, int L, float scale_in, float* 
     return OK;
 }
 
-int launch_istft_decompress(const float* spec_c64, int B, int T, int Tpad, float factor, float exponent, float* out,
-                            int Lout, float scale_out, hipStream_t s) {
+int flowse_istft_decompress(const void* spec_c64, int B, int T, int Tpad, float factor, float exponent, float* out,
+                            int Lout, float scale_out, void* stream) {
+    if (!spec_c64 || !out) {
+        set_error("flowse_istft_decompress: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (T < 1 || Tpad < T || Lout < 1 || Lout > (T - 1) * HOP + NFFT - PADC || B < 1 || B > 65535 || factor == 0.f) {
         set_error("istft: bad shape T=%d Tpad=%d Lout=%d B=%d", T, Tpad, Lout, B);
         return ERR_SHAPE;
@@ -444,27 +470,48 @@ static int launch_istft_stacks(const char* who, const float* chunks_c64, int S, 
     return OK;
 }
 
-int launch_istft_decompress_chunks(const float* chunks_c64, int K, int Tc, int hop, float factor, float exponent,
-                                   float* out, int Lout, float scale_out, hipStream_t s) {
-    return launch_istft_stacks("chunks", chunks_c64, 1, 1, K, Tc, hop, K, 0, factor, exponent, out, Lout, scale_out, nullptr,
-                               s);
+int flowse_istft_decompress_chunks(const void* chunks_c64, int K, int Tc, int hop, float factor, float exponent, float* out,
+                                   int Lout, float scale_out, void* stream) {
+    if (!chunks_c64 || !out) {
+        set_error("flowse_istft_decompress_chunks: null argument");
+        return ERR_ARG;
+    }
+    return launch_istft_stacks("chunks", static_cast<const float*>(chunks_c64), 1, 1, K, Tc, hop, K, 0, factor, exponent, out,
+                               Lout, scale_out, nullptr, static_cast<hipStream_t>(stream));
 }
 
-int launch_istft_decompress_stacks(const float* chunks_c64, int S, int K, int Tc, int hop, float factor, float exponent,
-                                   float* out, int Lout, float scale_out, hipStream_t s) {
-    return launch_istft_stacks("stacks", chunks_c64, S, 1, K, Tc, hop, K, 0, factor, exponent, out, Lout, scale_out, nullptr,
-                               s);
+// the chunk synthesis for S stacks of one geometry in one launch: [S][K][256][Tc] -> [S][Lout]
+int flowse_istft_decompress_stacks(const void* chunks_c64, int S, int K, int Tc, int hop, float factor, float exponent,
+                                   float* out, int Lout, float scale_out, void* stream) {
+    if (!chunks_c64 || !out) {
+        set_error("flowse_istft_decompress_stacks: null argument");
+        return ERR_ARG;
+    }
+    return launch_istft_stacks("stacks", static_cast<const float*>(chunks_c64), S, 1, K, Tc, hop, K, 0, factor, exponent, out,
+                               Lout, scale_out, nullptr, static_cast<hipStream_t>(stream));
 }
 
-int launch_istft_decompress_ensemble(const float* chunks_c64, int S, int D, int K, int Tc, int hop, int64_t stack_stride,
+// the stack synthesis over D draws per stack: the mean of the draws' linear spectra -> [S][Lout], and (tracks != null,
+// D >= 2) the per-frame deviation and power tracks [S][2][Tg]; row of (s, d, k) = s stack_stride + d draw_stride + k
+int flowse_istft_decompress_ensemble(const void* chunks_c64, int S, int D, int K, int Tc, int hop, int64_t stack_stride,
                                      int64_t draw_stride, float factor, float exponent, float* out, int Lout,
-                                     float scale_out, float* tracks, hipStream_t s) {
-    return launch_istft_stacks("ensemble", chunks_c64, S, D, K, Tc, hop, stack_stride, draw_stride, factor, exponent, out,
-                               Lout, scale_out, tracks, s);
+                                     float scale_out, float* tracks, void* stream) {
+    if (!chunks_c64 || !out) {
+        set_error("flowse_istft_decompress_ensemble: null argument");
+        return ERR_ARG;
+    }
+    return launch_istft_stacks("ensemble", static_cast<const float*>(chunks_c64), S, D, K, Tc, hop, stack_stride, draw_stride,
+                               factor, exponent, out, Lout, scale_out, tracks, static_cast<hipStream_t>(stream));
 }
 
-int launch_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, float* out_c64, float factor, float exponent,
-                              hipStream_t s) {
+// the R rows [R,1,256,Tw] of one sampler call from up to FLOWSE_MAX_SPEC_ROWS signals; `rows`: HOST table
+int flowse_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, void* out_c64, float factor, float exponent,
+                              void* stream) {
+    if (!rows || !out_c64) {
+        set_error("flowse_stft_compress_rows: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (R < 1 || R > FLOWSE_MAX_SPEC_ROWS || Tw < 1 || Tw > (1 << 23)) {
         set_error("stft rows: need 1 <= R <= %d and 1 <= Tw <= 2^23 (got R=%d Tw=%d)", FLOWSE_MAX_SPEC_ROWS, R, Tw);
         return ERR_SHAPE;
@@ -493,10 +540,17 @@ int launch_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, float*
 }
 
 // ---- windows of a recording that is still arriving (flowmse_amd.live) -------------------------------------------------
+// the same per-frame and per-sample code on a WINDOW of the recording: one row of frames [frame0, frame0 + Tc) from the
+// samples [s0, s0 + n); the output samples [e0, e0 + n_out) from chunks k-2, k-1, k
 constexpr int64_t WINDOW_MAX = (int64_t)1 << 40;        // frames and chunk indices: every product below stays in 64 bits
 
-int launch_stft_compress_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t frame0, int Tc,
-                                int64_t L_total, float* out_c64, float factor, float exponent, hipStream_t s) {
+int flowse_stft_compress_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t frame0, int Tc,
+                                int64_t L_total, void* out_c64, float factor, float exponent, void* stream) {
+    if (!buf || !out_c64) {
+        set_error("flowse_stft_compress_window: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
     const bool closed = L_total >= 0;
     if (s0 < 0 || n < 1 || s0 > WINDOW_MAX * HOP || n > WINDOW_MAX * HOP || frame0 < 0 || frame0 > WINDOW_MAX || Tc < 1 ||
         Tc > (1 << 23) || L_total < -1 || (closed && (L_total <= PADC || s0 + n > L_total))) {
@@ -538,9 +592,14 @@ int launch_stft_compress_window(const float* buf, int64_t s0, int64_t n, float s
     return OK;
 }
 
-int launch_istft_decompress_window(const float* prev2_c64, const float* prev_c64, const float* cur_c64, int64_t k, int Tc,
+int flowse_istft_decompress_window(const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k, int Tc,
                                    int hop, int last, int64_t L, float factor, float exponent, float* out, int64_t e0,
-                                   int64_t n_out, float scale_out, hipStream_t s) {
+                                   int64_t n_out, float scale_out, void* stream) {
+    if (!cur_c64 || !out) {
+        set_error("flowse_istft_decompress_window: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (k < 0 || k > WINDOW_MAX || Tc < 1 || Tc > (1 << 23) || hop < 1 || hop > Tc || 2 * (int64_t)hop < Tc || e0 < 0 ||
         n_out < 1 || n_out > ((int64_t)1 << 30) || e0 > WINDOW_MAX * HOP || factor == 0.f) {
         set_error("istft window: need 0 <= k <= 2^40, 1 <= hop <= Tc <= 2 hop, Tc <= 2^23, e0 >= 0, 1 <= n_out <= 2^30 and "
@@ -595,4 +654,4 @@ int launch_istft_decompress_window(const float* prev2_c64, const float* prev_c64
     return OK;
 }
 
-}  // namespace flowse
+}  // extern "C"

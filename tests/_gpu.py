@@ -21,18 +21,26 @@ def stream():
     return _lib.current_stream()
 
 
-def conv2d(x1, w, bias=None, x2=None, bias2=None, res=None, scale=1.0, padding=None, splitk=False):
-    """x*: NCHW cpu tensors; w: [Cout, Cin, k, k] (reference layout). Returns NCHW cpu."""
-    Cout, Cin, k, _ = w.shape
-    taps = k * k
+def conv_operands(x1, x2, w, taps, bias, bias2, res):
+    """What every conv entry takes, on the device: the NHWC inputs (x2 may be None), w [Cout, Cin, k, k] packed as
+    [Cout][taps][Cin], the bias, the per-sample bias table and the NHWC residual (each may be None)."""
+    Cout, Cin = w.shape[:2]
     a1 = nhwc(x1)
     a2 = nhwc(x2) if x2 is not None else None
-    B, H, W, C1 = a1.shape
-    C2 = a2.shape[3] if a2 is not None else 0
     wp = w.permute(0, 2, 3, 1).reshape(Cout, taps, Cin).contiguous().cuda()
     bb = bias.contiguous().cuda() if bias is not None else None
     b2 = bias2.contiguous().cuda() if bias2 is not None else None
     rr = nhwc(res) if res is not None else None
+    return a1, a2, wp, bb, b2, rr
+
+
+def conv2d(x1, w, bias=None, x2=None, bias2=None, res=None, scale=1.0, padding=None, splitk=False):
+    """x*: NCHW cpu tensors; w: [Cout, Cin, k, k] (reference layout). Returns NCHW cpu."""
+    Cout, Cin, k, _ = w.shape
+    taps = k * k
+    a1, a2, wp, bb, b2, rr = conv_operands(x1, x2, w, taps, bias, bias2, res)
+    B, H, W, C1 = a1.shape
+    C2 = a2.shape[3] if a2 is not None else 0
     out = torch.empty(B, H, W, Cout, device="cuda")
     scratch = None
     if splitk:
@@ -57,14 +65,9 @@ def conv2d_16(x1, w, dt, bias=None, x2=None, bias2=None, res=None, scale=1.0, ou
     beta [C]) or None; silu: SiLU behind the fused GroupNorm."""
     Cout, Cin, k, _ = w.shape
     taps = k * k
-    a1 = nhwc(x1)
-    a2 = nhwc(x2) if x2 is not None else None
+    a1, a2, wp, bb, b2, rr = conv_operands(x1, x2, w, taps, bias, bias2, res)
     B, H, W, C1 = a1.shape
     C2 = a2.shape[3] if a2 is not None else 0
-    wp = w.permute(0, 2, 3, 1).reshape(Cout, taps, Cin).contiguous().cuda()
-    bb = bias.contiguous().cuda() if bias is not None else None
-    b2 = bias2.contiguous().cuda() if bias2 is not None else None
-    rr = nhwc(res) if res is not None else None
     mean, scl, beta = (t.contiguous().cuda() for t in gn) if gn is not None else (None, None, None)
     out = torch.empty(B, H, W, Cout, device="cuda")
     M = B * H * W
@@ -180,14 +183,9 @@ def gfp(t, W):
 def conv3x3_gn(x1, gamma, beta, w, bias=None, x2=None, bias2=None, res=None, scale=1.0, silu=True, eps=1e-6):
     """(conv3x3(act(GN(cat[x1,x2]))) + bias + bias2 + res) * scale through the fused halo kernel."""
     Cout, Cin, k, _ = w.shape
-    a1 = nhwc(x1)
-    a2 = nhwc(x2) if x2 is not None else None
+    a1, a2, wp, bb, b2, rr = conv_operands(x1, x2, w, 9, bias, bias2, res)
     B, H, W, C1 = a1.shape
     C2 = a2.shape[3] if a2 is not None else 0
-    wp = w.permute(0, 2, 3, 1).reshape(Cout, 9, Cin).contiguous().cuda()
-    bb = bias.contiguous().cuda() if bias is not None else None
-    b2 = bias2.contiguous().cuda() if bias2 is not None else None
-    rr = nhwc(res) if res is not None else None
     g, be = gamma.cuda().contiguous(), beta.cuda().contiguous()
     scratch = torch.empty(L.flowse_op_group_norm_scratch_floats(B, H * W, C1 + C2), device="cuda")
     out = torch.empty(B, H, W, Cout, device="cuda")
@@ -204,14 +202,9 @@ def conv3x3_f43(x1, w, gamma=None, beta=None, bias=None, x2=None, bias2=None, re
     """Same contract as conv3x3_gn (gamma None: no normalisation) through the F(4,3) Winograd kernel (form "f43") or the
     two-dimensional F(4,3) x F(2,3) kernel (form "w2d")."""
     Cout, Cin, k, _ = w.shape
-    a1 = nhwc(x1)
-    a2 = nhwc(x2) if x2 is not None else None
+    a1, a2, wp, bb, b2, rr = conv_operands(x1, x2, w, 9, bias, bias2, res)
     B, H, W, C1 = a1.shape
     C2 = a2.shape[3] if a2 is not None else 0
-    wp = w.permute(0, 2, 3, 1).reshape(Cout, 9, Cin).contiguous().cuda()
-    bb = bias.contiguous().cuda() if bias is not None else None
-    b2 = bias2.contiguous().cuda() if bias2 is not None else None
-    rr = nhwc(res) if res is not None else None
     g = gamma.cuda().contiguous() if gamma is not None else None
     be = beta.cuda().contiguous() if beta is not None else None
     scratch = torch.empty(getattr(L, f"flowse_op_conv3x3_{form}_scratch_floats")(B, H, W, C1 + C2, Cout), device="cuda")
