@@ -353,9 +353,11 @@ struct ConvOffer {
     bool bias2 = false, stats = false;   // ConvArgs::bias2 / ::stats are present
     bool fold = false;      // a folded 1x1 shortcut rides along (ConvArgs::sc1 / wfrag_sc)
 };
-// one value per launcher launch_conv can reach; conv_kernel_name: the prefix that launcher records (conv_note_route)
+// one value per launcher launch_conv can reach, the three kernels of the 4-channel input convs (input layer, Combine)
+// included; conv_kernel_name: the prefix that launcher records (conv_note_route)
 enum ConvKernel { CK_HEAD4, CK_HEAD4_16, CK_SMALLM, CK_1X1_STREAM, CK_W2D, CK_F43, CK_F43_SPLITK, CK_HALO, CK_HALO_BF16X3,
-                  CK_HALO16, CK_PC16, CK_SMALLM16B, CK_FLAT, CK_FLAT_SPLITK, CK_FLAT16, CK_FLAT16_SPLITK, CK_NONE };
+                  CK_HALO16, CK_PC16, CK_SMALLM16B, CK_FLAT, CK_FLAT_SPLITK, CK_FLAT16, CK_FLAT16_SPLITK, CK_CIN4,
+                  CK_CIN4_STATS, CK_CIN4_MFMA, CK_NONE };
 const char* conv_kernel_name(ConvKernel k);
 struct ConvRoute {
     ConvKernel kernel = CK_NONE;
@@ -390,15 +392,6 @@ const char* conv_last_route();
 bool conv_reduce_gn_ok(int B, int HW, int Cout);
 int launch_splitk_reduce_gn(const ConvArgs& a, const float* gamma, const float* beta, float eps, int silu, int apply,
                             float* gn_mean, float* gn_scale, hipStream_t s);
-// true when the 4-channel input conv runs on the matrix cores (then it also emits fused GroupNorm statistics,
-// H*W/128 partial blocks per sample)
-bool conv_cin4_uses_mfma(int B, int H, int W, int Cout, int taps);
-// statistics blocks per sample the Combine kernel (conv1x1 4 -> C + in-place residual) writes with its output (0: none)
-int conv_cin4_stats_blocks(int B, int H, int W, int Cout);
-
-// direct conv for 4 input channels (input layer, Combine): VALU, HBM-bound
-int launch_conv_cin4(const ConvArgs& a, hipStream_t s);
-
 // ------------------------------------------------------------------ GroupNorm
 // stats over (C/G channels) x H x W for a (possibly concatenated) NHWC tensor
 int gn_partial_blocks(int HW, int C);

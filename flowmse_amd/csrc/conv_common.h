@@ -25,6 +25,11 @@ int launch_flat_fp32(const ConvArgs& a, hipStream_t s);        // conv_flat.hip:
 int launch_halo_fp32(const ConvArgs& a, hipStream_t s);        // conv_halo.hip: direct LDS-halo 3x3 (exact fmaf chain)
 int launch_head4(const ConvArgs& a, hipStream_t s);            // conv_halo.hip: 3x3 to four output channels
 bool conv_head4_widens();                                      // FLOWSE_HEAD4_FP32=1: 16-bit inputs run the fp32 head kernel ("head4")
+// conv_halo.hip: the kernels of a 4-channel fp32 input (input layer, Combine).  conv_cin4_kernel_of: which of the three takes
+// the shape -- CK_CIN4_MFMA, CK_CIN4_STATS (only where statistics are asked for), CK_CIN4 -- or CK_NONE; launch_cin4 runs k
+ConvKernel conv_cin4_kernel_of(const ConvShape& q, bool stats);
+int conv_cin4_stats_blocks(int B, int H, int W, int Cout);     // statistics blocks per sample of CK_CIN4_STATS
+int launch_cin4(const ConvArgs& a, ConvKernel k, hipStream_t s);
 int launch_f43(const ConvArgs& a, hipStream_t s);              // conv_f43.hip: F(4,3) Winograd 3x3 (whole K or slices)
 int launch_1x1_stream(const ConvArgs& a, hipStream_t s);       // conv_1x1.hip: fp32 1x1 on large images, every wave its own GEMM
 int launch_smallm(const ConvArgs& a, hipStream_t s);           // conv_smallm.hip: <= 2048 pixels, K split inside the block

@@ -6,7 +6,8 @@
 // Kernel families (one translation unit each):
 //   conv_f43.hip      fp32 F(4,3) Winograd 3x3 (production kernel of the fp32 mode)
 //   conv_w2d.hip      fp32 F(4,3) x F(2,3) two-dimensional Winograd 3x3 (large images, whole K)
-//   conv_halo.hip     direct fp32 LDS-halo 3x3, 4-channel heads / input layers
+//   conv_halo.hip     direct fp32 LDS-halo 3x3, 4-channel heads; the convs of a 4-channel input (input layer, Combine 1x1):
+//                     routed here like every other family, by shape (fp32 input, C1 = 4, C2 = 0), always whole K
 //   conv_flat.hip     flat fp32 kernels: 1x1, small 3x3, split-K slices
 //   conv_smallm.hip   fp32 convs on <= 2048 pixels: K split inside the block (no slab, no reduction launch)
 //   conv_1x1.hip      fp32 1x1 on large images: every wave its own GEMM, operands straight into fragment registers
@@ -54,8 +55,8 @@ bool conv_w2d_shape_ok(int B, int H, int W, int C1, int C2, int Cout, int taps) 
 
 // ------------------------------------------------------------------------------------------- the policy, fp32 storage
 // Everything below answers "what will run" and is asked by conv_route alone; "can this kernel run this shape" lives
-// with the kernels (conv_supports_head4, conv_smallm_ok, conv1x1_stream_ok, conv_w2d_shape_ok, conv16_uses_halo / _pc,
-// conv16_smallm_ok).
+// with the kernels (conv_supports_head4, conv_cin4_kernel_of, conv_smallm_ok, conv1x1_stream_ok, conv_w2d_shape_ok,
+// conv16_uses_halo / _pc, conv16_smallm_ok).
 struct Fp32Policy {
     int ksplit;       // K slices a slab would be cut into (1 = whole K)
     int f43;          // 0: not an F(4,3) shape (or too small even when sliced), 1: whole K, >= 2: that many slices of chunks
@@ -155,7 +156,7 @@ const char* conv_last_route() { return g_route; }
 const char* conv_kernel_name(ConvKernel k) {
     static const char* const names[] = {"head4", "head4_16", "smallm", "1x1_stream", "w2d", "f43", "f43_splitk", "halo",
                                         "halo_bf16x3", "halo16", "pc16", "smallm16b", "flat", "flat_splitk", "flat16",
-                                        "flat16_splitk", "none"};
+                                        "flat16_splitk", "cin4", "cin4_stats", "cin4_mfma", "none"};
     return names[k];
 }
 
@@ -164,7 +165,8 @@ static int route_stats_blocks(ConvKernel k, const ConvShape& q) {
     const int HW = q.H * q.W;
     if (q.Cout & 3) return 0;
     switch (k) {
-        case CK_HEAD4: case CK_HEAD4_16: case CK_NONE: return 0;
+        case CK_HEAD4: case CK_HEAD4_16: case CK_CIN4: case CK_NONE: return 0;
+        case CK_CIN4_STATS: return conv_cin4_stats_blocks(q.B, q.H, q.W, q.Cout);
         case CK_SMALLM: return conv_smallm_stats_blocks(q.B, q.H, q.W);
         case CK_SMALLM16B: return conv16_smallm_stats_blocks(q.B, q.H, q.W);
         case CK_1X1_STREAM: return conv1x1_stream_stats_blocks(q.B, q.H, q.W);
@@ -188,12 +190,14 @@ static bool route_gn_on_load(ConvKernel k) {
 ConvRoute conv_route(const ConvShape& q, const ConvOffer& o) {
     const int B = q.B, H = q.H, W = q.W, C1 = q.C1, C2 = q.C2, Cout = q.Cout, taps = q.taps;
     const bool in16 = q.in_dt != DT_F32;
+    // a 4-channel fp32 input (the input layer, the Combine 1x1): its own kernels, whole K whatever is offered
+    const bool cin4 = !in16 && C1 == 4 && C2 == 0;
     const bool head4 = conv_supports_head4(B, H, W, C1, C2, Cout, taps);
     // (the LDS-halo kernels store the operands' type only: an fp32-output launch of their shapes runs the flat kernel)
     const bool halo16 = in16 && q.out_dt == q.in_dt && conv16_uses_halo(B, H, W, C1, C2, Cout, taps);
-    const Fp32Policy p = in16 ? Fp32Policy{1, 0, false, false, false} : fp32_policy(q, head4);
+    const Fp32Policy p = in16 || cin4 ? Fp32Policy{1, 0, false, false, false} : fp32_policy(q, head4);
     ConvRoute r;
-    if (o.slab) r.ksplit = !in16 ? p.ksplit : (head4 || halo16) ? 1 : flat16_ksplit(q);
+    if (o.slab && !cin4) r.ksplit = !in16 ? p.ksplit : (head4 || halo16) ? 1 : flat16_ksplit(q);
     const int ks = r.ksplit;
     // the F(4,3) weights count half the nominal FLOPs for every conv that could run on them -- also where the bf16 planes
     // take the launch in the end (the plans have always been counted so)
@@ -218,7 +222,14 @@ ConvRoute conv_route(const ConvShape& q, const ConvOffer& o) {
             return fail(ERR_ARG, "conv: a folded shortcut needs a launch of conv3x3_pc16_kernel (16-bit storage, 16 x 16-pixel tiles)");
         return run(CK_PC16);
     }
-    if (in16) {                                         // activations stored as bf16 / half
+    if (cin4) {                                         // (none of these normalises on load: a gn request is run()'s error)
+        const ConvKernel k = conv_cin4_kernel_of(q, o.stats);
+        if (k != CK_NONE) return run(k);
+        run(CK_FLAT);          // shapes the three refuse: only the flat kernel, whole K and without statistics, has ever run them
+        r.stats_nblk = 0;
+        return r;
+    }
+    if (in16) {                                        // activations stored as bf16 / half
         if (ks <= 1 && !o.bias2 && !o.stats && q.out_dt == DT_F32 && head4) return run(conv_head4_widens() ? CK_HEAD4 : CK_HEAD4_16);
         if (ks <= 1 && halo16) return run(o.wfrag && conv16_uses_pc(B, H, W, C1, C2, Cout, taps) ? CK_PC16 : CK_HALO16);
         if (o.wfrag && ks <= 1 && !o.gn && (q.out_dt == q.in_dt || q.out_dt == DT_F32) && conv16_smallm_ok(B, H, W, C1, C2, Cout, taps))
@@ -265,6 +276,7 @@ int launch_conv_routed(const ConvArgs& a, const ConvRoute& r, hipStream_t s, boo
         case CK_SMALLM16B: return launch_smallm16b(a, s);
         case CK_FLAT: return launch_flat_fp32(a, s);
         case CK_FLAT16: return launch_flat16(a, s);
+        case CK_CIN4: case CK_CIN4_STATS: case CK_CIN4_MFMA: return launch_cin4(a, r.kernel, s);
         case CK_F43_SPLITK: rc = launch_f43(a, s); break;
         case CK_FLAT_SPLITK: rc = launch_flat_fp32(a, s); break;
         case CK_FLAT16_SPLITK: rc = launch_flat16(a, s); break;

@@ -665,7 +665,7 @@ __global__ __launch_bounds__(256) void conv_cin4_stats_kernel(ConvArgs a, int Q,
 int conv_cin4_stats_blocks(int B, int H, int W, int Cout) {
     const int HW = H * W, PB = HW < 128 ? HW : 128, Q = Cout / 4;
     (void)B;
-    if ((Cout & 3) || Q > 256 || (256 % Q) != 0 || (HW % PB) != 0 || (PB % (256 / Q)) != 0) return 0;
+    if ((Cout & 3) || Q < 1 || Q > 256 || (256 % Q) != 0 || (HW % PB) != 0 || (PB % (256 / Q)) != 0) return 0;
     return HW / PB;
 }
 
@@ -762,14 +762,30 @@ __global__ __launch_bounds__(256, 2) void conv3x3_cin4_mfma_kernel(ConvArgs a) {
     conv_epilogue<4, 1, 1, 4, OT>(a, acc, smem, m0, 0, M, HW, 0);
 }
 
-bool conv_cin4_uses_mfma(int B, int H, int W, int Cout, int taps) {
-    return taps == 9 && Cout == 128 && ((H * W) % 128) == 0 && (int64_t)B * H * W >= 128 * 256 && !conv_force_generic();
+// The family: an fp32 input of exactly four channels, any storage type of res / out.  Every member runs whole K.
+ConvKernel conv_cin4_kernel_of(const ConvShape& q, bool stats) {
+    if (q.in_dt != DT_F32 || q.C1 != 4 || q.C2 != 0) return CK_NONE;
+    // the matrix-core kernel (statistics with the output, H W / 128 blocks): whole 128-pixel tiles, enough of them
+    if (q.taps == 9 && q.Cout == 128 && ((q.H * q.W) % 128) == 0 && (int64_t)q.B * q.H * q.W >= 128 * 256 && !conv_force_generic())
+        return CK_CIN4_MFMA;
+    // VALU kernels: a thread per (pixel, channel quad), 256 / Q pixels per block, the weights in LDS
+    const int Q = q.Cout / 4;
+    if ((q.Cout & 3) || Q < 1 || Q > 256 || (256 % Q) != 0 || (size_t)q.Cout * q.taps * 16 > 64 * 1024) return CK_NONE;
+    if (stats && q.taps == 1 && conv_cin4_stats_blocks(q.B, q.H, q.W, q.Cout) > 0) return CK_CIN4_STATS;
+    return CK_CIN4;                                      // no statistics
 }
 
-int launch_conv_cin4(const ConvArgs& a, hipStream_t s) {
-    conv_note_route("cin4");
+int launch_cin4(const ConvArgs& a, ConvKernel k, hipStream_t s) {
+    const ConvShape q{a.in_dt, a.out_dt, a.B, a.H, a.W, a.C1, a.C2, a.Cout, a.taps};
+    const int nblk = k == CK_CIN4_MFMA ? a.H * a.W / 128 : k == CK_CIN4_STATS ? conv_cin4_stats_blocks(a.B, a.H, a.W, a.Cout) : 0;
+    if (k != conv_cin4_kernel_of(q, a.stats != nullptr) || a.gn.mean || a.ksplit > 1 || (a.stats && a.stats_nblk != nblk)) {
+        set_error("conv_cin4: %s does not take this request (in_dt=%d C=%d+%d Cout=%d taps=%d ksplit=%d; it writes %d statistics "
+                  "blocks per sample, stats_nblk=%d)", conv_kernel_name(k), a.in_dt, a.C1, a.C2, a.Cout, a.taps, a.ksplit, nblk, a.stats_nblk);
+        return ERR_ARG;
+    }
+    conv_note_route(conv_kernel_name(k));
     const int Q = a.Cout / 4;
-    if (a.C1 == 4 && a.C2 == 0 && a.ksplit <= 1 && !a.gn.mean && conv_cin4_uses_mfma(a.B, a.H, a.W, a.Cout, a.taps)) {
+    if (k == CK_CIN4_MFMA) {
         const size_t lds = ((size_t)128 * (128 + 4) + 256 * 8) * sizeof(float);
         if (const int rc = allow_lds<&conv3x3_cin4_mfma_kernel<float>>(lds)) return rc;
         if (const int rc = allow_lds<&conv3x3_cin4_mfma_kernel<bf16_t>>(lds)) return rc;
@@ -779,16 +795,7 @@ int launch_conv_cin4(const ConvArgs& a, hipStream_t s) {
         FLOWSE_LAUNCH_CHECK();
         return OK;
     }
-    if (a.C1 != 4 || a.C2 != 0 || (a.Cout & 3) || Q > 256 || (256 % Q) != 0 ||
-        (size_t)a.Cout * a.taps * 16 > 64 * 1024) {
-        return launch_conv(a, s);      // generic path handles any shape
-    }
-    if (a.stats) {                                       // Combine with fused statistics (1x1)
-        const int nblk = conv_cin4_stats_blocks(a.B, a.H, a.W, a.Cout);
-        if (a.taps != 1 || a.in_dt != DT_F32 || nblk == 0 || a.stats_nblk != nblk) {
-            set_error("conv_cin4: fused statistics need a 1x1 conv of an fp32 input on whole statistics blocks (stats_nblk=%d)", a.stats_nblk);
-            return ERR_ARG;
-        }
+    if (k == CK_CIN4_STATS) {                            // Combine with fused statistics (1x1)
         const int PB = a.H * a.W / nblk;
         const size_t lds_s = (size_t)a.Cout * 16 + (size_t)256 * 8 * sizeof(float);
         FLOWSE_DT_SWITCH(a.out_dt, OT, hipLaunchKernelGGL(conv_cin4_stats_kernel<OT>, dim3((unsigned)((int64_t)a.B * nblk)), dim3(256), lds_s, s, a, Q, PB));

@@ -52,7 +52,6 @@ struct ConvReq {
     const Tn* res = nullptr;            // residual: out = (conv + res) * scale
     float scale = 1.f;
     bool out_is_res = false;            // in place on `res`
-    bool cin4 = false;                  // the 4-channel input kernels
     const GnBuf* gin = nullptr;         // GroupNorm (+ SiLU) of the input on load
     bool gin_silu = false;
     int64_t wq_off = -1;                // offset of the reduced-precision weight copy
@@ -253,7 +252,7 @@ struct Builder {
         const int64_t w = q.w, bias = q.bias, wq_off = q.wq_off, bias_sc = q.bias_sc;
         const int dense_row0 = q.dense_row0, Cout = q.Cout, taps = q.taps, out_dt = q.out_dt;
         const float scale = q.scale;
-        const bool out_is_res = q.out_is_res, cin4 = q.cin4, gin_silu = q.gin_silu, no_stats = q.no_stats;
+        const bool out_is_res = q.out_is_res, gin_silu = q.gin_silu, no_stats = q.no_stats;
         const GnBuf* gin = q.gin;
         const SkPartial* extra = q.extra;
         const ScFold* fold = q.fold;
@@ -270,18 +269,18 @@ struct Builder {
         const bool has_gin = gin != nullptr, has_fold = fold != nullptr;
         // The one routing question of this conv, asked once: the offer is what the weight set holds for this weight.  The
         // answer says which kernel runs, over how many K slices and where its statistics go; the launch closure keeps it.
-        ConvRoute rt;                                    // (the 4-channel input kernels: launch_conv_cin4, never split)
-        if (!cin4) {
-            ConvOffer of = offer(idt, w, taps, wq_off);
-            of.gn = has_gin;
-            of.bias2 = dense_row0 >= 0 || bias_sc >= 0;
-            of.stats = !(out_is_res || Cout < 16 || no_stats);
-            of.fold = has_fold;
-            rt = conv_route(ConvShape{idt, want_odt, Bn, H, Wd, C1, C2, Cout, taps}, of);
-            if (rt.err != OK) {
-                set_error("internal: no kernel takes %s@%dx%d (%s)", label.c_str(), H, Wd, rt.err_text);
-                failed = true;
-            }
+        ConvOffer of = offer(idt, w, taps, wq_off);
+        of.gn = has_gin;
+        of.bias2 = dense_row0 >= 0 || bias_sc >= 0;
+        // statistics of the output where somebody normalises it.  In place on `res`, only Combine's (conv1x1 of the 4-channel
+        // pyramid, any storage type of `res`) are used: they are those of the updated tensor
+        const bool combine = out_is_res && taps == 1 && C1 == 4 && !b2 && idt == DT_F32;
+        of.stats = Cout >= 16 && !no_stats && (!out_is_res || combine);
+        of.fold = has_fold;
+        const ConvRoute rt = conv_route(ConvShape{idt, want_odt, Bn, H, Wd, C1, C2, Cout, taps}, of);
+        if (rt.err != OK) {
+            set_error("internal: no kernel takes %s@%dx%d (%s)", label.c_str(), H, Wd, rt.err_text);
+            failed = true;
         }
         const int ks = rt.ksplit;
         // a deferred reduction leaves no output tensor: decide before anything is allocated
@@ -299,14 +298,9 @@ struct Builder {
         const size_t a_off = a.off, b_off = b2 ? b2->off : 0, o_off = o.off, r_off = res ? res->off : 0;
         const bool has2 = b2 != nullptr, hasres = res != nullptr;
         const int odt = o.dt;                            // (a deferred conv has no output tensor: fp32, as its slices are)
-        // statistics of the output: the geometry of the kernel that runs
-        int st_nblk = (cin4 || out_is_res || Cout < 16) ? 0 : rt.stats_nblk;
-        if (cin4 && !out_is_res && C1 == 4 && !has2 && conv_cin4_uses_mfma(Bn, H, Wd, Cout, taps)) st_nblk = H * Wd / 128;
-        // Combine (conv1x1 4 -> C, in place on `res`, any storage type): the kernel leaves the statistics of the updated tensor
-        if (cin4 && out_is_res && taps == 1 && C1 == 4 && !has2 && idt == DT_F32 && Cout >= 16)
-            st_nblk = conv_cin4_stats_blocks(Bn, H, Wd, Cout);
-        if (defer || gnf) st_nblk = 0;                   // no output here / the statistics are finished inside the reduction
-        if (no_stats) st_nblk = 0;                       // nobody normalises this tensor (the shortcut: a residual only)
+        // statistics of the output: where asked for, in the geometry of the kernel that runs -- unless there is no output here
+        // (defer) or they are finished inside the reduction (gnf)
+        const int st_nblk = of.stats && !defer && !gnf ? rt.stats_nblk : 0;
         if (out_is_res && o.st_nblk > 0) {               // updated in place: the producer's statistics are stale
             arena.release(o.st_off);
             o.st_nblk = 0;
@@ -401,7 +395,7 @@ struct Builder {
         const double part_bytes = 4.0 * ks * (double)Bn * H * Wd * Cout;
         op(full_label, [=](hipStream_t s) {
             const ConvArgs c = make_args();
-            return cin4 ? launch_conv_cin4(c, s) : launch_conv_routed(c, rt, s, false);
+            return launch_conv_routed(c, rt, s, false);
         }, flops, in_bytes + (ks > 1 ? part_bytes : out_bytes),
            // the roofline's kernel: a whole-K 3x3 that normalises on load -- of those counted at half the FLOPs (the F(4,3)
            // weights), only the launches that use 128-channel blocks
@@ -694,7 +688,6 @@ static ConvReq combine_req(const Module& cb, const Tn& x, const Tn& y) {
     r.bias = cb.w_a_b;
     r.res = &y;
     r.out_is_res = true;
-    r.cin4 = true;
     return r;
 }
 
@@ -751,7 +744,6 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
     {
         ConvReq r = conv_req("conv_in", in4, cin.w_a, nf, 9);
         r.bias = cin.w_a_b;
-        r.cin4 = true;
         hs.push_back(bd.conv(r));
     }
     Tn ipyr = in4;

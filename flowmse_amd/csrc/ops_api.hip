@@ -92,7 +92,6 @@ int flowse_op_conv2d(const float* in1, int C1, const float* in2, int C2, const f
     }
     ConvArgs c = conv_args(in1, C1, in2, in2 ? C2 : 0, w, bias, bias2, bias2_stride, res, out, B, H, W, Cout, taps, scale);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (C1 == 4 && !in2) return launch_conv_cin4(c, s);
     if (splitk_scratch) {                            // the model handle's kernel for this shape
         const ConvRoute r = op_route_f32(B, H, W, c.C1, c.C2, Cout, taps, op_offer_scratch());
         if (r.kernel == CK_SMALLM || r.kernel == CK_1X1_STREAM) {
@@ -319,7 +318,9 @@ const char* flowse_op_last_conv_route(void) { return conv_last_route(); }
 
 int flowse_op_conv_route(int in_dt, int out_dt, int B, int H, int W, int C1, int C2, int Cout, int taps, int offer_bits,
                          char* text, int cap) {
-    if (!text || cap < 64 || in_dt < DT_F32 || in_dt > DT_F16 || (out_dt != DT_F32 && out_dt != in_dt) || B < 1 || H < 1 || W < 1) {
+    // (fp32 in, 16-bit out: the convs of the 4-channel input in the 16-bit storage modes)
+    const bool in4_out16 = in_dt == DT_F32 && C1 == 4 && C2 == 0 && (out_dt == DT_BF16 || out_dt == DT_F16);
+    if (!text || cap < 64 || in_dt < DT_F32 || in_dt > DT_F16 || (out_dt != DT_F32 && out_dt != in_dt && !in4_out16) || B < 1 || H < 1 || W < 1) {
         set_error("flowse_op_conv_route: bad argument");
         return ERR_ARG;
     }

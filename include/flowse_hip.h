@@ -553,16 +553,19 @@ int flowse_op_conv2d_16_ex(const float* in1, int C1, const float* in2, int C2, c
                            void* stream);
 /* Which kernel the calling thread's last convolution launch ran (any entry point that launches one: the per-op entries
  * above and below, a forward pass while it is being recorded): the kernel family -- "flat", "flat_splitk", "halo", "f43",
- * "f43_splitk", "w2d", "1x1_stream", "head4", "head4_16", "cin4", "flat16", "flat16_splitk", "halo16", "halo_bf16x3",
- * "pc16" -- or, for the small-image kernels (at most 2048 pixels), the instance: "smallm<1>", "smallm<2>", "smallm_tile16",
+ * "f43_splitk", "w2d", "1x1_stream", "head4", "head4_16", "cin4", "cin4_stats", "cin4_mfma", "flat16", "flat16_splitk",
+ * "halo16", "halo_bf16x3", "pc16" -- or, for the small-image kernels (at most 2048 pixels), the instance: "smallm<1>", "smallm<2>", "smallm_tile16",
  * "smallm16b<NT2, bf16|f16, out16|out32>" with NT2 = 1 or 2.  Written by the launcher next to the launch, never derived
  * from the shape a second time; a host-side, thread-local record ("" before the first launch): replaying a captured
  * graph does not change it.  The pointer stays valid for the thread's lifetime; the text changes with the next launch. */
 const char* flowse_op_last_conv_route(void);
 /* What a convolution of this shape WOULD run: the library's one routing decision (the plan of a model handle and every
- * per-op entry go through it), as one line of text.  Host only: no HIP call, works with no GPU present.  in_dt / out_dt:
- * storage types (0 fp32, 1 bf16, 2 half; out_dt = in_dt or 0); (C1, C2): the parts of a concat input; offer_bits: what
- * the caller could hand to the launch, FLOWSE_OFFER_* below.  Writes
+ * per-op entry go through it, the convs of a 4-channel input included), as one line of text.  Host only: no HIP call, works
+ * with no GPU present.  in_dt / out_dt: storage types (0 fp32, 1 bf16, 2 half; out_dt = in_dt or 0 -- or, for an fp32 input
+ * of four channels (C1 = 4, C2 = 0: the input layer and the Combine 1x1, whose input stays fp32 in the 16-bit modes), any of
+ * the three: "cin4_mfma", "cin4_stats" (only where statistics are asked for) or "cin4", always whole K, and "flat" for the
+ * widths those kernels do not take); (C1, C2): the parts of a concat input; offer_bits: what the caller could hand to the
+ * launch, FLOWSE_OFFER_* below.  Writes
  *   "<kernel> ks=<K slices> reduce=<0|1> stats=<blocks per sample> gn=<0|1> issued=<1/3|1/2|1|3>"
  * -- kernel: the family flowse_op_last_conv_route reports after that launch ("smallm" / "smallm16b" without the instance);
  * reduce: a separate reduction launch follows; stats: geometry of the fused GroupNorm statistics (0: none); gn: the kernel

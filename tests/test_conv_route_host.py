@@ -11,13 +11,15 @@ a route leaves the file untouched, one that does regenerates it and the diff of 
 File format.  One line per shape, storage type and answer: "HxW C1+C2>Cout/taps dt B<batches>" and, per distinct answer, the
 offers that get it, "names: answer".  An answer is the entry's text with the field names dropped, "kernel ks stats gn issued"
 (`reduce` is left out: it is ks > 1, which test_route_properties asserts for every query), or "error <status>".  dt "16"
-stands for bf16 and fp16 where their answers are equal; batches that give the same answers share a line.  The first
+stands for bf16 and fp16 where their answers are equal; "f32>bf16" is an fp32 input stored as bf16 (the convs of the
+4-channel input in the 16-bit modes); batches that give the same answers share a line.  The first
 section is the library as loaded by default; a section "[HOOK=value]" is the same list of queries asked in a fresh process
 with that environment variable set (the hooks are read when the library loads) and holds only what differs from the first.
 
 The queries: every distinct conv of tests/plan_pins.json (LEVELS x CASES below, concat inputs as their two parts) at the
 batch of its case and at B = 2 and 4, in all three storage types, offering what a model handle holds / nothing / the
-former plus normalise-on-load; and EDGES, the two sides of every threshold the policy has.
+former plus normalise-on-load -- the convs of the 4-channel input (IN4_LEVELS) with fp32 in and each storage type out, with
+and without statistics asked for --; and EDGES, the two sides of every threshold the policy has.
 """
 import ctypes
 import os
@@ -55,6 +57,11 @@ LEVELS = {
     4: [(256, 0, 4, 9), (256, 0, 256, 1), (256, 0, 256, 9), (256, 0, 768, 1), (256, 256, 256, 1),
         (256, 256, 256, 9)],
 }
+# the convs of the 4-channel input (labels conv_in and combine_1x1): fp32 in, every storage type out
+IN4_LEVELS = {256: [(4, 0, 128, 9)], 128: [(4, 0, 128, 1)], 64: [(4, 0, 128, 1)], 32: [(4, 0, 256, 1)], 16: [(4, 0, 256, 1)],
+              8: [(4, 0, 256, 1)], 4: [(4, 0, 256, 1)]}
+IN4 = (F32, (F32, BF16), (F32, F16))                  # a pair: (in_dt, out_dt) where the two differ by design
+IN4_OFFERS = [("h", 0), ("+stats", STATS), ("0", None), ("g", GN)]
 # offers: (name, bits added to HANDLE[dt]; None: no bits at all).  h = what a handle holds, 0 = nothing, g = h + normalise-on-load
 PLAN_OFFERS = [("h", 0), ("0", None), ("g", GN)]
 
@@ -90,6 +97,23 @@ EDGES += [((8, 128, 128, 128, 0, 4, 9), ALL, HEAD), ((1, 32, 32, 256, 0, 4, 9), 
 # fp32 storage with 16-bit weight planes next to the Winograd weights (precision modes bf16x3 / bf16 / fp16 operands)
 PLANES = [("+bf16x3", WQ | WQ3), ("+bf16x3+gn", WQ | WQ3 | GN), ("+bf16", WQ), ("+f16", WQ | WQF16), ("+f16x3", WQ | WQ3 | WQF16)]
 EDGES += [((B, H, W, 128, 0, Co, 9), (F32,), PLANES) for B, H, W in ((8, 256, 256), (1, 64, 64), (1, 16, 16)) for Co in (128, 64)]
+# the kernels of a 4-channel fp32 input.  Matrix-core kernel: 32768 | 32640 pixels over the batch, H W a multiple of 128 or
+# not, Cout 128 | 64, 256 (those run the VALU kernel)
+EDGES += [((B, 8, 16, 4, 0, 128, 9), IN4, IN4_OFFERS) for B in (256, 255)]
+EDGES += [((B, H, W, 4, 0, 128, 9), IN4, IN4_OFFERS) for B, H, W in ((64, 32, 16), (64, 33, 16))]
+EDGES += [((2, 128, 128, 4, 0, Co, 9), IN4, IN4_OFFERS) for Co in (128, 64, 256)]
+# VALU kernels: Cout / 4 divides 256 or not (96 | 64); weights of 72 KB | 36 KB | 8 KB in LDS (Cout 512 at taps 9 | 256 at
+# taps 9 | 512 at taps 1); what they refuse runs the flat kernel, whole K, without statistics
+EDGES += [((B, H, W, 4, 0, Co, t), IN4, IN4_OFFERS) for B, H, W in ((8, 64, 64), (1, 16, 16))
+          for Co, t in ((96, 9), (96, 1), (64, 9), (64, 1), (512, 9), (256, 9), (512, 1))]
+# statistics kernel: blocks of min(128, H W) pixels -- H W = 64, 128, 192 (not whole blocks); a block's pixels a multiple of the
+# 256 / (Cout / 4) pixel rows or not (H W = 128: Cout 8 | 4); 3x3 with statistics asked for
+EDGES += [((2, H, 8, 4, 0, 32, 1), IN4, IN4_OFFERS) for H in (8, 16, 24)]
+EDGES += [((2, 16, 8, 4, 0, Co, 1), IN4, IN4_OFFERS) for Co in (8, 4)]
+EDGES += [((2, 8, 8, 4, 0, 32, 9), IN4, IN4_OFFERS)]
+# not the family: a second input part, 16-bit input
+EDGES += [((2, 8, 8, 4, 4, 32, t), ALL, IN4_OFFERS) for t in (9, 1)]
+EDGES += [((B, H, W, 4, 0, Co, t), (BF16, F16), IN4_OFFERS) for B, H, W, Co, t in ((8, 256, 256, 128, 9), (2, 8, 8, 32, 1))]
 
 HOOKS = ["FLOWSE_NO_WINOGRAD=1", "FLOWSE_NO_HALO_CONV=1", "FLOWSE_FORCE_GENERIC_CONV=1", "FLOWSE_W2D=0", "FLOWSE_NO_SMALLM=1"]
 
@@ -105,6 +129,14 @@ def rows():
                     if shape not in seen:
                         seen.add(shape)
                         out.append((shape, ALL, PLAN_OFFERS))
+    for Bc, T in CASES:
+        for B in (Bc, 2, 4):
+            for lv, (H, convs) in enumerate(IN4_LEVELS.items()):
+                for c in convs:
+                    shape = (B, H, T >> lv) + c
+                    if shape not in seen:
+                        seen.add(shape)
+                        out.append((shape, IN4, IN4_OFFERS))
     return out + EDGES
 
 
@@ -114,10 +146,12 @@ def queries():
     for shape, dts, offers in rows():
         B, H, W, C1, C2, Cout, taps = shape
         for dt in dts:
-            out_dt = F32 if Cout == 4 else dt          # the 4-channel pyramids stay fp32 in every mode
+            in_dt, out_dt = dt if isinstance(dt, tuple) else (dt, dt)
+            if Cout == 4:
+                out_dt = F32                           # the 4-channel pyramids stay fp32 in every mode
             for name, add in offers:
-                bits = 0 if add is None else (HANDLE[dt] | add) & ~(WFRAG if name == "fold-wfrag" else 0)
-                out.append(((shape[1:], dt, B), name, (dt, out_dt, B, H, W, C1, C2, Cout, taps, bits)))
+                bits = 0 if add is None else (HANDLE[in_dt] | add) & ~(WFRAG if name == "fold-wfrag" else 0)
+                out.append(((shape[1:], dt, B), name, (in_dt, out_dt, B, H, W, C1, C2, Cout, taps, bits)))
     return out
 
 
@@ -150,10 +184,12 @@ def render_section(ent):
     for (H, W, C1, C2, Cout, taps), cell in by_shape.items():
         groups = {}
         for (dt, B), body in cell.items():
-            both = cell.get((BF16, B)) == cell.get((F16, B))
-            if dt == F16 and both:
+            pre, odt = (DT_NAME[dt[0]] + ">", dt[1]) if isinstance(dt, tuple) else ("", dt)
+            twin = {BF16: F16, F16: BF16}.get(odt)
+            both = twin is not None and cell.get(((dt[0], twin) if pre else twin, B)) == body
+            if odt == F16 and both:
                 continue
-            groups.setdefault(("16" if dt == BF16 and both else DT_NAME[dt], body), []).append(B)
+            groups.setdefault((pre + ("16" if both else DT_NAME[odt]), body), []).append(B)
         for (dtn, body), Bs in groups.items():
             lines.append(f"{H}x{W} {C1}+{C2}>{Cout}/{taps} {dtn} B{','.join(map(str, Bs))} {body}")
     return lines
@@ -213,9 +249,15 @@ def test_route_properties(answers):
     kernels = set()
     for args, text in answers:
         dt, out_dt, B, H, W, C1, C2, Cout, taps, bits = args
+        family = dt == F32 and (C1, C2) == (4, 0)         # the kernels of a 4-channel fp32 input ...
+        # ... take the widths whose channel quads divide a block of 256 threads and whose weights fit 64 KB of LDS
+        takes = family and Cout // 4 <= 256 and 256 % (Cout // 4) == 0 and Cout * taps * 16 <= 64 * 1024
+        assert family or out_dt in (F32, dt), args
         if text.startswith("error"):
             assert text in ("error 1", "error 4"), (args, text)
+            assert not family or bits & GN, (args, text)
             continue
+        assert text.split()[0].startswith("cin4") == takes, (args, text)
         f = dict(kv.split("=") for kv in text.split()[1:])
         kernels.add(text.split()[0])
         ks, nblk = int(f["ks"]), int(f["stats"])
@@ -224,8 +266,16 @@ def test_route_properties(answers):
         assert f["gn"] == "1" or not bits & GN, (args, text)                       # never a kernel that would ignore the request
         assert nblk == 0 or (H * W) % nblk == 0, (args, text)
         assert f["issued"] in ("1/3", "1/2", "1", "3"), (args, text)
+        if family:                                         # whole K whatever is offered; no kernel of theirs normalises on load
+            kernel = text.split()[0]
+            assert (ks, f["gn"], f["issued"]) == (1, "0", "1") and not bits & GN, (args, text)
+            if not takes:                                  # refused: the flat kernel, whole K, no statistics
+                assert text == "flat ks=1 reduce=0 stats=0 gn=0 issued=1", (args, text)
+            else:                                          # statistics: the matrix-core kernel's, or asked for
+                assert (nblk > 0) == (kernel in ("cin4_mfma", "cin4_stats")) and (kernel != "cin4_stats" or bits & STATS), (args, text)
     assert kernels == {"head4", "head4_16", "smallm", "1x1_stream", "w2d", "f43", "f43_splitk", "halo", "halo_bf16x3",
-                       "halo16", "pc16", "smallm16b", "flat", "flat_splitk", "flat16", "flat16_splitk"}, kernels
+                       "halo16", "pc16", "smallm16b", "flat", "flat_splitk", "flat16", "flat16_splitk", "cin4", "cin4_stats",
+                       "cin4_mfma"}, kernels
 
 
 def test_route_entry_is_declared_and_checks_its_arguments():

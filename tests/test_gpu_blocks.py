@@ -70,6 +70,13 @@ def test_combine_vs_reference():
     xp = torch.from_numpy(synth.normal(5, 6, (2, 4, 8, 8)))
     yh = torch.from_numpy(synth.normal(5, 7, (2, 32, 8, 8)))
     assert C.rel_l2(blk(xp, yh), g["out"]) < TOL
+    # the launcher's record of the block's one conv is what the route names for it, statistics asked for: the kernel that
+    # leaves the next GroupNorm's statistics
+    import ctypes
+    from flowmse_amd import _lib
+    buf = ctypes.create_string_buffer(96)
+    assert _lib.lib.flowse_op_conv_route(0, 0, 2, 8, 8, 4, 0, 32, 1, 1024, buf, 96) == 0        # 1024 = FLOWSE_OFFER_STATS
+    assert G.last_route() == "cin4_stats" == buf.value.decode().split()[0], (G.last_route(), buf.value)
 
 
 def test_block_handle_rejects_misuse():

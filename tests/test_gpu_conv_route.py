@@ -47,8 +47,15 @@ CASES = [
     ("head4_16", "16", 1, True, (1, 128, 128, 32, 4, 9), O16),
     ("pc16", "16", 2, False, (1, 64, 128, 32, 256, 9), O16 | WQF16),
     ("flat16_splitk", "16", 2, False, (1, 2, 2, 256, 16, 1), O16 | WQF16),
+    # a 4-channel fp32 input: the VALU kernel (3x3, 1x1), the matrix-core kernel (the smallest batch of whole 128-pixel
+    # tiles that reaches 32768 pixels), and a width those kernels refuse (24 / 4 = 6 does not divide 256): the flat kernel
+    ("cin4", "conv2d", 0, False, (1, 2, 2, 4, 16, 9), 0),
+    ("cin4", "conv2d", 0, False, (1, 2, 2, 4, 16, 1), 0),
+    ("cin4_mfma", "conv2d", 0, False, (2, 128, 128, 4, 128, 9), 0),
+    ("flat", "conv2d", 0, False, (1, 2, 2, 4, 24, 9), 0),
 ]
 IDS = [f"{c[0]}-{('f32', 'bf16', 'f16')[c[2]]}" for c in CASES]
+IDS = [i if i not in IDS[:n] else f"{i}-{c[4][3]}to{c[4][4]}x{c[4][5]}" for n, (i, c) in enumerate(zip(IDS, CASES))]   # a family's further cases: + the shape
 
 
 def route_of(case):
@@ -62,7 +69,8 @@ def route_of(case):
 def test_cases_name_their_family():
     assert [route_of(c) for c in CASES] == [c[0] for c in CASES]
     assert {c[0] for c in CASES} == {"head4", "head4_16", "smallm", "1x1_stream", "w2d", "f43", "f43_splitk", "halo", "halo16",
-                                     "pc16", "smallm16b", "flat", "flat_splitk", "flat16", "flat16_splitk"}
+                                     "pc16", "smallm16b", "flat", "flat_splitk", "flat16", "flat16_splitk", "cin4", "cin4_mfma"}
+    assert len(set(IDS)) == len(IDS)
 
 
 @pytest.mark.gpu
