@@ -312,11 +312,10 @@ int launch_f43_weights(const float* w_packed, int Cout, int Cin, float* out, hip
 int launch_pc16_weights(const void* w16, int Cout, int Cin, void* dst, hipStream_t s, int taps = 9);
 // 16-bit small-image kernel (conv16_smallm.hip): shapes it takes, its statistics geometry (blocks of min(32, H W) pixels)
 bool conv16_smallm_ok(int B, int H, int W, int C1, int C2, int Cout, int taps);
+bool conv16_smallm_enabled();              // not switched off by a hook (FLOWSE_NO_SMALLM, FLOWSE_FORCE_GENERIC_CONV)
 int conv16_smallm_stats_blocks(int B, int H, int W);
-inline int64_t conv_wino_numel(int Cout, int Cin) { return (int64_t)Cout * 18 * Cin; }
 // F(4,3) x F(2,3) weight transform, packed [Cout][9][Cin] -> fragment order [Cout/32][h][Cin/32][6][4][64][4], on device
 int launch_w2d_weights(const float* w_packed, int Cout, int Cin, float* out, hipStream_t s);
-inline int64_t conv_w2d_numel(int Cout, int Cin) { return (int64_t)Cout * 24 * Cin; }
 // the two-dimensional Winograd kernel can run this shape (whether it should: conv_route)
 bool conv_w2d_shape_ok(int B, int H, int W, int C1, int C2, int Cout, int taps);
 // the kernel itself, for a caller that asks for it by name (flowse_op_conv3x3_w2d): checks its own preconditions
@@ -330,7 +329,6 @@ int conv_smallm_stats_blocks(int B, int H, int W);
 // streaming fp32 1x1 kernel (conv_1x1.hip): shapes it takes, its statistics geometry (blocks of 256 pixels)
 bool conv1x1_stream_ok(int B, int H, int W, int C1, int C2, int Cout, int taps);
 int conv1x1_stream_stats_blocks(int B, int H, int W);
-bool conv_w2d_enabled();                   // FLOWSE_W2D (read once): the model handle keeps the 2-D weights and uses the kernel
 // whole-K F(4,3) launches of this shape use 128-channel blocks (conv3x3_f43_kernel<GN, false, 2>)
 bool conv_f43_wide(int B, int H, int W, int Cout);
 // host helper: split fp32 conv weights [Cout][Cin][3][3] into the packed bf16 planes described above
@@ -359,12 +357,41 @@ enum ConvKernel { CK_HEAD4, CK_HEAD4_16, CK_SMALLM, CK_1X1_STREAM, CK_W2D, CK_F4
                   CK_HALO16, CK_PC16, CK_SMALLM16B, CK_FLAT, CK_FLAT_SPLITK, CK_FLAT16, CK_FLAT16_SPLITK, CK_CIN4,
                   CK_CIN4_STATS, CK_CIN4_MFMA, CK_NONE };
 const char* conv_kernel_name(ConvKernel k);
+// ---- the weights a conv kernel can read next to the packed fp32 `w`.  The first CW_COPIES are the derived copies, made on
+// the device from the packed weights: one entry of the table each (conv_copy), named after its ConvArgs field.  CW_WQ -- the
+// weights in a 16-bit type, the conv's operand in the 16-bit storage modes, the bf16 planes of the fp32 ones -- is not
+// derived here: it has a bit in ConvRoute::reads and a case in conv_set_weight only.
+enum ConvWeight { CW_WINO, CW_WINO2, CW_WSM, CW_WSM16, CW_WFRAG, CW_COPIES, CW_WQ = CW_COPIES, CW_COUNT };
+struct ConvCopy {
+    const char* name;       // the ConvArgs field
+    int esize;              // bytes per element
+    bool mirror;            // the model handle keeps it at the conv's own offset in a blob-sized buffer (else: packed, 64-float aligned)
+    // the rule: a conv [Cout][taps][Cin] of a network whose activations are stored as act_dt gets this copy -- alignment, byte
+    // limit of the kernels' 32-bit addressing and environment hooks, all of it
+    bool (*gets)(int Cout, int taps, int Cin, int act_dt);
+    int64_t (*numel)(int Cout, int taps, int Cin);
+    // makes it: from the packed fp32 weights `w`, or (esize 2) from their elementwise 16-bit twin `w16`
+    int (*make)(const float* w, const void* w16, int Cout, int taps, int Cin, void* out, hipStream_t s);
+};
+const ConvCopy& conv_copy(int k);              // k < CW_COPIES
+inline void conv_set_weight(ConvArgs& c, int k, const void* p) {      // the ConvArgs pointer of one member of ConvRoute::reads
+    switch (k) {
+        case CW_WINO: c.wino = static_cast<const float*>(p); break;
+        case CW_WINO2: c.wino2 = static_cast<const float*>(p); break;
+        case CW_WSM: c.wsm = static_cast<const float*>(p); break;
+        case CW_WSM16: c.wsm16 = static_cast<const float*>(p); break;
+        case CW_WFRAG: c.wfrag = p; break;
+        case CW_WQ: c.wq = p; break;
+    }
+}
 struct ConvRoute {
     ConvKernel kernel = CK_NONE;
     int ksplit = 1;              // K slices (> 1 only when a slab was offered)
     bool reduce = false;         // a separate reduction launch follows (launch_splitk_reduce[_gn])
     int stats_nblk = 0;          // statistics blocks per sample the kernel (or its reduction) writes; 0: it cannot
     bool gn_on_load = false;     // the kernel can normalise its input on load
+    unsigned reads = 0;          // bit k: the kernel dereferences the ConvArgs pointer of ConvWeight k (the packed `w` aside)
+    bool reads_weight(int k) const { return (reads >> k) & 1u; }
     double issued = 1.0;         // issued / nominal FLOPs as the plan counts them: 1/3, 1/2, 3 or 1
     int err = OK;                // != OK: no kernel takes the request; err_text is launch_conv's message
     const char* err_text = "";

@@ -91,6 +91,7 @@ __global__ __launch_bounds__(512, 2) void conv_smallm16b_kernel(ConvArgs a) {
 // shapes the kernel takes in the 16-bit storage modes: at most 2048 pixels, 32-aligned channel counts, whole statistics
 // blocks, and not one of the launches the LDS-halo kernels cover anyway (those need >= 128 blocks of 128 pixels)
 static const bool g_no_smallm16 = getenv("FLOWSE_NO_SMALLM") != nullptr || getenv("FLOWSE_FORCE_GENERIC_CONV") != nullptr;
+bool conv16_smallm_enabled() { return !g_no_smallm16; }
 bool conv16_smallm_ok(int B, int H, int W, int C1, int C2, int Cout, int taps) {
     if (g_no_smallm16 || !sm_shape_ok(B, H, W, C1, C2, Cout, taps, 2048, 2) || sm_stats_blocks(H * W) == 0) return false;
     return !conv16_uses_halo(B, H, W, C1, C2, Cout, taps);

@@ -28,7 +28,7 @@ static const bool g_no_wino = getenv("FLOWSE_NO_WINOGRAD") != nullptr;
 static const bool g_no_wino_policy = g_no_wino || g_no_halo || g_force_generic;
 // FLOWSE_W2D=0 keeps the 1-D F(4,3) kernel everywhere (A-B hook); default: the 2-D kernel where w2d_wanted says so
 static const bool g_w2d = !(getenv("FLOWSE_W2D") && getenv("FLOWSE_W2D")[0] == '0');
-bool conv_w2d_enabled() { return g_w2d && !g_no_wino_policy; }
+static bool conv_w2d_enabled() { return g_w2d && !g_no_wino_policy; }
 // FLOWSE_NO_SMALLM=1: small images run the split-K flat / F(4,3) kernels + reduction launches of rounds 1-4 (A-B hook)
 static const bool g_no_smallm = getenv("FLOWSE_NO_SMALLM") != nullptr;
 static const int g_smallm_max = getenv("FLOWSE_SMALLM_MAX") ? atoi(getenv("FLOWSE_SMALLM_MAX")) : 2048;
@@ -44,13 +44,63 @@ bool conv_force_generic() { return g_force_generic; }
 // (4 waves side by side along N, 16 MFMAs per wave and step) and are sliced along K accordingly.
 bool conv_small_m(int64_t M, int Cout) { return M <= 64 && Cout > 64; }
 
+// ------------------------------------------------------------------------------------- the derived weight copies
+// One entry per copy (ConvCopy, common.h): which convs get it, how large it is, what makes it.  The model handle uploads
+// exactly what the rules name (flowse_model_load_weights), offers it (Builder::offer) and the route below -- which names
+// in ConvRoute::reads the copies its kernel reads -- only ever chooses among what was offered.
+static int64_t numel_packed(int Cout, int taps, int Cin) { return (int64_t)Cout * taps * Cin; }
+static int64_t numel_f43(int Cout, int, int Cin) { return (int64_t)Cout * 18 * Cin; }      // 18 transformed taps per channel pair
+static int64_t numel_w2d(int Cout, int, int Cin) { return (int64_t)Cout * 24 * Cin; }      // 24
+static bool fits(int64_t numel, int esize) { return numel * esize < (1LL << 31); }         // one 32-bit buffer descriptor
+static bool aligned(int Cout, int Cin, int cout_step) { return Cin > 0 && (Cin % KC) == 0 && (Cout % cout_step) == 0; }
+static bool gets_wino(int Cout, int taps, int Cin, int act_dt) {
+    return act_dt == DT_F32 && taps == 9 && aligned(Cout, Cin, 64) && fits(numel_f43(Cout, 9, Cin), 4);
+}
+static bool gets_wino2(int Cout, int taps, int Cin, int act_dt) {
+    return gets_wino(Cout, taps, Cin, act_dt) && conv_w2d_enabled() && fits(numel_w2d(Cout, 9, Cin), 4);
+}
+// both fragment orders of the small-image kernels; the attention projections are 1x1 convs and get them too
+static bool gets_wsm(int Cout, int taps, int Cin, int act_dt) {
+    return act_dt == DT_F32 && !g_no_smallm && !g_force_generic && aligned(Cout, Cin, 32) && fits(numel_packed(Cout, taps, Cin), 4);
+}
+// 16-bit storage: the 3x3 convs of the producer / consumer kernel, and whatever the 16-bit small-image kernel can take
+static bool gets_wfrag(int Cout, int taps, int Cin, int act_dt) {
+    return act_dt != DT_F32 && fits(numel_packed(Cout, taps, Cin), 2) &&
+           ((taps == 9 && aligned(Cout, Cin, 128)) || (conv16_smallm_enabled() && aligned(Cout, Cin, 32)));
+}
+const ConvCopy& conv_copy(int k) {
+    static const ConvCopy table[CW_COPIES] = {
+        {"wino", 4, false, gets_wino, numel_f43,
+         [](const float* w, const void*, int Cout, int, int Cin, void* out, hipStream_t s) {
+             return launch_f43_weights(w, Cout, Cin, static_cast<float*>(out), s);
+         }},
+        {"wino2", 4, false, gets_wino2, numel_w2d,
+         [](const float* w, const void*, int Cout, int, int Cin, void* out, hipStream_t s) {
+             return launch_w2d_weights(w, Cout, Cin, static_cast<float*>(out), s);
+         }},
+        {"wsm", 4, true, gets_wsm, numel_packed,
+         [](const float* w, const void*, int Cout, int taps, int Cin, void* out, hipStream_t s) {
+             return launch_smallm_weights(w, Cout, taps, Cin, static_cast<float*>(out), s, false);
+         }},
+        {"wsm16", 4, true, gets_wsm, numel_packed,
+         [](const float* w, const void*, int Cout, int taps, int Cin, void* out, hipStream_t s) {
+             return launch_smallm_weights(w, Cout, taps, Cin, static_cast<float*>(out), s, true);
+         }},
+        {"wfrag", 2, true, gets_wfrag, numel_packed,
+         [](const float*, const void* w16, int Cout, int taps, int Cin, void* out, hipStream_t s) {
+             return launch_pc16_weights(w16, Cout, Cin, out, s, taps);
+         }},
+    };
+    return table[k];
+}
+
 // The two-dimensional Winograd form: whole-K launches on images that give every CU at least two blocks of 16 x 16 pixels x
 // 64 channels, or one of 32 channels (below that the 1-D kernel's K slices fill the chip better).
 static const int g_w2d_min_blocks = getenv("FLOWSE_W2D_MIN_BLOCKS") ? atoi(getenv("FLOWSE_W2D_MIN_BLOCKS")) : 128;
 bool conv_w2d_shape_ok(int B, int H, int W, int C1, int C2, int Cout, int taps) {
     if (g_no_wino_policy || taps != 9 || (H & 15) || (W & 15) || (C1 % KC) || (C2 % KC) || (Cout % 64) || B < 1) return false;
     const int64_t cmax = C1 > C2 ? C1 : C2;
-    return (int64_t)Cout * 24 * (C1 + C2) * 4 < (1LL << 31) && ((int64_t)H * W + 2 * W + 2) * cmax * 4 < (1LL << 31);
+    return fits(numel_w2d(Cout, 9, C1 + C2), 4) && ((int64_t)H * W + 2 * W + 2) * cmax * 4 < (1LL << 31);
 }
 
 // ------------------------------------------------------------------------------------------- the policy, fp32 storage
@@ -124,7 +174,7 @@ static Fp32Policy fp32_policy(const ConvShape& q, bool head4) {
                        taps == 9 && !(H & 7) && !(W & 15) && !(C1 % KC) && !(C2 % KC) && !(Cout & 3) &&
                        (p.ksplit == 1 || p.ksplit == p.f43) &&                                             // only the Winograd kernel runs split
                        (int64_t)(9 * W + 18) * cmax * 4 < (1LL << 31) && (int64_t)Cout * 9 * Cin * 4 < (1LL << 31));
-    p.wino = !g_no_wino && (Cout % 64) == 0 && p.halo && p.f43 >= 1 && (int64_t)Cout * 18 * Cin * 4 < (1LL << 31) &&
+    p.wino = !g_no_wino && p.halo && p.f43 >= 1 && gets_wino(Cout, taps, Cin, DT_F32) &&
              // the F(4,3) kernel addresses a whole sample through one buffer descriptor per source tensor
              ((int64_t)H * W + 2 * W + 2) * cmax * 4 < (1LL << 31);
     p.w2d = p.halo && w2d_wanted(B, H, W, C1, C2, Cout, taps);
@@ -187,6 +237,19 @@ static bool route_gn_on_load(ConvKernel k) {
     }
 }
 
+// The weight pointers the kernel dereferences next to the packed `w` (ConvRoute::reads)
+static unsigned route_reads(ConvKernel k, const ConvShape& q) {
+    switch (k) {
+        case CK_F43: case CK_F43_SPLITK: return 1u << CW_WINO;
+        case CK_W2D: return 1u << CW_WINO2;
+        case CK_1X1_STREAM: return 1u << CW_WSM;
+        case CK_SMALLM: return 1u << (conv_smallm_tile16(q.B, q.H, q.W) ? CW_WSM16 : CW_WSM);
+        case CK_HALO_BF16X3: case CK_HALO16: case CK_FLAT16: case CK_FLAT16_SPLITK: return 1u << CW_WQ;
+        case CK_PC16: case CK_SMALLM16B: return 1u << CW_WQ | 1u << CW_WFRAG;
+        default: return 0;                               // (head4_16 reads the fp32 `w`)
+    }
+}
+
 ConvRoute conv_route(const ConvShape& q, const ConvOffer& o) {
     const int B = q.B, H = q.H, W = q.W, C1 = q.C1, C2 = q.C2, Cout = q.Cout, taps = q.taps;
     const bool in16 = q.in_dt != DT_F32;
@@ -204,6 +267,7 @@ ConvRoute conv_route(const ConvShape& q, const ConvOffer& o) {
     const bool wino = o.wino && p.wino;
     auto fail = [&](int err, const char* text) {
         r.kernel = CK_NONE;
+        r.reads = 0;
         r.err = err;
         r.err_text = text;
         return r;
@@ -213,6 +277,7 @@ ConvRoute conv_route(const ConvShape& q, const ConvOffer& o) {
         r.reduce = ks > 1;
         r.stats_nblk = route_stats_blocks(k, q);
         r.gn_on_load = route_gn_on_load(k);
+        r.reads = route_reads(k, q);
         r.issued = k == CK_W2D ? 1.0 / 3.0 : wino ? 0.5 : k == CK_HALO_BF16X3 ? 3.0 : 1.0;
         if (o.gn && !r.gn_on_load) return fail(ERR_ARG, "conv: fused GroupNorm input requested for a shape the halo kernel does not cover");
         return r;
@@ -313,7 +378,7 @@ int launch_conv(const ConvArgs& a, hipStream_t s, bool with_reduce) {
         return ERR_ARG;
     }
     ConvOffer o;
-    o.wino = a.wino != nullptr; o.wino2 = a.wino2 != nullptr; o.wsm = a.wsm != nullptr; o.wfrag = a.wfrag != nullptr;
+    o.wino = a.wino != nullptr; o.wino2 = a.wino2 != nullptr; o.wsm = a.wsm != nullptr || a.wsm16 != nullptr; o.wfrag = a.wfrag != nullptr;
     o.wq = a.wq != nullptr; o.terms = a.terms; o.wq_f16 = a.wq_f16 != 0;
     o.slab = a.partial != nullptr;
     o.gn = a.gn.mean != nullptr;

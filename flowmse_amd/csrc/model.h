@@ -1,13 +1,13 @@
 // Internal types of the model handle: NCSN++ module list, parameter table, launch plan (model_*.hip), and the six
 // functions through which the entries that live beside their kernels reach the handle (at the end).
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <functional>
 #include <map>
-#include <set>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -169,17 +169,18 @@ struct WeightSet {
     // between kernels are bf16 / half; d_w16 is an elementwise 16-bit copy of the packed weight blob d_w (same offsets)
     int act_dt = DT_F32;
     DevBuf<uint16_t> d_w16;
-    // 3x3 convs with Cin % 32 == 0 and Cout % 128 == 0 again in MFMA fragment order (launch_pc16_weights) at the SAME offsets
-    // as in d_w16: the B operand of conv3x3_pc16_kernel's consumer waves, straight from L2
-    DevBuf<uint16_t> d_wfrag;
-    std::set<int64_t> frag_offs;           // packed weight offsets that have fragment-order weights
-    DevBuf<float> d_wino;                  // F(4,3) Winograd weights of the 3x3 convs the Winograd kernel can take
-    std::map<int64_t, int64_t> wino_of;    // packed weight offset (d_w) -> offset in d_wino
-    DevBuf<float> d_wino2;                 // F(4,3) x F(2,3) weights of the same convs (conv3x3_w2d_kernel; FLOWSE_W2D=0: absent)
-    std::map<int64_t, int64_t> wino2_of;
-    DevBuf<float> d_wsm;                   // fragment-order copy of the conv weights with 32-aligned channel counts (conv_smallm_kernel)
-    DevBuf<float> d_wsm16;                 // the same in the 16 x 16-tile fragment order (conv_smallm16_kernel), same size and offsets
-    std::set<int64_t> wsm_offs;            // packed weight offsets (d_w) that have a copy at the SAME offset in d_wsm
+    // The derived copies of the conv weights, one per entry of conv_copy (common.h): at[w] = element offset in buf of the copy
+    // of the conv at packed offset w, for exactly the convs whose rule (ConvCopy::gets) held at the last upload.  The mirrors
+    // (ConvCopy::mirror) are blob-sized with at[w] = w; the others are packed, each entry rounded up to 64 elements.
+    struct Copy {
+        DevBuf<char> buf;
+        std::map<int64_t, int64_t> at;
+    } copies[CW_COPIES];
+    bool has_copy(int k, int64_t w) const { return copies[k].at.count(w) != 0; }
+    const void* copy_ptr(int k, int64_t w) const {       // null: the conv has no such copy
+        const auto it = copies[k].at.find(w);
+        return it == copies[k].at.end() ? nullptr : copies[k].buf.p + it->second * conv_copy(k).esize;
+    }
     int device = -1;                       // HIP device that owns every d_* buffer of the set and of its handles
     bool storage16() const { return act_dt != DT_F32; }
 };
@@ -236,10 +237,8 @@ Module resblock_module(int in_ch, int out_ch, bool up = false, bool down = false
 Module simple_module(ModKind k, int in_ch, int out_ch);
 struct Packer {
     std::vector<float> host;
-    struct WinoReq { int64_t off; int Cout, Cin; };
-    std::vector<WinoReq> wino;             // 3x3 convs that also get F(4,3) weights (transformed on the device)
-    struct SmReq { int64_t off; int Cout, Cin, taps; };
-    std::vector<SmReq> smallm;             // convs that also get a fragment-order copy (small-M kernel)
+    struct Conv { int64_t off; int Cout, Cin, taps; };
+    std::vector<Conv> convs;               // every conv weight of the blob (the attention projections are 1x1 convs)
     int64_t put(int64_t n) {
         const int64_t off = ((int64_t)host.size() + 63) & ~(int64_t)63;
         host.resize(off + n, 0.f);

@@ -194,7 +194,8 @@ static void each_owned_buffer(M* m, Fn f) {
 }
 template <class W, class Fn>
 static void each_weight_buffer(W* w, Fn f) {
-    f(w->d_w); f(w->d_wq); f(w->d_w16); f(w->d_wfrag); f(w->d_wino); f(w->d_wino2); f(w->d_wsm); f(w->d_wsm16);
+    f(w->d_w); f(w->d_wq); f(w->d_w16);
+    for (auto& c : w->copies) f(c.buf);
 }
 
 // The buffers only this handle holds: workspace, plans, time table, RK scratch, CallBlock, stream, events, profiler.
@@ -238,79 +239,34 @@ static bool weights_shared(const flowse_model* m, const char* what) {
 }
 
 // ------------------------------------------------------------------------- flowse_model_load_weights, table by table
-// Each step derives one table of the set from the packed fp32 blob that is already in d_w (and from the packer's lists).
-// The weight buffers grow without a synchronisation: the upload synchronises once, before the first of them.
+// Each step derives one table of the set from the packed fp32 blob that is already in d_w (and from the packer's list of
+// convs).  The weight buffers grow without a synchronisation: the upload synchronises once, before the first of them.
 
-// 16-bit storage modes: the elementwise 16-bit twin of the packed blob (conv weights keep their offsets) and, at the same
-// offsets, the fragment-order copies for the producer / consumer 3x3 kernel and the 16-bit small-image kernel
-static int upload_16bit_copies(WeightSet* w, Packer& pk) {
-    const int64_t n = (int64_t)pk.host.size(), n16 = (n + 3) & ~(int64_t)3;
-    if (const int rc = w->d_w16.reserve(n16, false)) return rc;
-    if (const int rc = launch_convert(w->d_w, DT_F32, w->d_w16, w->act_dt, n & ~(int64_t)3, nullptr)) return rc;
-    w->frag_offs.clear();
-    if (const int rc = w->d_wfrag.reserve(n16, false)) return rc;
-    for (auto& r : pk.wino) {
-        if ((r.Cout % 128) != 0 || (int64_t)r.Cout * 9 * r.Cin * 2 >= (1LL << 31)) continue;
-        if (const int rc = launch_pc16_weights(w->d_w16 + r.off, r.Cout, r.Cin, w->d_wfrag + r.off, nullptr)) return rc;
-        w->frag_offs.insert(r.off);
-    }
-    // ... and for every other conv with 32-aligned channel counts (1x1 shortcuts, attention projections, 3x3 with
-    // Cout % 128 != 0): the 16-bit small-image kernel reads the same layout
-    if (conv16_smallm_ok(1, 4, 4, 32, 0, 32, 1)) {
-        for (auto& r : pk.smallm) {
-            if (w->frag_offs.count(r.off) || (int64_t)r.Cout * r.taps * r.Cin * 2 >= (1LL << 31)) continue;
-            if (const int rc = launch_pc16_weights(w->d_w16 + r.off, r.Cout, r.Cin, w->d_wfrag + r.off, nullptr, r.taps)) return rc;
-            w->frag_offs.insert(r.off);
-        }
-    }
-    pk.wino.clear();                         // no fp32 Winograd kernels run on 16-bit activations
-    return OK;
+// 16-bit storage modes: the elementwise 16-bit twin of the packed blob (conv weights keep their offsets)
+static int upload_16bit_twin(WeightSet* w, int64_t n) {
+    if (const int rc = w->d_w16.reserve((n + 3) & ~(int64_t)3, false)) return rc;
+    return launch_convert(w->d_w, DT_F32, w->d_w16, w->act_dt, n & ~(int64_t)3, nullptr);
 }
 
-// F(4,3) Winograd weights, derived on the device
-static int upload_f43_weights(WeightSet* w, const Packer& pk) {
-    w->wino_of.clear();
+// Copy k of conv_copy for every conv its rule names, derived on the device
+static int upload_copy(WeightSet* w, const Packer& pk, int k) {
+    const ConvCopy& cp = conv_copy(k);
+    WeightSet::Copy& c = w->copies[k];
+    c.at.clear();
     int64_t total = 0;
-    for (auto& r : pk.wino) {
-        w->wino_of[r.off] = total;
-        total += (conv_wino_numel(r.Cout, r.Cin) + 63) & ~(int64_t)63;
+    for (auto& r : pk.convs) {
+        if (!cp.gets(r.Cout, r.taps, r.Cin, w->act_dt)) continue;
+        c.at[r.off] = cp.mirror ? r.off : total;
+        total += (cp.numel(r.Cout, r.taps, r.Cin) + 63) & ~(int64_t)63;
     }
-    if (const int rc = w->d_wino.reserve(total, false)) return rc;
-    for (auto& r : pk.wino)
-        if (const int rc = launch_f43_weights(w->d_w + r.off, r.Cout, r.Cin, w->d_wino + w->wino_of[r.off], nullptr)) return rc;
-    return OK;
-}
-
-// fragment-order copies for the small-M kernels (fp32 activations only), at the same offsets as in d_w
-static int upload_smallm_copies(WeightSet* w, const Packer& pk) {
-    w->wsm_offs.clear();
-    if (w->storage16() || pk.smallm.empty() || !conv_smallm_ok(1, 4, 4, 32, 0, 32, 1)) return OK;
-    if (const int rc = w->d_wsm.reserve(pk.host.size(), false)) return rc;
-    if (const int rc = w->d_wsm16.reserve(pk.host.size(), false)) return rc;
-    for (auto& r : pk.smallm) {
-        if ((int64_t)r.Cout * r.taps * r.Cin * 4 >= (1LL << 31)) continue;
-        if (const int rc = launch_smallm_weights(w->d_w + r.off, r.Cout, r.taps, r.Cin, w->d_wsm + r.off, nullptr)) return rc;
-        if (const int rc = launch_smallm_weights(w->d_w + r.off, r.Cout, r.taps, r.Cin, w->d_wsm16 + r.off, nullptr, true)) return rc;
-        w->wsm_offs.insert(r.off);
-    }
-    return OK;
-}
-
-// F(4,3) x F(2,3) weights of the F(4,3) convs (the two-dimensional kernel takes the large images)
-static int upload_w2d_weights(WeightSet* w, const Packer& pk) {
-    w->wino2_of.clear();
-    if (!conv_w2d_enabled()) return OK;
-    int64_t total = 0;
-    for (auto& r : pk.wino) {
-        if ((int64_t)r.Cout * 24 * r.Cin * 4 >= (1LL << 31)) continue;
-        w->wino2_of[r.off] = total;
-        total += (conv_w2d_numel(r.Cout, r.Cin) + 63) & ~(int64_t)63;
-    }
-    if (const int rc = w->d_wino2.reserve(total, false)) return rc;
-    for (auto& r : pk.wino) {
-        const auto it = w->wino2_of.find(r.off);
-        if (it == w->wino2_of.end()) continue;
-        if (const int rc = launch_w2d_weights(w->d_w + r.off, r.Cout, r.Cin, w->d_wino2 + it->second, nullptr)) return rc;
+    if (c.at.empty()) return OK;
+    if (cp.mirror) total = (int64_t)pk.host.size();
+    if (const int rc = c.buf.reserve((size_t)total * cp.esize, false)) return rc;
+    for (auto& r : pk.convs) {
+        const auto it = c.at.find(r.off);
+        if (it == c.at.end()) continue;
+        const void* w16 = w->storage16() ? w->d_w16 + r.off : nullptr;
+        if (const int rc = cp.make(w->d_w + r.off, w16, r.Cout, r.taps, r.Cin, c.buf.p + it->second * cp.esize, nullptr)) return rc;
     }
     return OK;
 }
@@ -496,10 +452,8 @@ int flowse_model_load_weights(flowse_model* m, const float* blob, int64_t numel)
     if (rc != OK) return rc;
     FLOWSE_HIP(hipMemcpy(w->d_w, pk.host.data(), pk.host.size() * sizeof(float), hipMemcpyHostToDevice));
     w->act_dt = storage_type_for(m);
-    if (w->storage16()) rc = upload_16bit_copies(w, pk);
-    if (rc == OK) rc = upload_f43_weights(w, pk);
-    if (rc == OK) rc = upload_smallm_copies(w, pk);
-    if (rc == OK) rc = upload_w2d_weights(w, pk);
+    if (w->storage16()) rc = upload_16bit_twin(w, (int64_t)pk.host.size());
+    for (int k = 0; k < CW_COPIES && rc == OK; ++k) rc = upload_copy(w, pk, k);
     if (rc != OK) return rc;
     FLOWSE_HIP(hipDeviceSynchronize());
     return upload_bf16_planes(w, blob);

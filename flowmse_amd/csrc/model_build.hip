@@ -200,8 +200,7 @@ static int64_t pack_conv(Packer& pk, const float* src, int Cout, int Cin, int ta
         for (int ci = 0; ci < Cin; ++ci)
             for (int t = 0; t < taps; ++t)
                 dst[((int64_t)co * taps + t) * Cin + ci] = src[((int64_t)co * Cin + ci) * taps + t];
-    if (taps == 9 && (Cin % 32) == 0 && (Cout % 64) == 0) pk.wino.push_back({off, Cout, Cin});
-    if ((Cin % 32) == 0 && (Cout % 32) == 0) pk.smallm.push_back({off, Cout, Cin, taps});
+    pk.convs.push_back({off, Cout, Cin, taps});
     return off;
 }
 static int64_t pack_copy(Packer& pk, const float* src, int64_t n) {
@@ -289,11 +288,9 @@ int pack_weights(flowse_model* m, const float* blob, Packer& pk) {
                 for (int o = 0; o < C; ++o)
                     for (int i = 0; i < C; ++i) pk.host[mod.w_o + (int64_t)o * C + i] = W3[(int64_t)i * C + o];
                 mod.w_o_b = pack_copy(pk, P(p + 9), C);
-                // the two projections are 1x1 convs: fragment-order copies for the small-M kernel (single utterances)
-                if ((C % 32) == 0) {
-                    pk.smallm.push_back({mod.w_qkv, 3 * C, C, 1});
-                    pk.smallm.push_back({mod.w_o, C, C, 1});
-                }
+                // the two projections are 1x1 convs (fragment-order copies for the small-image kernels: single utterances)
+                pk.convs.push_back({mod.w_qkv, 3 * C, C, 1});
+                pk.convs.push_back({mod.w_o, C, C, 1});
                 break;
             }
         }

@@ -222,11 +222,11 @@ struct Builder {
             of.wq = true;
             of.terms = 1;
             of.wq_f16 = idt == DT_F16;
-            of.wfrag = ws.frag_offs.count(w) != 0;
+            of.wfrag = ws.has_copy(CW_WFRAG, w);
         } else {
-            of.wino = taps == 9 && ws.wino_of.count(w) != 0;
-            of.wino2 = taps == 9 && ws.wino2_of.count(w) != 0;
-            of.wsm = ws.wsm_offs.count(w) != 0;
+            of.wino = ws.has_copy(CW_WINO, w);
+            of.wino2 = ws.has_copy(CW_WINO2, w);
+            of.wsm = ws.has_copy(CW_WSM, w);         // (and CW_WSM16: one rule)
             of.wq = !m->storage16() && wq_off >= 0 && ws.precision != 0 && taps == 9;
             of.terms = !of.wq ? 0 : ws.precision == 1 ? 3 : 1;
             of.wq_f16 = of.wq && ws.precision == 3;
@@ -311,12 +311,15 @@ struct Builder {
         }
         const size_t st_off = o.st_off;
         const GnBuf gbuf = has_gin ? *gin : GnBuf();
-        // the optional weight copies the route's kernel reads
-        const ConvKernel kn = rt.kernel;
-        const bool use_wq = !in16 && (kn == CK_HALO_BF16X3 || kn == CK_HALO16);
-        const bool use_wfrag = kn == CK_PC16 || kn == CK_SMALLM16B;
-        const int64_t wino_off = (kn == CK_F43 || kn == CK_F43_SPLITK) ? M->wt->wino_of.at(w) : -1;
-        const int64_t wino2_off = kn == CK_W2D ? M->wt->wino2_of.at(w) : -1;
+        // the derived copies the route's kernel reads: it chose among what offer() found in the weight set (the buffers
+        // stay where they are for as long as the plan lives: an upload drops the plans)
+        std::array<const void*, CW_COPIES> wcopy{};
+        for (int k = 0; k < CW_COPIES; ++k)
+            if (rt.reads_weight(k) && !(wcopy[k] = M->wt->copy_ptr(k, w))) {
+                set_error("internal: %s@%dx%d runs %s, whose %s copy was not uploaded", label.c_str(), H, Wd,
+                          conv_kernel_name(rt.kernel), conv_copy(k).name);
+                failed = true;
+            }
         const int terms = M->wt->precision == 1 ? 3 : 1;
         const size_t part_off = ks > 1 ? arena.alloc((size_t)ks * Bn * H * Wd * Cout * sizeof(float)) : 0;
         const size_t table_off = M_table_off;     // by value: the Builder dies before the plan runs
@@ -325,8 +328,9 @@ struct Builder {
         const size_t f1_off = has_fold ? fold->s1->off : 0, f2_off = has_fold && fold->s2 ? fold->s2->off : 0;
         const int FC1 = has_fold ? fold->s1->C : 0, FC2 = has_fold && fold->s2 ? fold->s2->C : 0;
         const int64_t fold_w = has_fold ? fold->w : -1, fold_b = has_fold ? fold->bias : -1;
+        const void* wfrag_sc = has_fold ? M->wt->copy_ptr(CW_WFRAG, fold_w) : nullptr;
         if (has_fold && (res || extra || ks != 1 || !in16 || taps != 9 || fold->s1->H != H || fold->s1->W != Wd ||
-                         fold->s1->dt != idt || !M->wt->frag_offs.count(w) || !M->wt->frag_offs.count(fold_w))) {
+                         fold->s1->dt != idt || !M->wt->has_copy(CW_WFRAG, w) || !wfrag_sc)) {
             set_error("internal: shortcut fold requested for a conv that cannot take it (%s)", label.c_str());
             failed = true;
         }
@@ -367,25 +371,22 @@ struct Builder {
                 c.SC1 = FC1;
                 c.sc2 = FC2 ? M->A(f2_off) : nullptr;
                 c.SC2 = FC2;
-                c.wfrag_sc = M->wt->d_wfrag + fold_w;
+                c.wfrag_sc = wfrag_sc;
                 c.bias_x = fold_b >= 0 ? M->W(fold_b) : nullptr;
             }
             c.in_dt = idt;
             c.out_dt = odt;
+            for (int k = 0; k < CW_COPIES; ++k)
+                if (wcopy[k]) conv_set_weight(c, k, wcopy[k]);
             if (in16) {                                   // [Cout][taps][Cin] in the storage type: same offsets as d_w
-                c.wq = M->wt->d_w16 + w;
-                if (use_wfrag) c.wfrag = M->wt->d_wfrag + w;
                 c.terms = 1;
                 c.wq_f16 = idt == DT_F16 ? 1 : 0;
-            } else if (use_wq) {
-                c.wq = M->wt->d_wq + wq_off;
+                if (rt.reads_weight(CW_WQ)) conv_set_weight(c, CW_WQ, M->wt->d_w16 + w);
+            } else if (rt.reads_weight(CW_WQ)) {           // the bf16 planes
                 c.terms = terms;
                 c.wq_f16 = M->wt->precision == 3 ? 1 : 0;
+                conv_set_weight(c, CW_WQ, M->wt->d_wq + wq_off);
             }
-            if (wino_off >= 0) c.wino = M->wt->d_wino + wino_off;
-            if (wino2_off >= 0) c.wino2 = M->wt->d_wino2 + wino2_off;
-            if (kn == CK_SMALLM || kn == CK_1X1_STREAM) c.wsm = M->wt->d_wsm + w;
-            if (kn == CK_SMALLM) c.wsm16 = M->wt->d_wsm16 + w;
             return c;
         };
         const double flops = 2.0 * Bn * H * Wd * (double)Cout * (taps * (C1 + C2) + (FC1 + FC2));
@@ -507,7 +508,7 @@ struct Builder {
         // launch (ConvArgs::sc1) -- no launch, no round trip of its output through HBM, one read of x less
         const int xc2 = (!mod.up && !mod.down && x2) ? x2->C : 0;
         const bool fold_sc = mod.shortcut && m->wt->act_dt != DT_F32 && !merge_sc && !getenv("FLOWSE_NO_SCFOLD") &&
-                             m->wt->frag_offs.count(mod.w_c2) && c1_plan.kernel == CK_PC16 && (x1.C % 32) == 0 && (xc2 % 32) == 0 &&
+                             m->wt->has_copy(CW_WFRAG, mod.w_c2) && c1_plan.kernel == CK_PC16 && (x1.C % 32) == 0 && (xc2 % 32) == 0 &&
                              x1.C + xc2 >= 96 && x1.dt == m->wt->act_dt;
         // fp32 up blocks whose shortcut is a launch of its own: Conv_2 has no spatial extent and upsample_2d filters every
         // channel alike, so W . up(x) = up(W . x) -- the 1x1 runs BEFORE the upsampling, on a quarter of the pixels, and the

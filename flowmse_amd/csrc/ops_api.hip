@@ -3,6 +3,7 @@
 // this file does not see the handle's types (no model.h).  No kernels here.
 #include <algorithm>
 #include <cstdio>
+#include <string>
 
 #include "../../include/flowse_hip.h"
 #include "common.h"
@@ -32,6 +33,20 @@ static int op_gn_prologue(const float* in1, int C1, const float* in2, int C2, co
     const int rc = launch_gn_stats(in1, C1, in2, C2, B, HW, scratch, nblk, s);
     if (rc != OK) return rc;
     return launch_gn_finalize(scratch, nblk, C, nullptr, 0, 0, B, HW, std::min(C / 4, 32), gamma, eps, mean, scl, s);
+}
+
+// Copy k of conv_copy of c's weights (`w16`: their 16-bit twin, for the 16-bit copies), made at dst; c then points at it
+static int op_make_copy(ConvArgs& c, int k, const void* w16, void* dst, hipStream_t s) {
+    const int rc = conv_copy(k).make(c.w, w16, c.Cout, c.taps, c.C1 + c.C2, dst, s);
+    if (rc == OK) conv_set_weight(c, k, dst);
+    return rc;
+}
+// elements of the derived copies a route reads
+static int64_t op_copies_numel(const ConvRoute& r, int Cout, int taps, int Cin) {
+    int64_t n = 0;
+    for (int k = 0; k < CW_COPIES; ++k)
+        if (r.reads_weight(k)) n += conv_copy(k).numel(Cout, taps, Cin);
+    return n;
 }
 
 // the caller's scratch of a 16-bit entry, handed out in sub-buffers rounded up to 256 bytes
@@ -79,8 +94,8 @@ static ConvOffer op_offer_f43() {                // flowse_op_conv3x3_f43's scra
 
 int64_t flowse_op_conv2d_scratch_floats(int B, int H, int W, int Cin, int Cout, int taps) {
     const ConvRoute r = op_route_f32(B, H, W, Cin, 0, Cout, taps, op_offer_scratch());
-    if (r.kernel == CK_SMALLM || r.kernel == CK_1X1_STREAM) return (int64_t)Cout * taps * Cin;   // fragment-order weight copy
-    return r.ksplit > 1 ? (int64_t)r.ksplit * B * H * W * Cout : 0;
+    // the fragment-order weight copy of a kernel that splits K inside the block, or the slab: never both
+    return op_copies_numel(r, Cout, taps, Cin) + (r.ksplit > 1 ? (int64_t)r.ksplit * B * H * W * Cout : 0);
 }
 
 int flowse_op_conv2d(const float* in1, int C1, const float* in2, int C2, const float* w, const float* bias,
@@ -94,16 +109,11 @@ int flowse_op_conv2d(const float* in1, int C1, const float* in2, int C2, const f
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (splitk_scratch) {                            // the model handle's kernel for this shape
         const ConvRoute r = op_route_f32(B, H, W, c.C1, c.C2, Cout, taps, op_offer_scratch());
-        if (r.kernel == CK_SMALLM || r.kernel == CK_1X1_STREAM) {
-            const bool t16 = r.kernel == CK_SMALLM && conv_smallm_tile16(B, H, W);
-            const int rc = launch_smallm_weights(w, Cout, taps, c.C1 + c.C2, splitk_scratch, s, t16);
-            if (rc != OK) return rc;
-            c.wsm = splitk_scratch;
-            c.wsm16 = t16 ? splitk_scratch : nullptr;
-        } else {
-            c.ksplit = r.ksplit;
-            c.partial = c.ksplit > 1 ? splitk_scratch : nullptr;
-        }
+        c.ksplit = r.ksplit;
+        c.partial = c.ksplit > 1 ? splitk_scratch : nullptr;
+        for (int k = 0; k < CW_COPIES; ++k)           // (at most one: the offer names one fragment-order copy)
+            if (r.reads_weight(k))
+                if (const int rc = op_make_copy(c, k, nullptr, splitk_scratch, s)) return rc;
     }
     return launch_conv(c, s);
 }
@@ -158,7 +168,8 @@ static int op_conv3x3_winograd(const float* in1, int C1, const float* in2, int C
     }
     if (!in2) C2 = 0;
     const ConvRoute r = op_route_f32(B, H, W, C1, C2, Cout, 9, op_offer_f43());
-    if (two_d ? !conv_w2d_shape_ok(B, H, W, C1, C2, Cout, 9) : (r.kernel != CK_F43 && r.kernel != CK_F43_SPLITK)) {
+    const int copy = two_d ? CW_WINO2 : CW_WINO;        // the entry names its kernel, and so the copy it reads
+    if (two_d ? !conv_w2d_shape_ok(B, H, W, C1, C2, Cout, 9) : !r.reads_weight(copy)) {
         set_error("flowse_op_conv3x3_%s: shape B=%d H=%d W=%d C=%d+%d Cout=%d not covered by the Winograd kernel",
                   two_d ? "w2d" : "f43", B, H, W, C1, C2, Cout);
         return ERR_SHAPE;
@@ -166,15 +177,13 @@ static int op_conv3x3_winograd(const float* in1, int C1, const float* in2, int C
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int C = C1 + C2, HW = H * W;
     float* wf = scratch + flowse_op_group_norm_scratch_floats(B, HW, C);
-    int rc = two_d ? launch_w2d_weights(w, Cout, C, wf, s) : launch_f43_weights(w, Cout, C, wf, s);
-    if (rc != OK) return rc;
     ConvArgs c = conv_args(in1, C1, in2, C2, w, bias, bias2, bias2_stride, res, out, B, H, W, Cout, 9, scale);
-    if (two_d) c.wino2 = wf;
-    else c.wino = wf;
+    int rc = op_make_copy(c, copy, nullptr, wf, s);
+    if (rc != OK) return rc;
     const int ks = two_d ? 1 : r.ksplit;
     if (ks > 1) {                           // same split plan as the model handle uses for this shape
         c.ksplit = ks;
-        c.partial = wf + conv_wino_numel(Cout, C);
+        c.partial = wf + conv_copy(CW_WINO).numel(Cout, 9, C);
     }
     if (gamma) {
         c.gn_silu = silu;
@@ -188,12 +197,12 @@ static int op_conv3x3_winograd(const float* in1, int C1, const float* in2, int C
 
 int64_t flowse_op_conv3x3_f43_scratch_floats(int B, int H, int W, int C, int Cout) {
     const int ks = op_route_f32(B, H, W, C, 0, Cout, 9, op_offer_f43()).ksplit;   // > 1: F(4,3) runs split over K (small images)
-    return flowse_op_group_norm_scratch_floats(B, H * W, C) + conv_wino_numel(Cout, C) +
+    return flowse_op_group_norm_scratch_floats(B, H * W, C) + conv_copy(CW_WINO).numel(Cout, 9, C) +
            (ks > 1 ? (int64_t)ks * B * H * W * Cout : 0);
 }
 
 int64_t flowse_op_conv3x3_w2d_scratch_floats(int B, int H, int W, int C, int Cout) {
-    return flowse_op_group_norm_scratch_floats(B, H * W, C) + conv_w2d_numel(Cout, C);
+    return flowse_op_group_norm_scratch_floats(B, H * W, C) + conv_copy(CW_WINO2).numel(Cout, 9, C);
 }
 
 int flowse_op_conv3x3_w2d(const float* in1, int C1, const float* in2, int C2, const float* gamma, const float* beta,
@@ -257,8 +266,7 @@ static int op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
     void* a1 = cv.take(2 * M * C1);
     void* a2 = C2 ? cv.take(2 * M * C2) : nullptr;
     void* wq = cv.take(2 * nw);
-    const bool frag = (taps == 9 && conv16_uses_pc(B, H, W, C1, C2, Cout, taps)) || conv16_smallm_ok(B, H, W, C1, C2, Cout, taps);
-    void* wfrag = frag ? cv.take(2 * nw) : nullptr;
+    void* wfrag = r.reads_weight(CW_WFRAG) ? cv.take(2 * nw) : nullptr;
     void* r16 = res && !direct ? cv.take(2 * M * Cout) : nullptr;
     void* o16 = direct ? nullptr : cv.take(2 * M * Cout);
     float* part = ks > 1 ? static_cast<float*>(cv.take(4 * (int64_t)ks * M * Cout)) : nullptr;
@@ -266,18 +274,20 @@ static int op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
         set_error("flowse_op_conv2d_16: scratch too small");
         return ERR_ARG;
     }
-    int rc = launch_convert(in1, DT_F32, a1, dt, M * C1, s);
-    if (rc == OK && C2) rc = launch_convert(in2, DT_F32, a2, dt, M * C2, s);
-    if (rc == OK) rc = launch_convert(w, DT_F32, wq, dt, nw, s);
-    if (rc == OK && frag) rc = launch_pc16_weights(wq, Cout, (int)C, wfrag, s, taps);
-    if (rc == OK && r16) rc = launch_convert(res, DT_F32, r16, dt, M * Cout, s);
-    if (rc != OK) return rc;
     ConvArgs c = conv_args(static_cast<const float*>(a1), C1, static_cast<const float*>(a2), C2, w, bias, bias2,
                            bias2 ? bias2_stride : 0, static_cast<const float*>(r16), static_cast<float*>(o16), B, H, W, Cout,
                            taps, scale);
+    int rc = launch_convert(in1, DT_F32, a1, dt, M * C1, s);
+    if (rc == OK && C2) rc = launch_convert(in2, DT_F32, a2, dt, M * C2, s);
+    if (rc == OK && r.reads_weight(CW_WQ)) {
+        rc = launch_convert(w, DT_F32, wq, dt, nw, s);
+        conv_set_weight(c, CW_WQ, wq);
+    }
+    if (rc == OK && wfrag) rc = op_make_copy(c, CW_WFRAG, wq, wfrag, s);
+    if (rc == OK && r16) rc = launch_convert(res, DT_F32, r16, dt, M * Cout, s);
+    if (rc != OK) return rc;
     c.ksplit = ks; c.partial = part;
-    c.wq = wq; c.terms = 1; c.wq_f16 = dt == DT_F16 ? 1 : 0;
-    c.wfrag = wfrag;
+    c.terms = 1; c.wq_f16 = dt == DT_F16 ? 1 : 0;
     c.in_dt = dt; c.out_dt = dt;
     if (gn_mean) {
         c.gn = GnParams{gn_mean, gn_scale, gn_beta};
@@ -343,8 +353,11 @@ int flowse_op_conv_route(int in_dt, int out_dt, int B, int H, int W, int C1, int
         return OK;
     }
     const char* issued = r.issued == 0.5 ? "1/2" : r.issued == 3.0 ? "3" : r.issued == 1.0 ? "1" : "1/3";
-    snprintf(text, cap, "%s ks=%d reduce=%d stats=%d gn=%d issued=%s", conv_kernel_name(r.kernel), r.ksplit, r.reduce ? 1 : 0,
-             r.stats_nblk, r.gn_on_load ? 1 : 0, issued);
+    std::string reads;                                   // "wq+wfrag", "wino", ... in ConvWeight order, wq first; "-": none
+    for (int k : {(int)CW_WQ, (int)CW_WINO, (int)CW_WINO2, (int)CW_WSM, (int)CW_WSM16, (int)CW_WFRAG})
+        if (r.reads_weight(k)) reads += (reads.empty() ? "" : "+") + std::string(k == CW_WQ ? "wq" : conv_copy(k).name);
+    snprintf(text, cap, "%s ks=%d reduce=%d stats=%d gn=%d issued=%s reads=%s", conv_kernel_name(r.kernel), r.ksplit,
+             r.reduce ? 1 : 0, r.stats_nblk, r.gn_on_load ? 1 : 0, issued, reads.empty() ? "-" : reads.c_str());
     return OK;
 }
 

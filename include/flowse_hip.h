@@ -566,11 +566,14 @@ const char* flowse_op_last_conv_route(void);
  * the three: "cin4_mfma", "cin4_stats" (only where statistics are asked for) or "cin4", always whole K, and "flat" for the
  * widths those kernels do not take); (C1, C2): the parts of a concat input; offer_bits: what the caller could hand to the
  * launch, FLOWSE_OFFER_* below.  Writes
- *   "<kernel> ks=<K slices> reduce=<0|1> stats=<blocks per sample> gn=<0|1> issued=<1/3|1/2|1|3>"
+ *   "<kernel> ks=<K slices> reduce=<0|1> stats=<blocks per sample> gn=<0|1> issued=<1/3|1/2|1|3> reads=<copies>"
  * -- kernel: the family flowse_op_last_conv_route reports after that launch ("smallm" / "smallm16b" without the instance);
  * reduce: a separate reduction launch follows; stats: geometry of the fused GroupNorm statistics (0: none); gn: the kernel
- * can normalise its input on load; issued: issued / nominal FLOPs as the profile counts them -- or "error <status>" for a
- * request no kernel takes (flowse_last_error has launch_conv's text).  cap >= 64. */
+ * can normalise its input on load; issued: issued / nominal FLOPs as the profile counts them; reads: the weight copies the
+ * kernel dereferences next to the packed fp32 weights, joined by "+" -- "wq" (the 16-bit weights: the operand itself for a
+ * 16-bit input, whether offered or not), "wino", "wino2", "wsm", "wsm16" (the 16 x 16-tile fragment order, offered with
+ * FLOWSE_OFFER_WSM), "wfrag" -- or "-" for none; always among what was offered -- or "error <status>" for a
+ * request no kernel takes (flowse_last_error has launch_conv's text).  cap >= 64; the longest answer has 70 characters. */
 enum {
     FLOWSE_OFFER_WINO = 1,        /* F(4,3) weights */
     FLOWSE_OFFER_WINO2 = 2,       /* F(4,3) x F(2,3) weights */

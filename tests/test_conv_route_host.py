@@ -10,7 +10,8 @@ a route leaves the file untouched, one that does regenerates it and the diff of 
 
 File format.  One line per shape, storage type and answer: "HxW C1+C2>Cout/taps dt B<batches>" and, per distinct answer, the
 offers that get it, "names: answer".  An answer is the entry's text with the field names dropped, "kernel ks stats gn issued"
-(`reduce` is left out: it is ks > 1, which test_route_properties asserts for every query), or "error <status>".  dt "16"
+(`reduce` is left out: it is ks > 1, which test_route_properties asserts for every query; `reads` too: the kernel decides
+it, test_route_reads holds every query to that mapping), or "error <status>".  dt "16"
 stands for bf16 and fp16 where their answers are equal; "f32>bf16" is an fp32 input stored as bf16 (the convs of the
 4-channel input in the 16-bit modes); batches that give the same answers share a line.  The first
 section is the library as loaded by default; a section "[HOOK=value]" is the same list of queries asked in a fresh process
@@ -162,8 +163,9 @@ def ask(L, args):
 
 
 def short(text):
-    """the entry's line without its field names, and without `reduce`: it is ks > 1 (test_route_properties holds every query to that)"""
-    return " ".join(f.split("=")[-1] for f in text.split() if not f.startswith("reduce="))
+    """the entry's line without its field names, and without `reduce` -- it is ks > 1 (test_route_properties holds every query to
+    that) -- and `reads`: the kernel decides it (test_route_reads)"""
+    return " ".join(f.split("=")[-1] for f in text.split() if not f.startswith(("reduce=", "reads=")))
 
 
 def entries():
@@ -270,12 +272,52 @@ def test_route_properties(answers):
             kernel = text.split()[0]
             assert (ks, f["gn"], f["issued"]) == (1, "0", "1") and not bits & GN, (args, text)
             if not takes:                                  # refused: the flat kernel, whole K, no statistics
-                assert text == "flat ks=1 reduce=0 stats=0 gn=0 issued=1", (args, text)
+                assert text == "flat ks=1 reduce=0 stats=0 gn=0 issued=1 reads=-", (args, text)
             else:                                          # statistics: the matrix-core kernel's, or asked for
                 assert (nblk > 0) == (kernel in ("cin4_mfma", "cin4_stats")) and (kernel != "cin4_stats" or bits & STATS), (args, text)
     assert kernels == {"head4", "head4_16", "smallm", "1x1_stream", "w2d", "f43", "f43_splitk", "halo", "halo_bf16x3",
                        "halo16", "pc16", "smallm16b", "flat", "flat_splitk", "flat16", "flat16_splitk", "cin4", "cin4_stats",
                        "cin4_mfma"}, kernels
+
+
+# the weight pointers a kernel dereferences next to the packed fp32 weights, by kernel name ("smallm": computed from the shape)
+READS = {"f43": {"wino"}, "f43_splitk": {"wino"}, "w2d": {"wino2"}, "1x1_stream": {"wsm"}, "halo_bf16x3": {"wq"},
+         "halo16": {"wq"}, "flat16": {"wq"}, "flat16_splitk": {"wq"}, "pc16": {"wq", "wfrag"}, "smallm16b": {"wq", "wfrag"}}
+NO_READS = ("head4", "head4_16", "halo", "flat", "flat_splitk", "cin4", "cin4_stats", "cin4_mfma")
+
+
+def test_route_reads(answers):
+    """`reads`, the weight copies the chosen kernel dereferences: for every query that has a route it is what the kernel's
+    name says, and nothing the query did not offer.
+
+    One exemption from "offered": the `wq` of a 16-bit input.  There the weights in the storage type are the conv's operand
+    itself -- every 16-bit kernel but head4_16 reads them -- and conv_route has never looked at the WQ bit of such a query (the
+    pinned answers of the "0" offers, which this change leaves untouched, name halo16 / flat16 with nothing offered).  For an
+    fp32 input, where `wq` is an optional copy like the others, it has to be offered."""
+    seen = set()
+    for args, text in answers:
+        dt, out_dt, B, H, W, C1, C2, Cout, taps, bits = args
+        if text.startswith("error"):
+            continue
+        kernel = text.split()[0]
+        f = dict(kv.split("=") for kv in text.split()[1:])
+        names = [] if f["reads"] == "-" else f["reads"].split("+")
+        reads = set(names)
+        assert names == [n for n in ("wq", "wino", "wino2", "wsm", "wsm16", "wfrag") if n in reads], (args, text)   # one spelling per set
+        if kernel == "smallm":                             # the 16 x 16-tile form: <= 256 pixels over the batch, whole 16-pixel blocks
+            want = {"wsm16"} if B * H * W <= 256 and (H * W) % 16 == 0 else {"wsm"}
+        elif kernel in NO_READS:
+            want = set()
+        else:
+            want = READS[kernel]
+        assert reads == want, (args, text)
+        offered = {n for n, bit in (("wino", WINO), ("wino2", WINO2), ("wsm", WSM), ("wsm16", WSM), ("wfrag", WFRAG), ("wq", WQ))
+                   if bits & bit}
+        if dt != F32:
+            offered.add("wq")
+        assert reads <= offered, (args, text, sorted(offered))
+        seen |= reads
+    assert seen == {"wq", "wino", "wino2", "wsm", "wsm16", "wfrag"}, seen
 
 
 def test_route_entry_is_declared_and_checks_its_arguments():
