@@ -23,7 +23,6 @@ struct SkPartial {
     size_t part_off = 0;
     int ks = 0;
     int64_t bias = -1;
-    bool valid = false;
 };
 // The 1x1 shortcut Conv_2(x) of a ResnetBlock folded into Conv_1's launch (ConvArgs::sc1, conv3x3_pc16_kernel only)
 struct ScFold {
@@ -31,17 +30,16 @@ struct ScFold {
     const Tn* s2 = nullptr;             // second part of a concat input, or null
     int64_t w = -1, bias = -1;          // packed offsets of Conv_2's weight / bias
 };
-// Request to fuse the GroupNorm that consumes a split-K conv's output into its reduction launch
-// (launch_splitk_reduce_gn).  apply: the conv returns act(GroupNorm(out)); else it returns out and fills `g`.
+// The GroupNorm that consumes a split-K conv's output, finished in its reduction launch (launch_splitk_reduce_gn).
+// apply: the conv returns act(GroupNorm(out)); else it returns out and leaves per-channel mean / scale in `g`.
 struct GnFuse {
     int64_t w_gamma = -1, w_beta = -1;
     bool silu = true, apply = false;
     GnBuf g;
-    bool done = false;
 };
 
 // One conv of the plan (Builder::conv).  conv_req() fills what every conv has; a call site names what else differs from
-// the defaults.
+// the defaults.  Everything here is a command: a conv whose route (Builder::route) cannot do what is asked fails the plan.
 struct ConvReq {
     std::string label;
     const Tn* a = nullptr;              // input
@@ -56,9 +54,9 @@ struct ConvReq {
     bool gin_silu = false;
     int64_t wq_off = -1;                // offset of the reduced-precision weight copy
     int out_dt = -1;                    // < 0: Builder::alloc's choice
-    SkPartial* defer = nullptr;         // leave the split-K slices to another conv's reduction, if this conv runs split
+    SkPartial* defer = nullptr;         // leave the split-K slices to another conv's reduction (filled in: where they are)
     const SkPartial* extra = nullptr;   // slices of a deferred conv to sum in this conv's reduction
-    GnFuse* gnf = nullptr;              // finish the consuming GroupNorm in the reduction, if this conv runs split
+    GnFuse* gnf = nullptr;              // finish the consuming GroupNorm in the reduction (filled in: g, unless applied)
     const ScFold* fold = nullptr;       // 1x1 shortcut as extra K steps of this launch
     bool no_stats = false;              // nobody normalises the output
     int64_t bias_sc = -1;               // a second per-channel bias from the weight blob
@@ -83,11 +81,21 @@ struct Builder {
     int B;
     Builder(flowse_model* m_, Plan* plan_, int B_) : m(m_), plan(plan_), B(B_) {}
 
-    // dt < 0: the model's activation type for wide tensors, fp32 for the 4-channel ones (input pack, pyramids)
-    Tn alloc(int H, int W, int C, int dt = -1) {
+    // The storage type of a tensor nobody names one for: the model's activation type for wide tensors, fp32 for the
+    // 4-channel ones (input pack, pyramids)
+    int act_type(int C) const { return C > 4 ? m->wt->act_dt : DT_F32; }
+    // A tensor by shape and type only (dt < 0: act_type), for asking how a conv on it will run before it exists (route()).
+    // It has no storage: conv() fails the plan when handed one.
+    static constexpr size_t NO_STORAGE = ~(size_t)0;
+    Tn shape_only(int H, int W, int C, int dt = -1) const {
         Tn t;
         t.B = B; t.H = H; t.W = W; t.C = C;
-        t.dt = dt >= 0 ? dt : (C > 4 ? m->wt->act_dt : DT_F32);
+        t.dt = dt >= 0 ? dt : act_type(C);
+        t.off = NO_STORAGE;
+        return t;
+    }
+    Tn alloc(int H, int W, int C, int dt = -1) {
+        Tn t = shape_only(H, W, C, dt);
         t.off = arena.alloc(t.bytes());
         return t;
     }
@@ -234,14 +242,25 @@ struct Builder {
         of.slab = true;                                  // the arena has room for one
         return of;
     }
-    // The route Builder::conv will get for a conv of this shape on weight w: resblock plans its fusions from it -- split over K
-    // (.ksplit > 1), normalising on load (.gn_on_load), on the producer / consumer kernel (.kernel == CK_PC16).  (C1, C2): the
-    // parts of a concat input.
-    ConvRoute predict(int dt, int H, int W, int C1, int C2, int Cout, int taps, int64_t w) const {
-        ConvOffer of = offer(dt, w, taps, -1);           // (the bf16 planes change neither of the three)
-        of.stats = Cout >= 16;
-        return conv_route(ConvShape{dt, Cout > 4 ? m->wt->act_dt : DT_F32, B, H, W, C1, C2, Cout, taps}, of);
+    // The routing question of a request: its shape, and as the offer what the weight set holds for its weight.  A function
+    // of the request alone -- conv() asks it of the request it emits, resblock of the requests it is about to submit, on
+    // shape_only() tensors where they do not exist yet.
+    struct ConvQuery { ConvShape shape; ConvOffer offer; };
+    ConvQuery query(const ConvReq& q) const {
+        const Tn& a = *q.a;
+        const int odt = q.out_is_res ? q.res->dt : q.out_dt >= 0 ? q.out_dt : act_type(q.Cout);   // = alloc()'s choice in conv()
+        ConvOffer of = offer(a.dt, q.w, q.taps, q.wq_off);
+        of.gn = q.gin != nullptr;
+        of.bias2 = q.dense_row0 >= 0 || q.bias_sc >= 0;
+        // statistics of the output where somebody normalises it.  In place on `res`, only Combine's (conv1x1 of the 4-channel
+        // pyramid, any storage type of `res`) are used: they are those of the updated tensor
+        const bool combine = q.out_is_res && q.taps == 1 && a.C == 4 && !q.b2 && a.dt == DT_F32;
+        of.stats = q.Cout >= 16 && !q.no_stats && (!q.out_is_res || combine);
+        of.fold = q.fold != nullptr;
+        return {ConvShape{a.dt, odt, B, a.H, a.W, a.C, q.b2 ? q.b2->C : 0, q.Cout, q.taps}, of};
     }
+    // ... and its answer: which kernel runs, over how many K slices (.ksplit), whether it normalises on load (.gn_on_load)
+    ConvRoute route(const ConvReq& q) const { const ConvQuery c = query(q); return conv_route(c.shape, c.offer); }
     // conv: out (new tensor unless `out_is_res`), res optional
     Tn conv(const ConvReq& q) {
         flowse_model* M = m;
@@ -252,47 +271,44 @@ struct Builder {
         const int64_t w = q.w, bias = q.bias, wq_off = q.wq_off, bias_sc = q.bias_sc;
         const int dense_row0 = q.dense_row0, Cout = q.Cout, taps = q.taps, out_dt = q.out_dt;
         const float scale = q.scale;
-        const bool out_is_res = q.out_is_res, gin_silu = q.gin_silu, no_stats = q.no_stats;
+        const bool out_is_res = q.out_is_res, gin_silu = q.gin_silu;
         const GnBuf* gin = q.gin;
         const SkPartial* extra = q.extra;
         const ScFold* fold = q.fold;
-        SkPartial* defer = q.defer;                      // requests: dropped below for a conv that cannot honour them
+        SkPartial* defer = q.defer;
         GnFuse* gnf = q.gnf;
         const int C1 = a.C, C2 = b2 ? b2->C : 0, H = a.H, Wd = a.W, Bn = B;
         if (bias_sc >= 0 && dense_row0 >= 0) {           // both ride on ConvArgs::bias2
             set_error("internal: a second per-channel bias and a Dense row on one conv (%s)", label.c_str());
             failed = true;
         }
+        for (const Tn* t : {q.a, b2, res, fold ? fold->s1 : nullptr, fold ? fold->s2 : nullptr})
+            if (t && t->off == NO_STORAGE) {
+                set_error("internal: %s submitted on a tensor that was never allocated", label.c_str());
+                failed = true;
+            }
         const int idt = a.dt;
-        const int want_odt = out_is_res ? res->dt : out_dt >= 0 ? out_dt : (Cout > 4 ? M->wt->act_dt : DT_F32);   // = alloc()'s choice below
         const bool in16 = idt != DT_F32;                 // 16-bit storage: the 16-bit matrix-core kernels take it
         const bool has_gin = gin != nullptr, has_fold = fold != nullptr;
-        // The one routing question of this conv, asked once: the offer is what the weight set holds for this weight.  The
-        // answer says which kernel runs, over how many K slices and where its statistics go; the launch closure keeps it.
-        ConvOffer of = offer(idt, w, taps, wq_off);
-        of.gn = has_gin;
-        of.bias2 = dense_row0 >= 0 || bias_sc >= 0;
-        // statistics of the output where somebody normalises it.  In place on `res`, only Combine's (conv1x1 of the 4-channel
-        // pyramid, any storage type of `res`) are used: they are those of the updated tensor
-        const bool combine = out_is_res && taps == 1 && C1 == 4 && !b2 && idt == DT_F32;
-        of.stats = Cout >= 16 && !no_stats && (!out_is_res || combine);
-        of.fold = has_fold;
-        const ConvRoute rt = conv_route(ConvShape{idt, want_odt, Bn, H, Wd, C1, C2, Cout, taps}, of);
+        // The one routing question of this conv, asked once.  The answer says which kernel runs, over how many K slices and
+        // where its statistics go; the launch closure keeps it.
+        const ConvQuery cq = query(q);
+        const ConvOffer& of = cq.offer;
+        const ConvRoute rt = conv_route(cq.shape, of);
         if (rt.err != OK) {
             set_error("internal: no kernel takes %s@%dx%d (%s)", label.c_str(), H, Wd, rt.err_text);
             failed = true;
         }
         const int ks = rt.ksplit;
-        // a deferred reduction leaves no output tensor: decide before anything is allocated
-        if (defer && !(ks > 1 && !res && dense_row0 < 0)) defer = nullptr;
-        if ((extra || gnf) && !(ks > 1)) {
-            if (extra && extra->valid) {
-                set_error("internal: merged reduction requested for an unsplit conv (%s)", label.c_str());
-                failed = true;
-            }
-            gnf = nullptr;
+        // What the request says about the reduction launch holds only for a conv that has one (and a deferred one leaves no
+        // output tensor: checked before anything is allocated)
+        if (((defer || extra || gnf) && !(ks > 1)) || (defer && (res || dense_row0 >= 0)) ||
+            (gnf && (res || !conv_reduce_gn_ok(Bn, H * Wd, Cout)))) {
+            set_error("internal: %s@%dx%d runs over %d K slice(s) and cannot take the reduction planned for it", label.c_str(),
+                      H, Wd, ks);
+            failed = true;
+            defer = nullptr; extra = nullptr; gnf = nullptr;
         }
-        if (gnf && (res || !conv_reduce_gn_ok(Bn, H * Wd, Cout))) gnf = nullptr;
         Tn o;
         if (!defer) o = out_is_res ? *res : alloc(a.H, a.W, Cout, out_dt);
         const size_t a_off = a.off, b_off = b2 ? b2->off : 0, o_off = o.off, r_off = res ? res->off : 0;
@@ -323,14 +339,15 @@ struct Builder {
         const int terms = M->wt->precision == 1 ? 3 : 1;
         const size_t part_off = ks > 1 ? arena.alloc((size_t)ks * Bn * H * Wd * Cout * sizeof(float)) : 0;
         const size_t table_off = M_table_off;     // by value: the Builder dies before the plan runs
-        const bool has_extra = extra != nullptr && extra->valid;
+        const bool has_extra = extra != nullptr;
         const SkPartial xp = has_extra ? *extra : SkPartial();
         const size_t f1_off = has_fold ? fold->s1->off : 0, f2_off = has_fold && fold->s2 ? fold->s2->off : 0;
         const int FC1 = has_fold ? fold->s1->C : 0, FC2 = has_fold && fold->s2 ? fold->s2->C : 0;
         const int64_t fold_w = has_fold ? fold->w : -1, fold_b = has_fold ? fold->bias : -1;
         const void* wfrag_sc = has_fold ? M->wt->copy_ptr(CW_WFRAG, fold_w) : nullptr;
-        if (has_fold && (res || extra || ks != 1 || !in16 || taps != 9 || fold->s1->H != H || fold->s1->W != Wd ||
-                         fold->s1->dt != idt || !M->wt->has_copy(CW_WFRAG, w) || !wfrag_sc)) {
+        // (that the conv itself is a whole-K launch of the producer / consumer kernel is the route's answer to of.fold: rt.err
+        // above.  Here: what the route is not asked -- the other riders on the launch, the fold's source, its weight copy)
+        if (has_fold && (res || extra || fold->s1->H != H || fold->s1->W != Wd || fold->s1->dt != idt || !wfrag_sc)) {
             set_error("internal: shortcut fold requested for a conv that cannot take it (%s)", label.c_str());
             failed = true;
         }
@@ -405,10 +422,9 @@ struct Builder {
             defer->part_off = part_off;
             defer->ks = ks;
             defer->bias = bias;
-            defer->valid = true;
             return Tn();
         }
-        if (ks > 1 && gnf) {
+        if (gnf) {
             const int64_t wg = gnf->w_gamma, wb = gnf->w_beta;
             const bool gsilu = gnf->silu, gapply = gnf->apply;
             GnBuf g;
@@ -423,7 +439,6 @@ struct Builder {
                                                gapply ? nullptr : M->A(gm), gapply ? nullptr : M->A(gs), s);
             }, 8.0 * Bn * H * Wd * Cout, part_bytes + out_bytes);
             gnf->g = g;
-            gnf->done = true;
         } else if (ks > 1)
             op("splitk_reduce" + at(H, Wd), [=](hipStream_t s) { return launch_splitk_reduce(make_args(), s); }, 0.0,
                part_bytes * (has_extra ? 1.0 + (double)xp.ks / ks : 1.0) + out_bytes);
@@ -457,67 +472,27 @@ struct Builder {
         return o;
     }
 
-    // A deferred split-K conv whose consumer turned out not to run a two-pass reduction after all: its own reduction launch
-    Tn reduce_deferred(SkPartial& sp, int H, int Wd, int Cout) {
-        flowse_model* M = m;
-        Tn o = alloc(H, Wd, Cout);
-        const size_t part = sp.part_off, o_off = o.off;
-        const int ks = sp.ks, Bn = B, odt = o.dt;
-        const int64_t bias = sp.bias;
-        op("splitk_reduce" + at(H, Wd), [=](hipStream_t s) {
-            ConvArgs c;
-            c.B = Bn; c.H = H; c.W = Wd; c.Cout = Cout; c.C1 = Cout; c.taps = 1;
-            c.scale = 1.f;
-            c.ksplit = ks;
-            c.partial = M->A(part);
-            c.bias = bias >= 0 ? M->W(bias) : nullptr;
-            c.out = M->A(o_off);
-            c.in_dt = odt;
-            c.out_dt = odt;
-            return launch_splitk_reduce(c, s);
-        }, 0.0, 4.0 * ks * (double)Bn * H * Wd * Cout + (double)dt_size(odt) * Bn * H * Wd * Cout);
-        arena.release(sp.part_off);
-        sp.valid = false;
-        return o;
-    }
+    // What a ResnetBlock fuses.  Small images run their convs split over K with a separate reduction launch, and two of
+    // those launches disappear: Conv_0's reduction also finishes GroupNorm_1 (its group structure is known), and the
+    // shortcut Conv_2(x) leaves its slices to Conv_1's reduction, which sums both sets.  Large 16-bit images run the
+    // shortcut as extra K steps of Conv_1's launch; large fp32 up blocks run it before the upsampling.
+    struct BlockPlan {
+        // Conv_2(x): no such conv (identity skip) | a launch of its own | ... at the low resolution, upsampled afterwards |
+        // its K slices summed by Conv_1's reduction (SkPartial) | extra K steps of Conv_1's launch (ScFold)
+        enum { SC_NONE, SC_OWN, SC_LOW, SC_MERGED, SC_FOLDED } sc = SC_NONE;
+        bool gn0_on_load = false;       // Conv_0 normalises x on load; else act(GroupNorm_0(x)) is materialised
+        // GroupNorm_1: Conv_0's reduction returns act(GroupNorm_1(.)) | ... returns the pre-norm tensor and per-channel mean /
+        // scale for a Conv_1 that normalises on load (GnFuse) | gn() and Conv_1 on load | materialised
+        enum { GN1_REDUCE_APPLY, GN1_REDUCE_STATS, GN1_ON_LOAD, GN1_MATERIAL } gn1 = GN1_MATERIAL;
+    };
 
-    // ResnetBlockBigGANpp.forward, layerspp.py:245-274
+    // ResnetBlockBigGANpp.forward, layerspp.py:245-274: decide what is fused, then emit
     Tn resblock(const Module& mod, const Tn& x1, const Tn* x2) {
         const float rs2 = 0.70710678118654752440f;
-        Tn h1, xs;
-        // Conv_0 / Conv_1 on (predicted or existing) tensors: does Conv(act(GroupNorm(t))) run as one kernel?
-        auto conv0_route = [&](const Tn& t, int c2) { return predict(t.dt, t.H, t.W, t.C, c2, mod.out_ch, 9, mod.w_c0); };
-        auto conv1_route = [&](int dt, int H, int W) { return predict(dt, H, W, mod.out_ch, 0, mod.out_ch, 9, mod.w_c1); };
+        const bool resample = mod.up || mod.down;
         // output geometry of the block (Conv_0 already runs at the resampled size)
         const int Ho = mod.up ? 2 * x1.H : mod.down ? x1.H / 2 : x1.H, Wo = mod.up ? 2 * x1.W : mod.down ? x1.W / 2 : x1.W;
-        // Small images run split over K with a separate reduction launch.  Two of those launches disappear here:
-        //  * Conv_0's reduction also finishes GroupNorm_1 (its group structure is known): it returns act(GN_1(.)) where
-        //    the next conv wants a materialised input, or the pre-norm tensor plus per-channel mean / scale where the
-        //    next conv normalises on load (GnFuse);
-        //  * the shortcut Conv_2(x) leaves its slices to Conv_1's reduction, which sums both sets (SkPartial).
-        GnFuse gf;
-        gf.w_gamma = mod.w_gn1_g;
-        gf.w_beta = mod.w_gn1_b;
-        gf.silu = true;
-        const ConvRoute c1_plan = conv1_route(m->wt->act_dt, Ho, Wo);       // Conv_1 as predicted: its input does not exist yet
-        gf.apply = !c1_plan.gn_on_load;
-        SkPartial sp;
-        const bool merge_sc = mod.shortcut && conv1_route(x1.dt, Ho, Wo).ksplit > 1 &&
-                              predict(x1.dt, Ho, Wo, mod.in_ch, 0, mod.out_ch, 1, mod.w_c2).ksplit > 1;
-        // 16-bit storage, Conv_1 on the producer / consumer kernel: the shortcut Conv_2(x) runs as extra K steps of Conv_1's
-        // launch (ConvArgs::sc1) -- no launch, no round trip of its output through HBM, one read of x less
-        const int xc2 = (!mod.up && !mod.down && x2) ? x2->C : 0;
-        const bool fold_sc = mod.shortcut && m->wt->act_dt != DT_F32 && !merge_sc && !getenv("FLOWSE_NO_SCFOLD") &&
-                             m->wt->has_copy(CW_WFRAG, mod.w_c2) && c1_plan.kernel == CK_PC16 && (x1.C % 32) == 0 && (xc2 % 32) == 0 &&
-                             x1.C + xc2 >= 96 && x1.dt == m->wt->act_dt;
-        // fp32 up blocks whose shortcut is a launch of its own: Conv_2 has no spatial extent and upsample_2d filters every
-        // channel alike, so W . up(x) = up(W . x) -- the 1x1 runs BEFORE the upsampling, on a quarter of the pixels, and the
-        // upsampled raw x never exists.  Only the bias does not commute (up(const) is not constant at the image border):
-        // Conv_1's epilogue adds it, once per output element.  Up to 2048 low-resolution pixels over the batch the reference's order
-        // stays (small-image kernels, shortcuts merged into split-K reductions: not measured in the other order).
-        const bool sc_low = mod.up && mod.shortcut && !merge_sc && !fold_sc && m->wt->act_dt == DT_F32 && x1.dt == DT_F32 &&
-                            (int64_t)B * x1.H * x1.W > 2048 && !getenv("FLOWSE_NO_SC_LOW");
-        // What every request for the shortcut Conv_2 / for Conv_0 has in common; the call sites name the rest
+        // What every request for the shortcut Conv_2 / for Conv_0 / for Conv_1 has in common; the call sites name the rest
         auto shortcut = [&](const Tn& s) {
             ConvReq r = conv_req("conv2_1x1", s, mod.w_c2, mod.out_ch, 1);
             r.bias = mod.w_c2_b;
@@ -527,33 +502,90 @@ struct Builder {
         auto conv0 = [&](const char* label, const Tn& s) {
             ConvReq r = conv_req(label, s, mod.w_c0, mod.out_ch, 9);
             r.dense_row0 = mod.dense_row0;               // Conv_0.bias rides in the Dense_0 table
-            r.gnf = &gf;
             return r;
         };
-        Tn xr;
-        if (!mod.up && !mod.down) {
-            if (mod.shortcut && !fold_sc) {
+        auto conv1 = [&](const char* label, const Tn& s) {
+            ConvReq r = conv_req(label, s, mod.w_c1, mod.out_ch, 9);
+            r.bias = mod.w_c1_b;
+            r.scale = rs2;
+            return r;
+        };
+
+        // ---- decide, before anything is allocated or emitted.  q0 / q1 are the requests for Conv_0 / Conv_1 that are
+        // submitted below, here on tensors named by shape and type where these do not exist yet.  A fusion that changes the
+        // routing question (GroupNorm on load, the fold) is decided from the route without it and then added to the request:
+        // conv()'s own query confirms it, and fails the plan if a route cannot do what this record says.
+        const int xc2 = (!resample && x2) ? x2->C : 0;
+        const Tn xr_s = shape_only(Ho, Wo, x1.C, x1.dt);             // fir()'s outputs: x resampled, raw and as act(GN_0(x))
+        const Tn h0_s = shape_only(x1.H, x1.W, x1.C + xc2, x1.dt);   // gn_norm()'s output
+        const Tn h1_s = shape_only(Ho, Wo, mod.out_ch);              // Conv_0's output; GroupNorm_1 keeps shape and type
+        BlockPlan bp;
+        ConvReq q0 = resample ? conv0("conv0_3x3", xr_s) : conv0("conv0_3x3_gn", x1);
+        q0.wq_off = mod.wq_c0;
+        if (!resample) {
+            q0.b2 = x2;
+            bp.gn0_on_load = route(q0).gn_on_load;
+            if (!bp.gn0_on_load) q0 = conv0("conv0_3x3", h0_s);
+        }
+        const bool reduce_gn1 = route(q0).ksplit > 1 && conv_reduce_gn_ok(B, Ho * Wo, mod.out_ch);
+        ConvReq q1 = conv1("conv1_3x3_gn", h1_s);
+        q1.wq_off = mod.wq_c1;
+        const ConvRoute c1 = route(q1);
+        if (!c1.gn_on_load) q1 = conv1("conv1_3x3", h1_s);
+        bp.gn1 = reduce_gn1 ? (c1.gn_on_load ? BlockPlan::GN1_REDUCE_STATS : BlockPlan::GN1_REDUCE_APPLY)
+                            : (c1.gn_on_load ? BlockPlan::GN1_ON_LOAD : BlockPlan::GN1_MATERIAL);
+        if (mod.shortcut) {
+            ConvReq qs = shortcut(resample ? xr_s : x1);
+            if (!resample) qs.b2 = x2;
+            const bool merge = c1.ksplit > 1 && route(qs).ksplit > 1;
+            // 16-bit storage, Conv_1 on the producer / consumer kernel: no launch, no round trip of Conv_2's output through
+            // HBM, one read of x less.  (Next to the route: what the kernel asks of the fold's source and weight.)
+            const bool fold = !merge && m->wt->act_dt != DT_F32 && !getenv("FLOWSE_NO_SCFOLD") && c1.kernel == CK_PC16 &&
+                              m->wt->has_copy(CW_WFRAG, mod.w_c2) && (x1.C % 32) == 0 && (xc2 % 32) == 0 && x1.C + xc2 >= 96 &&
+                              x1.dt == m->wt->act_dt;
+            // fp32 up blocks whose shortcut is a launch of its own: Conv_2 has no spatial extent and upsample_2d filters every
+            // channel alike, so W . up(x) = up(W . x) -- the 1x1 runs BEFORE the upsampling, on a quarter of the pixels, and the
+            // upsampled raw x never exists.  Only the bias does not commute (up(const) is not constant at the image border):
+            // Conv_1's epilogue adds it, once per output element.  Up to 2048 low-resolution pixels over the batch the
+            // reference's order stays (small-image kernels, shortcuts merged into split-K reductions: not measured in the
+            // other order).
+            const bool low = mod.up && !merge && !fold && m->wt->act_dt == DT_F32 && x1.dt == DT_F32 &&
+                             (int64_t)B * x1.H * x1.W > 2048 && !getenv("FLOWSE_NO_SC_LOW");
+            bp.sc = merge ? BlockPlan::SC_MERGED : fold ? BlockPlan::SC_FOLDED : low ? BlockPlan::SC_LOW : BlockPlan::SC_OWN;
+        }
+        const bool sc_launch = bp.sc == BlockPlan::SC_OWN || bp.sc == BlockPlan::SC_MERGED;
+        const bool merged = bp.sc == BlockPlan::SC_MERGED, folded = bp.sc == BlockPlan::SC_FOLDED;
+
+        // ---- emit
+        GnFuse gf;
+        gf.w_gamma = mod.w_gn1_g;
+        gf.w_beta = mod.w_gn1_b;
+        gf.silu = true;
+        gf.apply = bp.gn1 == BlockPlan::GN1_REDUCE_APPLY;
+        if (reduce_gn1) q0.gnf = &gf;
+        SkPartial sp;
+        Tn h1, xs, xr;
+        if (!resample) {
+            if (sc_launch) {
                 ConvReq r = shortcut(x1);
                 r.b2 = x2;
-                if (merge_sc) r.defer = &sp;
+                if (merged) r.defer = &sp;
                 xs = conv(r);
             }
-            if (conv0_route(x1, x2 ? x2->C : 0).gn_on_load) {
+            if (bp.gn0_on_load) {
                 // Conv_0(act(GroupNorm_0(x))) in one kernel: the normalised tensor never reaches HBM
                 GnBuf g0 = gn(x1, x2, mod.w_gn0_g, mod.w_gn0_b);
-                ConvReq r = conv0("conv0_3x3_gn", x1);
-                r.b2 = x2;
-                r.gin = &g0;
-                r.gin_silu = true;
-                r.wq_off = mod.wq_c0;
-                h1 = conv(r);
+                q0.gin = &g0;
+                q0.gin_silu = true;
+                h1 = conv(q0);
                 gn_release(g0);
             } else {
                 Tn h0 = gn_norm(x1, x2, mod.w_gn0_g, mod.w_gn0_b, true);
-                h1 = conv(conv0("conv0_3x3", h0));
+                q0.a = &h0;
+                h1 = conv(q0);
                 release(h0);
             }
-        } else if (sc_low) {
+        } else if (bp.sc == BlockPlan::SC_LOW) {
             ConvReq r = shortcut(x1);
             r.bias = -1;                                 // Conv_1's epilogue adds it (bias_sc below)
             Tn xl = conv(r);
@@ -562,92 +594,57 @@ struct Builder {
             GnBuf g0 = gn(x1, x2, mod.w_gn0_g, mod.w_gn0_b);
             Tn hr = fir(x1, true, &g0, true, nullptr);
             gn_release(g0);
-            ConvReq r0 = conv0("conv0_3x3", hr);
-            r0.wq_off = mod.wq_c0;
-            h1 = conv(r0);
+            q0.a = &hr;
+            h1 = conv(q0);
             release(hr);
         } else {
             GnBuf g0 = gn(x1, x2, mod.w_gn0_g, mod.w_gn0_b);
             Tn hr = fir(x1, mod.up, &g0, true, nullptr, false, &xr);      // act(GN(x)) and x resampled in one pass
             gn_release(g0);
-            // the shortcut Conv_2(x) (layerspp.py:268-270)
-            if (!fold_sc) {
+            if (sc_launch) {                             // the shortcut Conv_2(x) (layerspp.py:268-270)
                 ConvReq r = shortcut(xr);
-                if (merge_sc) r.defer = &sp;
+                if (merged) r.defer = &sp;
                 xs = conv(r);
             }
-            ConvReq r0 = conv0("conv0_3x3", hr);
-            r0.wq_off = mod.wq_c0;
-            h1 = conv(r0);
+            q0.a = &hr;
+            h1 = conv(q0);
             release(hr);
-            if (!fold_sc) release(xr);
+            if (!folded) release(xr);
         }
-        Tn out;
-        // The two fusions above were requested from PREDICTED shapes / types; Conv_1 is decided from the tensors that exist:
-        //  * the shortcut's slices can only ride on Conv_1's reduction if Conv_1 itself runs split -- else they get their
-        //    own reduction launch now;
-        //  * per-channel mean / scale from Conv_0's reduction are only of use to a Conv_1 that normalises on load -- else
-        //    they are released and GroupNorm_1 is materialised below.
-        const ConvRoute c1 = predict(h1.dt, h1.H, h1.W, h1.C, 0, mod.out_ch, 9, mod.w_c1);
-        if (sp.valid && !(c1.ksplit > 1)) xs = reduce_deferred(sp, h1.H, h1.W, mod.out_ch);
-        if (gf.done && !gf.apply && !c1.gn_on_load) {
-            gn_release(gf.g);
-            gf.done = false;
-        }
-        const Tn* resid = (sp.valid || fold_sc) ? nullptr : (xs.valid() ? &xs : &x1);
-        const SkPartial* extra = sp.valid ? &sp : nullptr;
         ScFold fo;
-        if (fold_sc) {
-            fo.s1 = (mod.up || mod.down) ? &xr : &x1;
-            fo.s2 = (mod.up || mod.down) ? nullptr : x2;
+        if (folded) {
+            fo.s1 = resample ? &xr : &x1;
+            fo.s2 = resample ? nullptr : x2;
             fo.w = mod.w_c2;
             fo.bias = mod.w_c2_b;
+            q1.label = "conv1_3x3_gn_sc";
+            q1.fold = &fo;
         }
-        const ScFold* fold = fold_sc ? &fo : nullptr;
-        const int64_t bias_sc = sc_low ? mod.w_c2_b : -1;   // Conv_2's bias, left out of the low-resolution 1x1
-        if (fold && ((gf.done && gf.apply) || c1.kernel != CK_PC16 ||
-                     getenv("FLOWSE_SCFOLD_LATE"))) {          // (the variable: test hook that forces this branch)
-            // The fold was planned from the PREDICTED tensor and the shortcut launch skipped; the Conv_1 that exists does not
-            // take it: the same conv_route answered both times, so only a tensor type or shape that differs from the predicted
-            // one gets here (or Conv_0's reduction that already applied GroupNorm_1).  The shortcut runs now, as its own
-            // launch, and rides as Conv_1's residual: a little slower, never an unusable model.
-            ConvReq r = shortcut(*fo.s1);
-            r.b2 = fo.s2;
-            xs = conv(r);
-            if (mod.up || mod.down) release(xr);
-            resid = &xs;
-            fold = nullptr;
-        }
-        auto conv1 = [&](const char* label, const Tn& s) {   // what every request for Conv_1 has in common
-            ConvReq r = conv_req(label, s, mod.w_c1, mod.out_ch, 9);
-            r.bias = mod.w_c1_b;
-            r.res = resid;
-            r.scale = rs2;
-            r.extra = extra;
-            r.bias_sc = bias_sc;
-            return r;
-        };
-        if (gf.done && gf.apply) {                       // h1 already is act(GroupNorm_1(Conv_0(.)))
-            out = conv(conv1("conv1_3x3", h1));
+        q1.res = (merged || folded) ? nullptr : (xs.valid() ? &xs : &x1);
+        q1.extra = merged ? &sp : nullptr;
+        q1.bias_sc = bp.sc == BlockPlan::SC_LOW ? mod.w_c2_b : -1;   // Conv_2's bias, left out of the low-resolution 1x1
+        Tn out;
+        if (bp.gn1 == BlockPlan::GN1_REDUCE_APPLY) {     // h1 already is act(GroupNorm_1(Conv_0(.)))
+            q1.a = &h1;
+            out = conv(q1);
             release(h1);
-        } else if (c1.gn_on_load) {
-            GnBuf g1 = gf.done ? gf.g : gn(h1, nullptr, mod.w_gn1_g, mod.w_gn1_b);
-            ConvReq r = conv1(fold ? "conv1_3x3_gn_sc" : "conv1_3x3_gn", h1);
-            r.gin = &g1;
-            r.gin_silu = true;
-            r.wq_off = mod.wq_c1;
-            r.fold = fold;
-            out = conv(r);
+        } else if (bp.gn1 != BlockPlan::GN1_MATERIAL) {
+            GnBuf g1 = bp.gn1 == BlockPlan::GN1_REDUCE_STATS ? gf.g : gn(h1, nullptr, mod.w_gn1_g, mod.w_gn1_b);
+            q1.a = &h1;
+            q1.gin = &g1;
+            q1.gin_silu = true;
+            out = conv(q1);
             gn_release(g1);
             release(h1);
-            if (fold && (mod.up || mod.down)) release(xr);
+            if (folded && resample) release(xr);
         } else {
             Tn h2 = gn_norm(h1, nullptr, mod.w_gn1_g, mod.w_gn1_b, true);
             release(h1);
-            out = conv(conv1("conv1_3x3", h2));
+            q1.a = &h2;
+            out = conv(q1);
             release(h2);
         }
-        if (sp.valid) arena.release(sp.part_off);
+        if (merged) arena.release(sp.part_off);
         release(xs);
         return out;
     }
@@ -798,14 +795,14 @@ int build_plan(flowse_model* m, Plan* plan, int B, int F, int T) {
         const Module& pcv = next();
         // 16-bit h: the dedicated 4-channel head kernel reads it directly; small images materialise act(GN(h)) in fp32
         // and run the fp32 kernels
-        const bool pfuse = bd.predict(h.dt, h.H, h.W, h.C, 0, 4, 9, pcv.w_a).gn_on_load;
+        ConvReq rp = conv_req("pyramid_conv", h, pcv.w_a, 4, 9);
+        rp.bias = pcv.w_a_b;
+        const bool pfuse = bd.route(rp).gn_on_load;      // (asked without the GroupNorm; the request with it confirms)
         GnBuf g;
         if (pfuse) g = bd.gn(h, nullptr, gnm.w_a, gnm.w_a_b);
         Tn ph = pfuse ? h : bd.gn_norm(h, nullptr, gnm.w_a, gnm.w_a_b, true, DT_F32);
-        const GnBuf* pg = pfuse ? &g : nullptr;
-        ConvReq rp = conv_req("pyramid_conv", ph, pcv.w_a, 4, 9);
-        rp.bias = pcv.w_a_b;
-        rp.gin = pg;
+        rp.a = &ph;
+        rp.gin = pfuse ? &g : nullptr;
         rp.gin_silu = true;
         if (!pyr.valid()) {
             pyr = bd.conv(rp);

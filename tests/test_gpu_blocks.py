@@ -131,10 +131,10 @@ def test_resblock_16bit_storage_vs_oracle(tag, cin, cout, shp, kw, split, mode, 
     assert got.shape == ref.shape and err < bound
 
 
-def test_resblock_16bit_shortcut_fold_safety_net():
-    """The 1x1 shortcut is folded into Conv_1's launch from PREDICTED shapes (the shortcut launch is skipped before Conv_0
-    exists); if the Conv_1 that is finally planned does not take the fold, the shortcut must run late as its own launch and
-    ride as the residual (FLOWSE_SCFOLD_LATE=1 forces that branch): same result as the folded plan, within the mode's ceiling."""
+def test_resblock_16bit_shortcut_folded_vs_own_launch():
+    """The 1x1 shortcut of a large 16-bit block runs as extra K steps of Conv_1's launch; under FLOWSE_NO_SCFOLD=1 (read when
+    the plan is built) it is a launch of its own whose output rides as Conv_1's residual: same result as the folded plan,
+    within the mode's ceiling."""
     import os
     import _gpu as G
     from oracle import ncsnpp_oracle as O
@@ -145,17 +145,17 @@ def test_resblock_16bit_shortcut_fold_safety_net():
     temb = torch.from_numpy(synth.normal(7, 12, (shp[0], 512)))
     ref = O.resblock(O._W({f"all_modules.0.{k}": v for k, v in wl.items()}), 0, x, temb)
     outs = {}
-    for late in (False, True):
-        if late:
-            os.environ["FLOWSE_SCFOLD_LATE"] = "1"
+    for own in (False, True):
+        if own:
+            os.environ["FLOWSE_NO_SCFOLD"] = "1"
         try:
             blk = G.Block("resnet", cin, cout, temb_dim=512).load(wl, precision="bf16")
-            outs[late] = blk(x[:, :split].contiguous(), x[:, split:].contiguous(), temb=temb)
+            outs[own] = blk(x[:, :split].contiguous(), x[:, split:].contiguous(), temb=temb)
         finally:
-            os.environ.pop("FLOWSE_SCFOLD_LATE", None)
+            os.environ.pop("FLOWSE_NO_SCFOLD", None)
     e0, e1, d = C.rel_l2(outs[False], ref), C.rel_l2(outs[True], ref), C.rel_l2(outs[True], outs[False])
-    print(f"folded {e0:.3e}  late shortcut {e1:.3e}  between them {d:.3e}")
-    assert e0 < 6e-3 and e1 < 6e-3 and 0 < d < 6e-3               # (d > 0: the late branch really ran another plan)
+    print(f"folded {e0:.3e}  own launch {e1:.3e}  between them {d:.3e}")
+    assert e0 < 6e-3 and e1 < 6e-3 and 0 < d < 6e-3               # (d > 0: the hook really gave another plan)
 
 
 def _worst_sample(got, ref):
@@ -259,3 +259,75 @@ def test_resblock_split_k_shapes_vs_oracle(tag, shp):
     err, worst = C.rel_l2(got, ref), _worst_sample(got, ref)
     print(tag, "split-K resblock vs oracle", err, "worst sample", worst)
     assert err < TOL and worst < TOL
+
+
+def forward_with_labels(blk, x, split, temb):
+    """-> (block output, {launch label: launches} of that forward, in launch order)"""
+    import ctypes as Ct
+    import json
+    from flowmse_amd import _lib
+    _lib.check(_lib.lib.flowse_profile_begin(blk.h, 1))
+    got = blk(x, temb=temb) if split is None else blk(x[:, :split].contiguous(), x[:, split:].contiguous(), temb=temb)
+    buf = Ct.create_string_buffer(1 << 16)
+    _lib.check(_lib.lib.flowse_profile_end(blk.h, buf, len(buf)))
+    return got, {k: v["launches"] for k, v in json.loads(buf.value.decode()).items() if not k.startswith("_")}
+
+
+# ResnetBlocks with 2049..8191 pixels over the batch: past the small-image kernels (<= 2048 pixels), short of one block per
+# CU -- every 3x3 conv runs as K slices with a reduction launch, and the plan folds work into those reductions.  The last
+# column: launches per label family (the label up to its "@") that show the case reached its plan; 0 = must not appear.
+#   F(4,3) slices need H % 8 == 0 and W % 16 == 0 and normalise on load; other widths run flat slices on a materialised input
+#   Conv_0's reduction takes GroupNorm_1 from 128 (group, sample) blocks on: B >= 4 at 32 groups
+#   a concat input (256 + 256 -> 256) has the 1x1 shortcut Conv_2; its slices ride on Conv_1's reduction: ONE splitk_reduce
+# Which block-level case covers which form of the plan (Builder::resblock's record):
+#   shortcut     none: every 256 -> 256 row here | own launch: rb_widen, rb_gn12, CASES16 tiny_4x4_concat / up / down, the
+#                small up block of test_gpu_upblock_shortcut.py | low resolution: UP of test_gpu_upblock_shortcut.py |
+#                merged: the *_merged rows | folded: CASES16 concat_halo_shortcut, concat384_straddle, concat_halo_16x16_tile
+#   GroupNorm_0  on load: the f43_* rows, CASES16 *_halo* | materialised: the flat_* rows, RB
+#   GroupNorm_1  applied by Conv_0's reduction: flat_apply* | mean / scale from Conv_0's reduction: f43_stats* | gn() + on
+#                load: f43_b1*, CASES16 *_halo* | materialised: flat_b3, RB, the small-image rows of the test above
+SLICED = [  # tag, mode, cin, cout, (B, C, H, W), two-source split, label family -> launches
+    ("f43_stats", "fp32", 256, 256, (4, 256, 16, 48), None,
+     {"conv0_3x3_gn": 1, "splitk_reduce_gn": 1, "conv1_3x3_gn": 1, "splitk_reduce": 1, "gn_finalize": 1, "gn_norm": 0}),
+    ("flat_apply", "fp32", 256, 256, (4, 256, 24, 24), None,
+     {"conv0_3x3": 1, "splitk_reduce_gn": 1, "conv1_3x3": 1, "splitk_reduce": 1, "gn_norm": 1, "gn_finalize": 0}),
+    ("f43_stats_merged", "fp32", 512, 256, (4, 512, 16, 48), 256,
+     {"conv2_1x1": 1, "conv0_3x3_gn": 1, "splitk_reduce_gn": 1, "conv1_3x3_gn": 1, "splitk_reduce": 1}),
+    ("flat_apply_merged", "fp32", 512, 256, (4, 512, 24, 24), 256,
+     {"conv2_1x1": 1, "conv0_3x3": 1, "splitk_reduce_gn": 1, "conv1_3x3": 1, "splitk_reduce": 1}),
+    ("f43_b1", "fp32", 256, 256, (1, 256, 48, 48), None,
+     {"conv0_3x3_gn": 1, "splitk_reduce_gn": 0, "gn_finalize": 2, "conv1_3x3_gn": 1, "splitk_reduce": 2}),
+    ("f43_b1_merged", "fp32", 512, 256, (1, 512, 48, 48), 256,
+     {"conv2_1x1": 1, "conv0_3x3_gn": 1, "splitk_reduce_gn": 0, "gn_finalize": 2, "conv1_3x3_gn": 1, "splitk_reduce": 2}),
+    ("flat_b3", "fp32", 256, 256, (3, 256, 32, 24), None,
+     {"conv0_3x3": 1, "splitk_reduce_gn": 0, "gn_norm": 2, "conv1_3x3": 1, "splitk_reduce": 2}),
+    ("flat16_merged", "bf16", 512, 256, (4, 512, 32, 32), 256,
+     {"conv2_1x1": 1, "conv0_3x3": 1, "splitk_reduce_gn": 1, "conv1_3x3": 1, "splitk_reduce": 1}),
+    ("flat16_merged", "fp16", 512, 256, (4, 512, 32, 32), 256,
+     {"conv2_1x1": 1, "conv0_3x3": 1, "splitk_reduce_gn": 1, "conv1_3x3": 1, "splitk_reduce": 1}),
+]
+
+
+def sliced_inputs(tag, cin, cout, shp):
+    """weights, input and raw time embedding of a SLICED row (tools/block_plans.py runs the same)"""
+    wl = _weights(C.resblock_keys(cin, cout, 512, None), f"sl.{tag}.")
+    return wl, torch.from_numpy(synth.normal(9, 23, shp)), torch.from_numpy(synth.normal(9, 24, (shp[0], 512)))
+
+
+@pytest.mark.parametrize("tag,mode,cin,cout,shp,split,want", SLICED, ids=[f"{c[0]}-{c[1]}" for c in SLICED])
+def test_resblock_sliced_range_vs_oracle(tag, mode, cin, cout, shp, split, want):
+    import _gpu as G
+    from oracle import ncsnpp_oracle as O
+    assert 2048 < shp[0] * shp[2] * shp[3] < 8192
+    bound = dict(MODES16).get(mode, TOL)
+    wl, x, temb = sliced_inputs(tag, cin, cout, shp)
+    blk = G.Block("resnet", cin, cout, temb_dim=512).load(wl, precision=mode)
+    ref = O.resblock(O._W({f"all_modules.0.{k}": v for k, v in wl.items()}), 0, x, temb)
+    got, labels = forward_with_labels(blk, x, split, temb)
+    err, worst = C.rel_l2(got, ref), _worst_sample(got, ref)
+    print(f"resblock {tag} {mode}: rel-L2 vs oracle {err:.3e}, worst sample {worst:.3e}; launches: {labels}")
+    assert got.shape == ref.shape and err < bound and worst < bound
+    families = {}
+    for k, n in labels.items():
+        families[k.split("@")[0]] = families.get(k.split("@")[0], 0) + n
+    assert {f: families.get(f, 0) for f in want} == want, labels
