@@ -255,8 +255,8 @@ struct ConvArgs {
     const float* partial2 = nullptr;    // [ksplit2][B*H*W][Cout]
     int ksplit2 = 0;
     const float* bias_x = nullptr;      // [Cout] or null
-    // fused GroupNorm statistics of the OUTPUT (optional): per-(sample, pixel tile, channel) sum / sum of squares
-    // written to stats[((b * stats_nblk + tile) * Cout + c) * 2 + {0,1}], the layout gn_finalize consumes.
+    // fused GroupNorm statistics of the OUTPUT (optional): per-(sample, pixel tile, channel) mean / M2 (sum of squared
+    // deviations) written to stats[((b * stats_nblk + tile) * Cout + c) * 2 + {0,1}], the layout gn_finalize consumes.
     // stats_nblk must be the geometry of the kernel that runs (ConvRoute::stats_nblk).
     float* stats = nullptr;
     int stats_nblk = 0;
@@ -398,6 +398,8 @@ struct ConvRoute {
 };
 ConvRoute conv_route(const ConvShape& q, const ConvOffer& o);
 int conv_shape_check(const ConvShape& q);      // the argument checks of launch_conv that the shape alone decides
+// the route launch_conv takes for these arguments: conv_route of their shape and of what their pointers offer
+ConvRoute conv_route_of(const ConvArgs& a);
 // validate, route, switch.  with_reduce = false: a split-K launch only writes the partial slices (the caller runs
 // launch_splitk_reduce)
 int launch_conv(const ConvArgs& a, hipStream_t s, bool with_reduce = true);

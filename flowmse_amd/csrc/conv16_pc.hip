@@ -710,9 +710,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pc16_kernel(ConvArgs a) {
         d_voff = (unsigned)((((dp.y0 + (d_pg >> 4)) * W + dp.x0 + (d_pg & 15)) * a.Cout + dp.n0 + d_o * 8) * 2);
     };
     // One strip: NPH 16-byte pieces LDS -> global (write-through, see FLOWSE_PC16_STORE_AUX), and the moments of what is
-    // stored per channel PAIR: S1 = sum x, S2 = sum x^2 over the thread's 2 NPH values with ONE v_dot2c each per packed word
-    // (fp32 accumulation of exact products; half: about the thread's first value as pivot -- 22-bit squares do not sum exactly),
-    // equal-count Chan merges over the lanes that share the octet (64 values), then `red`.
+    // stored per channel PAIR: S1 = sum x, S2 = sum x^2 over the thread's 2 NPH values.  bf16: ONE v_dot2c each per packed word
+    // (fp32 accumulation of exact products).  half: 22-bit squares do not sum exactly, so the sums run over the deviations from
+    // the thread's first value -- widened to fp32 BEFORE the subtraction: a packed half subtraction rounds every deviation to
+    // 11 bits, which cost the mean 1.2e-5 sigma and the variance 4.5e-5 against float64 (tests/test_gpu_fused_stats.py; the
+    // bf16 form and every other producer stay below 1e-7).  Then equal-count Chan merges over the lanes that share the octet
+    // (64 values), then `red`.
 #define FLOWSE_PC_DRAIN(TS)                                                                                          \
     {                                                                                                                \
         u32x4 pc[NPH];                                                                                               \
@@ -727,13 +730,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pc16_kernel(ConvArgs a) {
                 float s1 = 0.f, s2 = 0.f, pv = 0.f;                                                                  \
                 if (F16) {                                                                                           \
                     typedef _Float16 h2_t __attribute__((ext_vector_type(2)));                                       \
-                    const unsigned pk = (w0 & 0xffffu) * 0x10001u;                                                   \
                     pv = (float)__builtin_bit_cast(_Float16, (unsigned short)(w0 & 0xffffu));                        \
                     _Pragma("unroll") for (int k = 0; k < NPH; ++k) {                                                \
                         const unsigned wk = e == 0 ? pc[k].x : e == 1 ? pc[k].y : e == 2 ? pc[k].z : pc[k].w;       \
-                        const h2_t d = __builtin_bit_cast(h2_t, wk) - __builtin_bit_cast(h2_t, pk);                  \
-                        s1 = __builtin_amdgcn_fdot2(d, __builtin_bit_cast(h2_t, 0x3c003c00u), s1, false);            \
-                        s2 = __builtin_amdgcn_fdot2(d, d, s2, false);                                                \
+                        const h2_t x = __builtin_bit_cast(h2_t, wk);                                                 \
+                        const float d0 = (float)x.x - pv, d1 = (float)x.y - pv;                                      \
+                        s1 = (s1 + d0) + d1;                                                                         \
+                        s2 = __builtin_fmaf(d1, d1, __builtin_fmaf(d0, d0, s2));                                     \
                     }                                                                                                \
                 } else {                                                                                             \
                     typedef __bf16 b2_t __attribute__((ext_vector_type(2)));                                         \

@@ -366,6 +366,20 @@ int conv_shape_check(const ConvShape& q) {
     return OK;
 }
 
+// What a hand-filled ConvArgs offers -- the pointers it carries -- and the route of that: launch_conv's own derivation, shared
+// with a caller that needs the answer before the launch (the statistics sink of the per-op entries)
+ConvRoute conv_route_of(const ConvArgs& a) {
+    const ConvShape q{a.in_dt, a.out_dt, a.B, a.H, a.W, a.C1, a.C2, a.Cout, a.taps};
+    ConvOffer o;
+    o.wino = a.wino != nullptr; o.wino2 = a.wino2 != nullptr; o.wsm = a.wsm != nullptr || a.wsm16 != nullptr; o.wfrag = a.wfrag != nullptr;
+    o.wq = a.wq != nullptr; o.terms = a.terms; o.wq_f16 = a.wq_f16 != 0;
+    o.slab = a.partial != nullptr;
+    o.gn = a.gn.mean != nullptr;
+    o.bias2 = a.bias2 != nullptr; o.stats = a.stats != nullptr;
+    o.fold = a.sc1 || a.sc2 || a.wfrag_sc;
+    return conv_route(q, o);
+}
+
 int launch_conv(const ConvArgs& a, hipStream_t s, bool with_reduce) {
     const ConvShape q{a.in_dt, a.out_dt, a.B, a.H, a.W, a.C1, a.C2, a.Cout, a.taps};
     if ((a.bias2 && (a.bias2_stride & 3)) || (a.in2 == nullptr && a.C2 != 0)) {
@@ -377,14 +391,7 @@ int launch_conv(const ConvArgs& a, hipStream_t s, bool with_reduce) {
         set_error("conv: split-K needs a partial buffer");
         return ERR_ARG;
     }
-    ConvOffer o;
-    o.wino = a.wino != nullptr; o.wino2 = a.wino2 != nullptr; o.wsm = a.wsm != nullptr || a.wsm16 != nullptr; o.wfrag = a.wfrag != nullptr;
-    o.wq = a.wq != nullptr; o.terms = a.terms; o.wq_f16 = a.wq_f16 != 0;
-    o.slab = a.partial != nullptr;
-    o.gn = a.gn.mean != nullptr;
-    o.bias2 = a.bias2 != nullptr; o.stats = a.stats != nullptr;
-    o.fold = a.sc1 || a.sc2 || a.wfrag_sc;
-    const ConvRoute r = conv_route(q, o);
+    const ConvRoute r = conv_route_of(a);
     if (r.err == OK && r.ksplit != (a.ksplit > 1 ? a.ksplit : 1)) {     // the slab was sized for another split
         set_error("conv: ksplit=%d, this shape runs over %d K slices", a.ksplit, r.ksplit);
         return ERR_ARG;

@@ -35,6 +35,33 @@ static int op_gn_prologue(const float* in1, int C1, const float* in2, int C2, co
     return launch_gn_finalize(scratch, nblk, C, nullptr, 0, 0, B, HW, std::min(C / 4, 32), gamma, eps, mean, scl, s);
 }
 
+// The statistics sink (flowse_op_stats_sink): while armed, every per-op conv entry has its launch leave the fused GroupNorm
+// partials of its output there -- a thread-local test hook in the style of conv_last_route.  op_sink_stats is called on the
+// ConvArgs as they will be launched (weights, slab, GroupNorm input all set): the geometry is the route's of exactly those
+// arguments, and a route that writes no statistics launches without.
+static thread_local struct { float* buf; int64_t floats; int blocks; } g_sink = {nullptr, 0, 0};
+static int op_sink_stats(ConvArgs& c, const char* entry, bool w2d_named = false) {
+    if (!g_sink.buf) return OK;
+    g_sink.blocks = 0;
+    const ConvShape q{c.in_dt, c.out_dt, c.B, c.H, c.W, c.C1, c.C2, c.Cout, c.taps};
+    if ((c.in2 == nullptr && c.C2 != 0) || conv_shape_check(q) != OK) return OK;      // launch_conv's error to report
+    c.stats = g_sink.buf;
+    const ConvRoute r = conv_route_of(c);
+    // (flowse_op_conv3x3_w2d names its kernel whatever the policy would run: that kernel's 64-pixel strips)
+    const int nblk = r.err != OK ? 0 : w2d_named ? c.H * c.W / 64 : r.stats_nblk;
+    if (nblk <= 0) {
+        c.stats = nullptr;
+        return OK;
+    }
+    if ((int64_t)c.B * nblk * c.Cout * 2 > g_sink.floats) {
+        set_error("%s: the statistics sink holds %lld floats, this launch writes %lld", entry, (long long)g_sink.floats,
+                  (long long)c.B * nblk * c.Cout * 2);
+        return ERR_ARG;
+    }
+    c.stats_nblk = g_sink.blocks = nblk;
+    return OK;
+}
+
 // Copy k of conv_copy of c's weights (`w16`: their 16-bit twin, for the 16-bit copies), made at dst; c then points at it
 static int op_make_copy(ConvArgs& c, int k, const void* w16, void* dst, hipStream_t s) {
     const int rc = conv_copy(k).make(c.w, w16, c.Cout, c.taps, c.C1 + c.C2, dst, s);
@@ -115,6 +142,7 @@ int flowse_op_conv2d(const float* in1, int C1, const float* in2, int C2, const f
             if (r.reads_weight(k))
                 if (const int rc = op_make_copy(c, k, nullptr, splitk_scratch, s)) return rc;
     }
+    if (const int rc = op_sink_stats(c, "flowse_op_conv2d")) return rc;
     return launch_conv(c, s);
 }
 
@@ -154,7 +182,8 @@ int flowse_op_conv3x3_gn(const float* in1, int C1, const float* in2, int C2, con
     hipStream_t s = static_cast<hipStream_t>(stream);
     ConvArgs c = conv_args(in1, C1, in2, C2, w, bias, bias2, bias2_stride, res, out, B, H, W, Cout, 9, scale);
     c.gn_silu = silu;
-    const int rc = op_gn_prologue(in1, C1, in2, C2, gamma, beta, eps, B, H * W, scratch, s, &c.gn);
+    int rc = op_gn_prologue(in1, C1, in2, C2, gamma, beta, eps, B, H * W, scratch, s, &c.gn);
+    if (rc == OK) rc = op_sink_stats(c, "flowse_op_conv3x3_gn");
     return rc != OK ? rc : launch_conv(c, s);
 }
 
@@ -190,6 +219,8 @@ static int op_conv3x3_winograd(const float* in1, int C1, const float* in2, int C
         rc = op_gn_prologue(in1, C1, in2, C2, gamma, beta, eps, B, HW, scratch, s, &c.gn);
         if (rc != OK) return rc;
     }
+    rc = op_sink_stats(c, two_d ? "flowse_op_conv3x3_w2d" : "flowse_op_conv3x3_f43", two_d);
+    if (rc != OK) return rc;
     // the 2-D entry names its kernel: every shape conv_w2d_shape_ok admits runs it (launch_conv's policy would hand images of
     // up to 2048 pixels to another kernel, or refuse their fused GroupNorm input)
     return two_d ? launch_w2d(c, s) : launch_conv(c, s);
@@ -298,7 +329,8 @@ static int op_conv2d_16(const float* in1, int C1, const float* in2, int C2, cons
         c.out = out;
         c.out_dt = DT_F32;
     }
-    rc = launch_conv(c, s);
+    rc = op_sink_stats(c, "flowse_op_conv2d_16");
+    if (rc == OK) rc = launch_conv(c, s);
     if (rc != OK || direct) return rc;
     return launch_convert(o16, dt, out, DT_F32, M * Cout, s);
 }
@@ -415,9 +447,60 @@ int flowse_op_resblock_tail_16(const float* h, int C, const float* gn_mean, cons
         c.gn = GnParams{gn_mean, gn_scale, gn_beta};
         c.gn_silu = silu;
     }
-    rc = launch_conv(c, s);
+    rc = op_sink_stats(c, "flowse_op_resblock_tail_16");
+    if (rc == OK) rc = launch_conv(c, s);
     if (rc != OK) return rc;
     return launch_convert(o16, dt, out, DT_F32, M * Cout, s);
+}
+
+int flowse_op_stats_sink(float* buf, int64_t floats) {
+    if ((buf == nullptr) != (floats <= 0)) {
+        set_error("flowse_op_stats_sink: a buffer and its size in floats, or (null, 0) to disarm");
+        return ERR_ARG;
+    }
+    g_sink = {buf, buf ? floats : 0, 0};
+    return OK;
+}
+int flowse_op_stats_sink_blocks(void) { return g_sink.blocks; }
+
+int flowse_op_gn_stats(const float* in1, int C1, const float* in2, int C2, int B, int HW, int dt, void* scratch,
+                       int64_t scratch_bytes, float* partial, int nblk, void* stream) {
+    if (!in1 || !partial || nblk < 1 || B < 1 || HW < 1 || dt < DT_F32 || dt > DT_F16 || (dt != DT_F32 && !scratch)) {
+        set_error("flowse_op_gn_stats: bad argument");
+        return ERR_ARG;
+    }
+    if (!in2) C2 = 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dt == DT_F32) return launch_gn_stats(in1, C1, in2, C2, B, HW, partial, nblk, s);
+    const int64_t M = (int64_t)B * HW;
+    if ((C1 & 3) || (C2 & 3) || scratch_bytes < Carver::up(2 * M * C1) + Carver::up(2 * M * C2)) {
+        set_error("flowse_op_gn_stats: channel counts must be multiples of 4 and scratch hold both inputs in 16 bits");
+        return ERR_ARG;
+    }
+    Carver cv{static_cast<char*>(scratch)};
+    void* a1 = cv.take(2 * M * C1);
+    void* a2 = C2 ? cv.take(2 * M * C2) : nullptr;
+    int rc = launch_convert(in1, DT_F32, a1, dt, M * C1, s);
+    if (rc == OK && C2) rc = launch_convert(in2, DT_F32, a2, dt, M * C2, s);
+    if (rc != OK) return rc;
+    return launch_gn_stats(a1, C1, a2, C2, B, HW, partial, nblk, s, dt);
+}
+
+int flowse_op_gn_finalize(const float* p1, int nblk1, int C1, const float* p2, int nblk2, int C2, int B, int HW, int G,
+                          const float* gamma, float eps, float* mean, float* scale, const float* in1, const float* in2,
+                          const float* beta, int silu, float* out, void* stream) {
+    if (!p1 || !gamma || nblk1 < 1 || B < 1 || HW < 1 || G < 1 || (out ? !in1 || !beta : !mean || !scale)) {
+        set_error("flowse_op_gn_finalize: bad argument");
+        return ERR_ARG;
+    }
+    if (!p2) { C2 = 0; nblk2 = 0; }
+    if (C2 > 0 && nblk2 < 1) {
+        set_error("flowse_op_gn_finalize: the second set needs its block count");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (out) return launch_gn_finalize_apply(in1, p1, nblk1, C1, in2, p2, nblk2, C2, B, HW, G, gamma, beta, eps, silu, out, s);
+    return launch_gn_finalize(p1, nblk1, C1, p2, nblk2, C2, B, HW, G, gamma, eps, mean, scale, s);
 }
 
 int flowse_op_pc16_channel_blocks(int mode) {

@@ -607,6 +607,28 @@ int flowse_op_resblock_tail_16(const float* h, int C, const float* gn_mean, cons
  * 1: always 64 (also FLOWSE_PC16_NARROW=0 / 1 in the environment).  Results differ only in summation grouping of the
  * GroupNorm partial statistics (the convolution sums are identical). */
 int flowse_op_pc16_channel_blocks(int mode);
+/* Test hook, thread-local: a sink for the GroupNorm statistics a conv kernel fuses into its output stage.  While armed
+ * (buf, floats > 0), every per-op conv entry -- flowse_op_conv2d, _conv3x3_gn, _conv3x3_f43, _conv3x3_w2d, _conv2d_16,
+ * _conv2d_16_ex, _resblock_tail_16 -- launches with the partials of its OUTPUT written to buf, [B][nblk][Cout][2] floats of
+ * (mean, M2) per (sample, pixel block, channel): the layout flowse_op_gn_finalize consumes.  nblk is the route's of exactly
+ * the arguments the entry launches (the "stats=" of flowse_op_conv_route for them); flowse_op_stats_sink_blocks() returns it
+ * after the call, 0 where that route writes no statistics (the launch then runs without).  A sink too small for
+ * B * nblk * Cout * 2 floats: FLOWSE_ERR_ARG, nothing launched.  Only the GROUP sums of the partials are specified: a
+ * kernel may spread a group's (mean, M2) over its channels as it likes.  (NULL, 0) disarms; disarmed, nothing changes. */
+int flowse_op_stats_sink(float* buf, int64_t floats);
+int flowse_op_stats_sink_blocks(void);
+/* The stand-alone statistics kernel: partial [B][nblk][C1 + C2][2] of cat[in1, in2] ([B][HW][C*] fp32, in2 may be NULL) in
+ * nblk blocks of ceil(HW / nblk) pixels.  dt 1 / 2: the input is first rounded to bf16 / half into `scratch` (256 bytes of
+ * slack per tensor) and read from there, as the 16-bit storage modes do; dt 0 needs no scratch. */
+int flowse_op_gn_stats(const float* in1, int C1, const float* in2, int C2, int B, int HW, int dt, void* scratch,
+                       int64_t scratch_bytes, float* partial, int nblk, void* stream);
+/* Merge of one or two partial sets (set 1: channels [0, C1), nblk1 blocks; set 2, may be NULL: [C1, C1 + C2), nblk2 blocks;
+ * each in blocks of ceil(HW / nblk) pixels, the last one short) into per-(sample, channel) mean and scale = rstd * gamma
+ * [B][C1 + C2] over G groups.  With `out` (and in1, beta; in2 where C2 > 0) the one-launch form for small images instead:
+ * out = act((cat[in1, in2] - mean) * scale + beta), mean / scale not written. */
+int flowse_op_gn_finalize(const float* p1, int nblk1, int C1, const float* p2, int nblk2, int C2, int B, int HW, int G,
+                          const float* gamma, float eps, float* mean, float* scale, const float* in1, const float* in2,
+                          const float* beta, int silu, float* out, void* stream);
 /* Fused ResnetBlock half:  out = (conv3x3(act(GroupNorm(cat[in1,in2]))) + bias + bias2[b] + res) * scale
  * (layerspp.py:246-249 / :265-267) with the normalisation + SiLU applied while the input tile is staged into LDS.
  * Only for shapes the halo kernel covers (H % 8 == 0, W % 16 == 0, C1 % 32 == 0, C2 % 32 == 0, image large

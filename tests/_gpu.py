@@ -34,14 +34,15 @@ def conv_operands(x1, x2, w, taps, bias, bias2, res):
     return a1, a2, wp, bb, b2, rr
 
 
-def conv2d(x1, w, bias=None, x2=None, bias2=None, res=None, scale=1.0, padding=None, splitk=False):
-    """x*: NCHW cpu tensors; w: [Cout, Cin, k, k] (reference layout). Returns NCHW cpu."""
+def conv2d(x1, w, bias=None, x2=None, bias2=None, res=None, scale=1.0, padding=None, splitk=False, res_in_place=False):
+    """x*: NCHW cpu tensors; w: [Cout, Cin, k, k] (reference layout). Returns NCHW cpu.  res_in_place: the residual sits in
+    the output buffer (res aliases out, as the Combine 1x1 runs)."""
     Cout, Cin, k, _ = w.shape
     taps = k * k
     a1, a2, wp, bb, b2, rr = conv_operands(x1, x2, w, taps, bias, bias2, res)
     B, H, W, C1 = a1.shape
     C2 = a2.shape[3] if a2 is not None else 0
-    out = torch.empty(B, H, W, Cout, device="cuda")
+    out = rr if res_in_place else torch.empty(B, H, W, Cout, device="cuda")
     scratch = None
     if splitk:
         n = L.flowse_op_conv2d_scratch_floats(B, H, W, C1 + C2, Cout, taps)
@@ -52,6 +53,71 @@ def conv2d(x1, w, bias=None, x2=None, bias2=None, res=None, scale=1.0, padding=N
                                   taps, float(scale), _lib.ptr(scratch), stream()))
     torch.cuda.synchronize()
     return nchw(out)
+
+
+class stats_sink:
+    """Context manager around flowse_op_stats_sink: every per-op conv entry called inside leaves the fused GroupNorm partials
+    of its output in a device buffer of `floats` floats (filled with NaN before).  After the block: .blocks = the launch's
+    blocks per sample (0: its route writes none), .partial(B, Cout) = the [B, nblk, Cout, 2] (mean, M2) tensor on the cpu,
+    .clean_beyond(B, Cout) = nothing was written past it."""
+
+    def __init__(self, floats):
+        self.buf = torch.full((int(floats),), float("nan"), device="cuda")
+        self.blocks = 0
+
+    def __enter__(self):
+        _lib.check(L.flowse_op_stats_sink(_lib.ptr(self.buf), self.buf.numel()))
+        return self
+
+    def __exit__(self, *exc):
+        self.blocks = int(L.flowse_op_stats_sink_blocks())
+        _lib.check(L.flowse_op_stats_sink(None, 0))
+        torch.cuda.synchronize()
+        return False
+
+    def partial(self, B, Cout):
+        return self.buf[:B * self.blocks * Cout * 2].view(B, self.blocks, Cout, 2).cpu()
+
+    def clean_beyond(self, B, Cout):
+        return bool(torch.isnan(self.buf[B * self.blocks * Cout * 2:]).all())
+
+
+def gn_stats(x1, nblk, x2=None, dt=0):
+    """The stand-alone statistics kernel (flowse_op_gn_stats) on NCHW cpu tensors (rounded to dt inside: 1 = bf16, 2 = half):
+    partial [B, nblk, C1 + C2, 2] on the cpu"""
+    a1 = nhwc(x1)
+    a2 = nhwc(x2) if x2 is not None else None
+    B, H, W, C1 = a1.shape
+    C2 = a2.shape[3] if a2 is not None else 0
+    part = torch.full((B, nblk, C1 + C2, 2), float("nan"), device="cuda")
+    scratch = torch.empty(2 * B * H * W * (C1 + C2) + 512, dtype=torch.uint8, device="cuda") if dt else None
+    _lib.check(L.flowse_op_gn_stats(_lib.ptr(a1), C1, _lib.ptr(a2), C2, B, H * W, dt, _lib.ptr(scratch),
+                                    scratch.numel() if dt else 0, _lib.ptr(part), nblk, stream()))
+    torch.cuda.synchronize()
+    return part.cpu()
+
+
+def gn_finalize(p1, HW, G, gamma, p2=None, eps=1e-6, x1=None, x2=None, beta=None, silu=False):
+    """flowse_op_gn_finalize on partial sets [B, nblk, C, 2] (cpu).  Without x1: (mean, scale) [B, C1 + C2] on the cpu; with
+    x1 (x2), beta (NCHW cpu): the normalised tensor of the finalize + apply kernel, NCHW cpu."""
+    d1 = p1.contiguous().cuda().float()
+    d2 = p2.contiguous().cuda().float() if p2 is not None else None
+    B, nblk1, C1, _ = d1.shape
+    nblk2, C2 = (d2.shape[1], d2.shape[2]) if d2 is not None else (0, 0)
+    g = gamma.contiguous().cuda().float()
+    mean = scl = a1 = a2 = be = out = None
+    if x1 is None:
+        mean = torch.full((B, C1 + C2), float("nan"), device="cuda")
+        scl = torch.full((B, C1 + C2), float("nan"), device="cuda")
+    else:
+        a1, a2 = nhwc(x1), nhwc(x2) if x2 is not None else None
+        be = beta.contiguous().cuda().float()
+        out = torch.full((B, a1.shape[1], a1.shape[2], C1 + C2), float("nan"), device="cuda")
+    _lib.check(L.flowse_op_gn_finalize(_lib.ptr(d1), nblk1, C1, _lib.ptr(d2), nblk2, C2, B, HW, G, _lib.ptr(g), eps,
+                                       _lib.ptr(mean), _lib.ptr(scl), _lib.ptr(a1), _lib.ptr(a2), _lib.ptr(be), int(silu),
+                                       _lib.ptr(out), stream()))
+    torch.cuda.synchronize()
+    return (mean.cpu(), scl.cpu()) if x1 is None else nchw(out)
 
 
 def last_route():

@@ -8,7 +8,8 @@ Every row first asserts that the launch ran the kernel its row names (flowse_op_
 launcher), then the element bound on every element and, without fused GroupNorm, the second check.  pc16 rows run with
 128- and with 64-channel blocks (flowse_op_pc16_channel_blocks(0) / (1)); every row runs in bf16 and fp16.  The probe rows
 (one-hot weights: output block t = the staged operand of tap t) are compared bit for bit.  The fused GroupNorm
-statistics are not part of this file: the op entries launch with stats = nullptr.
+statistics of these kernels are held to float64 in tests/test_gpu_fused_stats.py (here the statistics sink is not armed:
+the op entries launch with stats = nullptr).
 
 Recorded on an MI355X (worst over the rows of a route and type: max |d| / bound, mismatch share of the rows without
 fused GN; fp32-output rows: rel-L2):

@@ -332,8 +332,9 @@ def test_group_norm_large_mean(G, offset):
     got = G.group_norm(x, g, b, silu=False)
     # floor: the mean itself is stored in fp32 (half an ulp of 1000 is 3e-5 of one standard deviation)
     assert C.rel_l2(got, ref) < (2e-5 if offset < 100 else 6e-5)
-    # same through the statistics fused into a conv epilogue + GroupNorm fused into the next conv's input:
-    # y = conv_b(GN(conv_a(x0)))  with conv_a producing a large-mean tensor
+    # same with the GroupNorm fused into the next conv's input: y = conv_b(GN(conv_a(x0))) with conv_a producing a
+    # large-mean tensor.  The statistics are the stand-alone kernel's again (flowse_op_conv3x3_gn measures its input itself);
+    # the ones conv_a's output stage leaves: test_gpu_fused_stats.py::test_group_norm_large_mean_fused
     x0 = rnd(20, (2, 32, 128, 128))
     wa = rnd(21, (128, 32, 3, 3), (1.0 / (32 * 9)) ** 0.5)
     ba = torch.full((128,), float(offset))

@@ -6,7 +6,8 @@ that the bounds are attainable and that a kernel rounding twice misses them).
 Every case first asserts that the launch ran the instance its row names (flowse_op_last_conv_route: recorded by the
 launcher, not re-derived from the shape), then the element bound on every element and the second check (rel-L2 for fp32
 output; the share of elements that differ from the once-rounded reference for 16-bit output).  The fused GroupNorm
-statistics are not part of this file: the op entries launch with stats = nullptr.
+statistics of these kernels are held to float64 in tests/test_gpu_fused_stats.py (here the statistics sink is not armed:
+the op entries launch with stats = nullptr).
 """
 import pytest
 import torch
