@@ -92,6 +92,7 @@ SIGNATURES = {
     "flowse_resample_num_taps": (_i, [_i, _i]),
     "flowse_resample_taps": (_i, [_i, _i, C.POINTER(_d), _i]),
     "flowse_resample_poly": (_i, [_fp, _i, _i, _i, _i, _fp, _i, _vp]),
+    "flowse_resample_poly_window": (_i, [_fp, _i64, _i64, _i64, _i, _i, _fp, _i64, _i64, _vp]),
     "flowse_estoi_num_taps": (_i, []),
     "flowse_estoi_taps": (_i, [C.POINTER(_d), _i]),
     "flowse_metrics_workspace_bytes": (_i64, [_i]),

@@ -89,6 +89,25 @@ static void design_taps(const Ratio& r, double* h) {
     for (int k = 0; k < n; ++k) h[k] = h[k] / sum * (double)r.up;
 }
 
+// One output: the fmaf chain over j = 0 .. P - 1 of h[j] x[q - j], from +0.f -- the one tap loop of both kernels below, so
+// that a window's output is the whole signal's bit for bit.  X_LDS: `xq` points at x[q] in a staged span that holds
+// x[q - (P - 1) .. q], zeros already written where the signal has no sample.  Otherwise `x` holds the samples [lo, hi) of
+// the row (x[0] is sample lo) and every other sample is zero.
+template <bool X_LDS>
+__device__ __forceinline__ float resample_output(const float* h, int P, const float* xq, const float* __restrict__ x,
+                                                 int64_t q, int64_t lo, int64_t hi) {
+    float acc = 0.f;
+    if (X_LDS) {
+        for (int j = 0; j < P; ++j) acc = fmaf(h[j], xq[-j], acc);
+    } else {
+        for (int j = 0; j < P; ++j) {
+            const int64_t m = q - j;
+            acc = fmaf(h[j], m >= lo && m < hi ? x[m - lo] : 0.f, acc);
+        }
+    }
+    return acc;
+}
+
 // A block owns `run` consecutive outputs of row blockIdx.y.  X_LDS: the input span they touch is staged once, zeros
 // written for samples outside [0, L) -- otherwise (ratios whose span does not fit) each tap reads global memory behind the
 // same bounds test.  H_LDS: the whole table is copied next to it -- otherwise rows of it are read through L2.
@@ -119,17 +138,44 @@ __global__ __launch_bounds__(RESAMPLE_THREADS) void resample_poly_kernel(const f
         const int64_t c = (int64_t)half + n * down;
         const int64_t q = c / up;
         const float* h = (H_LDS ? hs : H) + (int)(c - q * up) * P;
-        float acc = 0.f;
-        if (X_LDS) {
-            const float* xq = xs + (int)(q - q_lo);                       // in [P - 1, span)
-            for (int j = 0; j < P; ++j) acc = fmaf(h[j], xq[-j], acc);
-        } else {
-            for (int j = 0; j < P; ++j) {
-                const int64_t m = q - j;
-                acc = fmaf(h[j], m >= 0 && m < L ? x[m] : 0.f, acc);
-            }
+        const float* xq = xs + (int)(q - q_lo);                           // in [P - 1, span) when X_LDS
+        o[n] = resample_output<X_LDS>(h, P, xq, x, q, 0, L);
+    }
+}
+
+// The same outputs from a window of ONE row: `win` holds the samples [m0, m0 + n_win) of the signal, the grid covers the
+// outputs [n0, n0 + n_out), a block `run` consecutive ones, and out[0] is output n0.  The host has checked that every
+// sample of the signal an output needs lies in the window, so a sample outside the window is a zero of the definition
+// (below 0, or at or past the end of a closed signal).  Every index is 64-bit: m0, n0, c and q are absolute.
+template <bool X_LDS, bool H_LDS>
+__global__ __launch_bounds__(RESAMPLE_THREADS) void resample_poly_window_kernel(const float* __restrict__ win, int64_t m0,
+                                                                                int64_t n_win, const float* __restrict__ H,
+                                                                                float* __restrict__ out, int64_t n0,
+                                                                                int64_t n_out, int up, int down, int half,
+                                                                                int P, int run, int span) {
+    extern __shared__ float lds[];
+    float* xs = lds;                               // [span] when X_LDS
+    float* hs = lds + (X_LDS ? span : 0);          // [up][P] when H_LDS
+    const int64_t m1 = m0 + n_win;
+    const int64_t na = n0 + (int64_t)blockIdx.x * run;
+    const int64_t nb = na + run < n0 + n_out ? na + run : n0 + n_out;
+    const int64_t q_lo = ((int64_t)half + na * down) / up - (P - 1);      // the first sample the run touches
+    if (X_LDS) {
+        for (int i = threadIdx.x; i < span; i += RESAMPLE_THREADS) {
+            const int64_t m = q_lo + i;
+            xs[i] = m >= m0 && m < m1 ? win[m - m0] : 0.f;
         }
-        o[n] = acc;
+    }
+    if (H_LDS) {
+        for (int i = threadIdx.x; i < up * P; i += RESAMPLE_THREADS) hs[i] = H[i];
+    }
+    if (X_LDS || H_LDS) __syncthreads();
+    for (int64_t n = na + threadIdx.x; n < nb; n += RESAMPLE_THREADS) {
+        const int64_t c = (int64_t)half + n * down;
+        const int64_t q = c / up;
+        const float* h = (H_LDS ? hs : H) + (int)(c - q * up) * P;
+        const float* xq = xs + (int)(q - q_lo);                           // in [P - 1, span) when X_LDS
+        out[n - n0] = resample_output<X_LDS>(h, P, xq, win, q, m0, m1);
     }
 }
 
@@ -180,6 +226,34 @@ static void launch_one(dim3 grid, size_t lds_bytes, hipStream_t s, const float* 
                        r.up, r.down, r.half, r.P, run, span);
 }
 
+template <bool X_LDS, bool H_LDS>
+static void launch_window(dim3 grid, size_t lds_bytes, hipStream_t s, const float* win, int64_t m0, int64_t n_win,
+                          const float* H, float* out, int64_t n0, int64_t n_out, const Ratio& r, int run, int span) {
+    hipLaunchKernelGGL((resample_poly_window_kernel<X_LDS, H_LDS>), grid, dim3(RESAMPLE_THREADS), lds_bytes, s, win, m0, n_win,
+                       H, out, n0, n_out, r.up, r.down, r.half, r.P, run, span);
+}
+
+// The form of a launch, one test for both entries: the outputs per block, and what of the input span and the table a
+// block holds in LDS.
+struct LaunchForm {
+    int run, span;
+    bool x_lds, h_lds;
+    size_t lds_bytes;
+};
+
+static LaunchForm launch_form(const Ratio& r) {
+    // the span of a run: q moves by at most ceil((run - 1) down / up) over it, and every output reaches P - 1 back
+    auto span_of = [&](int run) { return ((int64_t)(run - 1) * r.down + r.up - 1) / r.up + r.P; };
+    LaunchForm f;
+    f.run = RESAMPLE_RUN;
+    if (span_of(f.run) > RESAMPLE_SPAN_LDS) f.run = RESAMPLE_THREADS;
+    f.x_lds = span_of(f.run) <= RESAMPLE_SPAN_LDS;
+    f.h_lds = r.up * r.P <= RESAMPLE_TABLE_LDS;
+    f.span = f.x_lds ? (int)span_of(f.run) : 0;
+    f.lds_bytes = ((size_t)f.span + (f.h_lds ? (size_t)r.up * r.P : 0)) * sizeof(float);
+    return f;
+}
+
 }  // namespace flowse
 
 using namespace flowse;
@@ -228,18 +302,77 @@ int flowse_resample_poly(const float* sig, int B, int L, int up, int down, float
     }
     const float* H = nullptr;
     if (const int rc = get_table(r, s, &H)) return rc;
-    // the span of a run: q moves by at most ceil((run - 1) down / up) over it, and every output reaches P - 1 back
-    auto span_of = [&](int run) { return ((int64_t)(run - 1) * r.down + r.up - 1) / r.up + r.P; };
-    int run = RESAMPLE_RUN;
-    if (span_of(run) > RESAMPLE_SPAN_LDS) run = RESAMPLE_THREADS;
-    const bool x_lds = span_of(run) <= RESAMPLE_SPAN_LDS, h_lds = r.up * r.P <= RESAMPLE_TABLE_LDS;
-    const int span = x_lds ? (int)span_of(run) : 0;
-    const size_t lds_bytes = ((size_t)span + (h_lds ? (size_t)r.up * r.P : 0)) * sizeof(float);
-    const dim3 grid((unsigned)(((int64_t)L_out + run - 1) / run), (unsigned)B);
-    if (x_lds && h_lds) launch_one<true, true>(grid, lds_bytes, s, sig, H, out, L, L_out, r, run, span);
-    else if (x_lds) launch_one<true, false>(grid, lds_bytes, s, sig, H, out, L, L_out, r, run, span);
-    else if (h_lds) launch_one<false, true>(grid, lds_bytes, s, sig, H, out, L, L_out, r, run, span);
-    else launch_one<false, false>(grid, lds_bytes, s, sig, H, out, L, L_out, r, run, span);
+    const LaunchForm f = launch_form(r);
+    const dim3 grid((unsigned)(((int64_t)L_out + f.run - 1) / f.run), (unsigned)B);
+    if (f.x_lds && f.h_lds) launch_one<true, true>(grid, f.lds_bytes, s, sig, H, out, L, L_out, r, f.run, f.span);
+    else if (f.x_lds) launch_one<true, false>(grid, f.lds_bytes, s, sig, H, out, L, L_out, r, f.run, f.span);
+    else if (f.h_lds) launch_one<false, true>(grid, f.lds_bytes, s, sig, H, out, L, L_out, r, f.run, f.span);
+    else launch_one<false, false>(grid, f.lds_bytes, s, sig, H, out, L, L_out, r, f.run, f.span);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+int flowse_resample_poly_window(const float* win, int64_t m0, int64_t n_win, int64_t L_total, int up, int down, float* out,
+                                int64_t n0, int64_t n_out, void* stream) {
+    const char* who = "flowse_resample_poly_window";
+    if (!win || !out || m0 < 0 || n_win < 0 || n0 < 0 || n_out < 0 || L_total < -1) {
+        set_error("%s: null pointer or a negative count (m0 %lld, n_win %lld, L_total %lld, n0 %lld, n_out %lld)", who,
+                  (long long)m0, (long long)n_win, (long long)L_total, (long long)n0, (long long)n_out);
+        return ERR_ARG;
+    }
+    Ratio r;
+    if (const int rc = make_ratio(who, up, down, &r)) return rc;
+    const int64_t reach = (int64_t)1 << 50;        // every product below stays inside 64 bits (up, down <= 2^10)
+    if (m0 > reach || n_win > reach || n0 > reach || L_total > reach || n_out > 0x7fffffff) {
+        set_error("%s: m0 %lld, n_win %lld, n0 %lld and L_total %lld may reach 2^50, n_out %lld 2^31 - 1", who, (long long)m0,
+                  (long long)n_win, (long long)n0, (long long)L_total, (long long)n_out);
+        return ERR_SHAPE;
+    }
+    const int64_t m1 = m0 + n_win, n1 = n0 + n_out;
+    if (L_total >= 0) {
+        const int64_t L_out = (L_total * r.up + r.down - 1) / r.down;
+        if (m1 > L_total || n1 > L_out) {
+            set_error("%s: a signal of %lld samples has %lld outputs at %d / %d; the window [%lld, %lld) or the outputs "
+                      "[%lld, %lld) pass its end", who, (long long)L_total, (long long)L_out, r.up, r.down, (long long)m0,
+                      (long long)m1, (long long)n0, (long long)n1);
+            return ERR_SHAPE;
+        }
+    }
+    if (n_out == 0) return OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (r.up == r.down) {                          // out[n] = x[n]: the slice [n0, n1) of the window
+        if (n0 < m0 || n1 > m1) {
+            set_error("%s: at %d / %d the outputs [%lld, %lld) are those samples; the window holds [%lld, %lld)", who, r.up,
+                      r.down, (long long)n0, (long long)n1, (long long)m0, (long long)m1);
+            return ERR_SHAPE;
+        }
+        FLOWSE_HIP(hipMemcpyAsync(out, win + (n0 - m0), (size_t)n_out * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return OK;
+    }
+    // what the outputs read: x[q(n0) - (P - 1) .. q(n1 - 1)], all P taps of each (a table entry past 2 half is a zero
+    // that still multiplies its sample), clamped to the signal
+    const int64_t q_first = ((int64_t)r.half + n0 * r.down) / r.up, q_last = ((int64_t)r.half + (n1 - 1) * r.down) / r.up;
+    if (L_total < 0 && q_last >= m1) {
+        set_error("%s: output %lld of an open signal reads sample %lld, the window [%lld, %lld) ends before it (has it "
+                  "arrived?)", who, (long long)(n1 - 1), (long long)q_last, (long long)m0, (long long)m1);
+        return ERR_SHAPE;
+    }
+    const int64_t need_lo = q_first - (r.P - 1) > 0 ? q_first - (r.P - 1) : 0;
+    const int64_t need_hi = L_total >= 0 && q_last > L_total - 1 ? L_total - 1 : q_last;       // inclusive
+    if (need_lo < m0 || need_hi >= m1) {
+        set_error("%s: the outputs [%lld, %lld) at %d / %d read the samples [%lld, %lld], the window holds [%lld, %lld)", who,
+                  (long long)n0, (long long)n1, r.up, r.down, (long long)need_lo, (long long)need_hi, (long long)m0,
+                  (long long)m1);
+        return ERR_SHAPE;
+    }
+    const float* H = nullptr;
+    if (const int rc = get_table(r, s, &H)) return rc;
+    const LaunchForm f = launch_form(r);
+    const dim3 grid((unsigned)((n_out + f.run - 1) / f.run));
+    if (f.x_lds && f.h_lds) launch_window<true, true>(grid, f.lds_bytes, s, win, m0, n_win, H, out, n0, n_out, r, f.run, f.span);
+    else if (f.x_lds) launch_window<true, false>(grid, f.lds_bytes, s, win, m0, n_win, H, out, n0, n_out, r, f.run, f.span);
+    else if (f.h_lds) launch_window<false, true>(grid, f.lds_bytes, s, win, m0, n_win, H, out, n0, n_out, r, f.run, f.span);
+    else launch_window<false, false>(grid, f.lds_bytes, s, win, m0, n_win, H, out, n0, n_out, r, f.run, f.span);
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

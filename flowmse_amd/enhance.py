@@ -4,6 +4,7 @@
     python -m flowmse_amd.enhance --input WAV_OR_DIR --output DIR --ckpt MODEL.ckpt [--N 5] [--batch 8]
                                   [--chunk_frames 256] [--overlap_frames 32] [--noise keyed|torch] [--seed S]
                                   [--resample [--output_rate 16000|input]] [--pool [--channels first|all] [--samples D]]
+    ... | python -m flowmse_amd.enhance --live --ckpt MODEL.ckpt [--live_rate HZ [--output_rate input]] | ...
 
 Unlike ``flowmse_amd.evaluate`` it needs no clean files and reports no metrics.  Every recording goes through
 ``flowmse_amd.chunked.enhance_long``: one that fits a single chunk is enhanced exactly as ``evaluate`` would; a longer
@@ -53,7 +54,13 @@ make the first chunk ready.  The output trails the input by at most ``128 chunk_
 256 frames, 0.54 s at 64) plus the sampler's compute time.  Nothing but PCM goes to stdout; messages go to stderr.  The
 file-mode options that make no sense on one open stream (``--input``, ``--output``, ``--pool``, ``--resample``, ``--samples``
 > 1, ``--channels all``, ``--noise torch``) are refused by name.  ``--synthetic 1`` stands in for a checkpoint (synthetic
-weights); stdin is still the signal.
+weights); stdin is still the signal.  ``--live_rate HZ`` (default 16000) names the rate of stdin: the stream is resampled to
+16 kHz on the device as it arrives (``flowmse_amd.resample.StreamResampler``, the file mode's filter sample for sample), and
+with ``--output_rate input`` the enhanced stream is resampled back, as many samples out as came in: ``arecord -t raw -f S16_LE
+-r 48000 | python -m flowmse_amd.enhance --live --live_rate 48000 --output_rate input --ckpt m.ckpt | aplay -t raw -f S16_LE
+-r 48000``.  The bytes are then those of the file mode under ``--resample`` with the same ``--output_rate`` (at ``--batch 1``,
+``--live_norm`` the peak of the resampled recording).  ``--live_block`` and the latency count samples at ``--live_rate``;
+a rate whose ratio to 16 kHz the resampler does not support is refused by name.  ``--resample`` itself stays a file-mode flag.
 """
 import argparse
 import csv
@@ -119,7 +126,7 @@ def build_parser():
                     help="accept input at other sample rates (8 .. 192 kHz; the ratio to 16 kHz at most 1024 after reduction) "
                          "and resample it to 16 kHz on the device before it is enhanced. Without it such files are refused")
     ap.add_argument("--output_rate", choices=("16000", "input"), default="16000",
-                    help="needs --resample. 16000: write the enhanced signal at the network's rate. input: resample it back "
+                    help="needs --resample (or --live --live_rate). 16000: write the enhanced signal at the network's rate. input: resample it back "
                          "on the device to the file's own rate, trimmed to the input's sample count; such a file carries "
                          "nothing above 8 kHz (the network never saw that band)")
     ap.add_argument("--synthetic_rate", type=int, default=SAMPLE_RATE, metavar="HZ",
@@ -138,7 +145,7 @@ def build_parser():
                     help="channel counts of the --synthetic signals, a comma list cycled over them (default 1); channel "
                          "c > 0 is an independent signal at half the level of channel 0")
     ap.add_argument("--live", action="store_true",
-                    help="enhance raw mono 16 kHz PCM from stdin to stdout as it arrives (flowmse_amd.live): the bytes of the "
+                    help="enhance raw mono PCM (16 kHz, or --live_rate) from stdin to stdout as it arrives (flowmse_amd.live): the bytes of the "
                          "chunked file mode at --batch 1, at most 128 chunk_frames + 382 samples behind the input")
     ap.add_argument("--live_pcm", choices=tuple(PCM_FORMATS), default="s16le",
                     help="needs --live. Sample format of stdin and stdout (default s16le; output rounded to nearest, saturated)")
@@ -147,6 +154,10 @@ def build_parser():
     ap.add_argument("--live_norm", type=_live_norm_arg, default="first", metavar="FLOAT|first",
                     help="needs --live. The peak the signal is normalised by: a positive number (the recording's max|y| gives "
                          "the file mode's bytes), or 'first' (default): the peak of the samples that make the first chunk ready")
+    ap.add_argument("--live_rate", type=int, default=SAMPLE_RATE, metavar="HZ",
+                    help="needs --live. Sample rate of stdin (default 16000): the stream is resampled to 16 kHz on the device "
+                         "as it arrives (the ratio to 16 kHz at most 1024 after reduction). stdout is at 16 kHz, or with "
+                         "--output_rate input at this rate, as many samples as were read")
     return ap
 
 
@@ -171,6 +182,10 @@ def _check_live(args, ap):
             ap.error(f"--live does not take {name}: it enhances one mono 16 kHz stream from stdin to stdout with keyed noise")
     if args.live_block < 1:
         ap.error(f"--live_block must be >= 1, got {args.live_block}")
+    try:
+        rational(args.live_rate, SAMPLE_RATE)
+    except ValueError as e:
+        ap.error(f"--live_rate: {e}")
     if not args.synthetic and not args.ckpt:
         ap.error("--live needs --ckpt (or --synthetic 1 for synthetic weights)")
     if args.N < 1:
@@ -187,6 +202,8 @@ def parse_args(argv=None, ap=None):
     args = ap.parse_args(argv)
     if args.live:
         return _check_live(args, ap)
+    if args.live_rate != SAMPLE_RATE:
+        ap.error(f"--live_rate {args.live_rate} needs --live (files at other rates take --resample)")
     if args.output is None:
         ap.error("the following arguments are required: --output")
     if args.synthetic < 0:
@@ -374,9 +391,13 @@ def run_live(args, ap):
         seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(8), "little")
         live = LiveEnhancer(model, norm=args.live_norm, key=utterance_key("live"), seed=seed, chunk_frames=args.chunk_frames,
                             overlap_frames=args.overlap_frames, N=args.N, T_rev=args.reverse_starting_point,
-                            t_eps=args.last_eval_point, odesolver=args.odesolver)
+                            t_eps=args.last_eval_point, odesolver=args.odesolver, input_rate=args.live_rate,
+                            output_rate=args.output_rate)
+        if args.live_rate != SAMPLE_RATE:
+            print(f"live: {args.live_rate} Hz in, {args.live_rate if args.output_rate == 'input' else SAMPLE_RATE} Hz out",
+                  file=sys.stderr)
         print(f"live: keyed noise seed {seed}, {args.live_pcm}, blocks of {args.live_block}, at most "
-              f"{live.latency_samples} samples ({live.latency_samples / SAMPLE_RATE:.2f} s) behind the input", file=sys.stderr)
+              f"{live.latency_samples} samples ({live.latency_samples / args.live_rate:.2f} s) behind the input", file=sys.stderr)
         width, t0 = PCM_FORMATS[args.live_pcm], time.time()
         while True:
             data = stdin.read(args.live_block * width)

@@ -44,9 +44,24 @@ State: the sample buffer (one linear device tensor whose capacity follows the la
 the host waits for the device only in the copy of the emitted samples, with ``as_tensor=True`` never (beyond what one
 ``enhance_long`` sampler call does).
 
-Out of scope: rows of several sessions pooled into one sampler call, ``--streams`` lanes, several GPUs, resampling,
-several channels, noise that is not keyed, and any CPU or oracle path -- the oracle composition is ``enhance_long``'s, and
-this module is pinned to ``enhance_long``.
+Other rates (``input_rate != 16000``; ``flowmse_amd.resample.StreamResampler``, one ``flowse_resample_poly_window`` launch
+per push that finalises an output, bit for bit ``flowse_resample_poly`` on the finished signal).  Pushes go through a
+resampler to 16 kHz; the 16 kHz samples that it makes final feed the path above unchanged, and ``finish()`` appends its
+last outputs, so that the 16 kHz recording has ``ceil(L 16000 / input_rate)`` samples.  With ``output_rate="input"`` the
+emitted 16 kHz samples go through a second resampler back, and the total is trimmed to the input's sample count at
+``finish()``.  **Contract:** the concatenated output is, bit for bit, the waveform of ``enhance.enhance_recording(model, y,
+input_rate, output_rate, chunk_frames, overlap_frames, batch=1, noise_key, noise_seed, ...)`` when ``norm`` equals
+``max|y16|`` of the resampled recording, which is what ``enhance_long`` normalises by.  ``norm="first"`` is the peak of the
+16 kHz samples ``[0, n_0)``.  ``samples_in`` and ``samples_out`` count at the caller's rates.  The schedule gains two steps:
+16 kHz sample ``m`` is final once input sample ``q_in(m) = (half + m down) div up`` has arrived (``stream_plan``), so chunk
+``k`` runs at ``q_in(n_k - 1) + 1`` input samples, and of the ``E`` 16 kHz samples returned ``stream_plan(E, 16000 ->
+input)`` are final at the input rate; ``latency_samples`` takes the worst case over ``k`` (at 48 kHz in and out:
+``3 (128 Tc + 382) + 58`` samples, 58 being the two filters' ``28 + 30``).  With the defaults nothing of this exists: the
+object makes the calls it made before and returns the same bytes.
+
+Out of scope: rows of several sessions pooled into one sampler call, ``--streams`` lanes, several GPUs, time-varying or
+non-rational rates, several channels, noise that is not keyed, and any CPU or oracle path -- the oracle composition is
+``enhance_long``'s, and this module is pinned to ``enhance_long``.
 """
 import numpy as np
 import torch
@@ -54,6 +69,7 @@ import torch
 from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, plan_chunks
 
 HOP, PADC = 128, 255                # hop_length and n_fft // 2 of the released STFT, the only one the kernels cover
+RATE = 16000                        # the network's sample rate
 KEEP = PADC + 1                     # samples kept before the next chunk's first frame centre (module docstring)
 
 
@@ -106,20 +122,47 @@ def pcm_encode(x, fmt):
     return np.clip(v, -32768.0, 32767.0).astype("<i2").tobytes()
 
 
-def latency_samples(Tc=CHUNK_FRAMES):
-    """Worst algorithmic latency ``max_k (n_k - E_{k-1}) = 128 Tc + 382`` samples; it does not depend on the overlap."""
-    return HOP * int(Tc) + 382
+def latency_samples(Tc=CHUNK_FRAMES, input_rate=RATE, output_rate="16000", To=OVERLAP_FRAMES):
+    """Worst algorithmic latency in samples at ``input_rate``.  At 16 kHz: ``max_k (n_k - E_{k-1}) = 128 Tc + 382``; it does
+    not depend on the overlap.  At another rate it follows from the three schedules (module docstring, "Other rates"): chunk
+    ``k`` runs when ``A_k = q_in(n_k - 1) + 1`` input samples have arrived, and what was returned before it covers
+    ``R_k`` input samples, ``stream_plan(E_{k-1}, 16000 -> input)`` under ``output_rate="input"`` and
+    ``E_{k-1} input_rate div 16000`` at 16 kHz output; the value is ``max_k (A_k - R_k)``.  Both terms are floors over the
+    reduced ``up`` of the input ratio, so ``k = 0 .. up`` covers every case."""
+    Tc = int(Tc)
+    if int(input_rate) == RATE:
+        return HOP * Tc + 382
+    from flowmse_amd.resample import rational, stream_plan
+    _, hop, _ = plan_chunks(1, Tc, To)
+    up, down = rational(input_rate, RATE)
+    half = 10 * max(up, down)
+    worst = 0
+    for k in range(up + 1):
+        arrived = (half + (_ready_at(k, Tc, hop) - 1) * down) // up + 1
+        e = HOP * k * hop - PADC if k else 0
+        returned = stream_plan(e, down, up) if output_rate == "input" else e * down // up
+        worst = max(worst, arrived - returned)
+    return worst
 
 
 class LiveEnhancer:
     """One recording, enhanced as it arrives (module docstring).  ``model``: a HIP-backed ``VFModel`` on ``device`` (default:
     the current one); ``key`` / ``seed``: the keyed noise stream, as ``enhance_long``'s ``noise_key`` / ``noise_seed``;
-    ``norm``: a positive float or ``"first"``.  The precision is the model's (``model.dnn.set_precision``)."""
+    ``norm``: a positive float or ``"first"``.  The precision is the model's (``model.dnn.set_precision``).  ``input_rate``:
+    the sample rate of what is pushed (default 16000; any ratio ``resample.rational`` admits); ``output_rate``: ``"16000"``
+    returns the network's rate, ``"input"`` the input's (module docstring, "Other rates")."""
 
     def __init__(self, model, *, norm, key, seed=0, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES, N=5, T_rev=1.0,
-                 t_eps=0.03, odesolver="euler", device=None):
+                 t_eps=0.03, odesolver="euler", device=None, input_rate=RATE, output_rate="16000"):
         _, self.hop, _ = plan_chunks(1, chunk_frames, overlap_frames)
         self.Tc, self.To = int(chunk_frames), int(overlap_frames)
+        self.input_rate = int(input_rate)
+        if output_rate not in ("16000", "input"):
+            raise ValueError(f"LiveEnhancer: output_rate is '16000' or 'input', got {output_rate!r}")
+        self.output_rate = output_rate
+        if self.input_rate != RATE:
+            from flowmse_amd.resample import rational
+            rational(self.input_rate, RATE)                       # an unsupported ratio is refused here, by name
         if key is None:
             raise ValueError("LiveEnhancer: key is required (keyed noise only; util.noise.utterance_key makes one)")
         if isinstance(norm, str):
@@ -149,24 +192,36 @@ class LiveEnhancer:
         with torch.cuda.device(self.device):
             dnn.reserve(1, 256, self.Tc)
         self._buf = torch.empty(0, dtype=torch.float32, device=self.device)
+        self._rs_in = self._rs_out = None                   # input_rate != 16000: the resamplers around the 16 kHz path
+        if self.input_rate != RATE:
+            from flowmse_amd.resample import StreamResampler
+            self._rs_in = StreamResampler(self.input_rate, RATE, self.device)
+            if output_rate == "input":
+                self._rs_out = StreamResampler(RATE, self.input_rate, self.device)
         self.reset(key)
 
     # ---- public state -----------------------------------------------------------------------------------------
     @property
     def latency_samples(self):
-        return latency_samples(self.Tc)
+        return latency_samples(self.Tc, self.input_rate, self.output_rate, self.To)
 
     def state_bytes(self):
-        """Device bytes this object holds between pushes: the sample buffer (its capacity) and the previous chunks.  No
-        output is pending between calls.  The model's workspace is the model's (``reserve(1, 256, Tc)``)."""
+        """Device bytes this object holds between pushes: the sample buffer (its capacity), the previous chunks and the
+        buffers of the resamplers, if any.  No output is pending between calls.  The model's workspace is the model's
+        (``reserve(1, 256, Tc)``)."""
         kept = [c for c in (self._prev, self._prev2) if c is not None]
-        return self._buf.numel() * 4 + sum(c.numel() * 8 for c in kept)
+        rs = sum(r.state_bytes() for r in (self._rs_in, self._rs_out) if r is not None)
+        return self._buf.numel() * 4 + sum(c.numel() * 8 for c in kept) + rs
 
     def reset(self, key=None):
         """Forget the recording (the buffer keeps its capacity); ``key``: the next recording's, default the same one."""
         if key is not None:
             self.key = int(key)
-        self.samples_in = self.samples_out = 0
+        self.samples_in = self.samples_out = 0              # at the caller's rates
+        self._in16 = self._out16 = 0                        # at 16 kHz: what the chunk schedule counts
+        for r in (self._rs_in, self._rs_out):
+            if r is not None:
+                r.reset()
         self._s0 = self._n = 0                              # the buffer holds samples [s0, s0 + n) of the recording
         self._k = 0                                         # next chunk to sample
         self._prev = self._prev2 = None
@@ -179,10 +234,14 @@ class LiveEnhancer:
         samples that became final: float32 numpy (possibly empty), or with ``as_tensor`` a 1-D device tensor."""
         if self._finished:
             raise RuntimeError("LiveEnhancer.push after finish(): call reset() to start another recording")
+        if self._rs_in is not None:                         # the 16 kHz samples this push made final feed the path below
+            with torch.cuda.device(self.device):
+                samples = self._rs_in.push(samples, as_tensor=True)
+            self.samples_in = self._rs_in.samples_in
         self._append(samples)
         out = []
         with torch.cuda.device(self.device):
-            while self.samples_in >= _ready_at(self._k, self.Tc, self.hop):
+            while self._in16 >= _ready_at(self._k, self.Tc, self.hop):
                 out.append(self._chunk(self._k, None))
         return self._deliver(out, as_tensor)
 
@@ -190,10 +249,17 @@ class LiveEnhancer:
         """The recording has ended: sample what was waiting and return the remaining samples up to ``L = samples_in``."""
         if self._finished:
             raise RuntimeError("LiveEnhancer.finish called twice: call reset() to start another recording")
-        L = self.samples_in
+        if self._rs_in is not None:                         # the 16 kHz recording ends at out_len(samples_in)
+            from flowmse_amd.resample import stream_plan
+            L = stream_plan(self.samples_in, self._rs_in.up, self._rs_in.down, finished=True)
+        else:
+            L = self._in16
         if L <= PADC:
             raise ValueError(f"LiveEnhancer.finish: a recording needs more than {PADC} samples (n_fft // 2 of the centred "
                              f"STFT), got {L}")
+        if self._rs_in is not None:
+            with torch.cuda.device(self.device):
+                self._append(self._rs_in.finish(as_tensor=True))
         K = plan_chunks(L // HOP + 1, self.Tc, self.To)[0]
         out = []
         with torch.cuda.device(self.device):
@@ -206,7 +272,7 @@ class LiveEnhancer:
         self._prev = self._prev2 = None
         self._s0 += self._n
         self._n = 0
-        return self._deliver(out, as_tensor)
+        return self._deliver(out, as_tensor, last=True)
 
     # ---- internals --------------------------------------------------------------------------------------------
     def _append(self, samples):
@@ -228,13 +294,13 @@ class LiveEnhancer:
             self._buf = grown
         self._buf[self._n:self._n + n] = samples.to(self.device)
         self._n += n
-        self.samples_in += n
+        self._in16 += n
 
     def _normalised(self, lo, hi):
         """Samples [lo, hi) of the recording divided by ``norm`` as ``enhance_long`` divides them: on the device, one
         elementwise torch division by the Python float."""
         if self.norm is None:                               # norm="first": the peak of [0, n_0), or of all there is
-            n0 = min(_ready_at(0, self.Tc, self.hop), self.samples_in)
+            n0 = min(_ready_at(0, self.Tc, self.hop), self._in16)
             peak = self._buf[:n0].abs().max().item()
             self.norm = peak if peak > 0.0 else 1.0
         return self._buf[lo - self._s0:hi - self._s0] / self.norm
@@ -272,10 +338,10 @@ class LiveEnhancer:
         if L is not None:                                   # the right reflection may read one sample before the first frame
             lo = max(min(lo, L - KEEP), self._s0)
         cur = self._sample(self._stft(lo, hi, k * hop, Tc, -1 if L is None else L), k * hop)
-        e0 = self.samples_out
+        e0 = self._out16
         e1 = L if last else HOP * (k + 1) * hop - PADC
         out = self._istft(self._prev2, self._prev, cur, k, Tc, hop, last, L if last else 0, e0, e1)
-        self.samples_out = e1
+        self._out16 = e1
         self._prev2, self._prev = (self._prev if self._keep_two else None), cur
         self._k = k + 1
         self._drop(max(HOP * (k + 1) * hop - KEEP, 0))
@@ -287,7 +353,7 @@ class LiveEnhancer:
         Tpad = -(-(L // HOP + 1) // 64) * 64
         cur = self._sample(self._stft(0, L, 0, Tpad, L), None)
         out = self._istft(None, None, cur, 0, Tpad, Tpad, True, L, 0, L)
-        self.samples_out = L
+        self._out16 = L
         self._k = 1
         return out
 
@@ -301,8 +367,27 @@ class LiveEnhancer:
         self._s0 += cut
         self._n -= cut
 
-    def _deliver(self, out, as_tensor):
+    def _deliver(self, out, as_tensor, last=False):
+        if self._rs_in is None:                             # 16 kHz in and out: the caller's counters are the schedule's
+            self.samples_in, self.samples_out = self._in16, self._out16
+        elif self._rs_out is None:
+            self.samples_out = self._out16
+        else:
+            out = [self._back(out, last)]
         if not out:
             return torch.empty(0, dtype=torch.float32, device=self.device) if as_tensor else np.empty(0, dtype=np.float32)
         x = out[0] if len(out) == 1 else torch.cat(out)
         return x if as_tensor else x.cpu().numpy()
+
+    def _back(self, out, last):
+        """``output_rate="input"``: the emitted 16 kHz samples through the second resampler; at the end its remaining
+        outputs, the total trimmed to the input's sample count as ``enhance_recording`` trims.  Before the end the count
+        returned stays below ``samples_in`` (an output at the input rate is final later than the input sample under it)."""
+        with torch.cuda.device(self.device):
+            parts = [self._rs_out.push(out[0] if len(out) == 1 else torch.cat(out), as_tensor=True)] if out else []
+            if last:
+                parts.append(self._rs_out.finish(as_tensor=True))
+        x = torch.cat(parts) if parts else torch.empty(0, dtype=torch.float32, device=self.device)
+        x = x[:max(self.samples_in - self.samples_out, 0)]
+        self.samples_out += x.numel()
+        return x

@@ -14,6 +14,10 @@ both ways.  The taps come from the library (``flowse_resample_taps``, host only)
 ``flowse_resample_poly`` launch (csrc/resample.hip), and ``resample_reference`` is the float64 restatement the tests hold
 against scipy -- nothing here calls scipy.  ``n down`` passes 2^31 five minutes into a 44.1 kHz recording: every index is
 a Python int or an int64.
+
+A signal that is still arriving (``flowmse_amd.live`` at 44.1 or 48 kHz) goes through ``StreamResampler``: the same
+outputs from a window of the signal, one ``flowse_resample_poly_window`` launch per push; ``stream_plan`` says how many
+outputs are final after ``n`` samples.
 """
 import ctypes as C
 import math
@@ -110,3 +114,146 @@ def resample(sig, sr_in, sr_out):
         _lib.check(_lib.lib.flowse_resample_poly(_lib.ptr(sig), B, L, up, down, _lib.ptr(out), out.size(1),
                                                  _lib.current_stream()))
     return out
+
+
+# ---- a signal that is still arriving ---------------------------------------------------------------------------
+def _geometry(up, down):
+    """``(up, down, half, P)`` of a pair, reduced: ``half = 10 max(up, down)``, ``P = ceil((2 half + 1) / up)``."""
+    up, down = rational(int(down), int(up))                        # reduces and checks: rational(sr_in, sr_out)
+    half = 10 * max(up, down)
+    return up, down, half, (2 * half + up) // up
+
+
+def stream_plan(n_in, up, down, finished=False):
+    """How many outputs are final after ``n_in`` samples of a signal.  Output ``n`` reads the samples up to
+    ``q(n) = (half + n down) div up``, so while the signal is open it is final iff ``q(n) <= n_in - 1``: the count is
+    ``max(0, (n_in up - 1 - half) div down + 1)``.  ``finished``: the signal has ended at ``n_in`` -- ``out_len(n_in)``.
+    Equal rates pass samples through: ``n_in``.  Host arithmetic on Python ints."""
+    n_in = int(n_in)
+    if n_in < 0:
+        raise ValueError(f"stream_plan: n_in must be >= 0, got {n_in}")
+    up, down, half, _ = _geometry(up, down)
+    if up == down:
+        return n_in
+    if finished:
+        return out_len(n_in, up, down)
+    return max(0, (n_in * up - 1 - half) // down + 1)
+
+
+class StreamResampler:
+    """``resample`` for ONE row that arrives in pushes of any sizes (empty ones and single samples included).
+    **Contract:** the concatenation of everything ``push`` and ``finish`` returned equals
+    ``resample(x[None], sr_in, sr_out)[0]`` for the finished signal ``x``, whatever the push sizes.
+
+    On a HIP device the equality is bit for bit: every push that finalises at least one output (``stream_plan``) makes one
+    ``flowse_resample_poly_window`` launch on the current stream, whose outputs are those of ``flowse_resample_poly`` by
+    construction, and nothing here waits for the device (``as_tensor=True`` returns device tensors; the default copies the
+    outputs to numpy).  On the CPU the outputs are ``resample_reference(..., n0, n1, m0)`` rounded to float32: within one
+    float32 ulp of ``resample``'s CPU path (the float64 sums are blocked differently), not bit for bit.
+
+    ``device``: where the state lives and the outputs are made; default: the device of the first pushed samples (numpy
+    arrays and CPU tensors: the CPU).  State: one linear float32 tensor.  After a push the samples before
+    ``q(next output) - (P - 1)`` are dropped; the next output is not final, ``q(next output) >= samples_in``, so at most
+    ``P - 1`` samples stay, and the capacity is ``P - 1`` plus the largest push: ``state_bytes()`` follows the largest
+    push and does not grow with the recording.  Equal rates pass the samples through untouched.  The first
+    call for a ratio on a device uploads the ratio's table: make it outside stream capture."""
+
+    def __init__(self, sr_in, sr_out, device=None):
+        self.sr_in, self.sr_out = int(sr_in), int(sr_out)
+        self.up, self.down = rational(sr_in, sr_out)
+        _, _, self.half, self.P = _geometry(self.up, self.down)
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._buf = None
+        self.reset()
+
+    def state_bytes(self):
+        """Bytes of samples this object holds between pushes (the buffer's capacity)."""
+        return 0 if self._buf is None else self._buf.numel() * 4
+
+    def reset(self):
+        """Forget the signal; the buffer keeps its capacity."""
+        self.samples_in = self.samples_out = 0
+        self._m0 = self._n = 0                                     # the buffer holds samples [m0, m0 + n) of the signal
+        self._finished = False
+
+    def push(self, samples, as_tensor=False):
+        """Append ``samples`` (float32, 1-D or [1, n], n >= 0: numpy, CPU tensor or device tensor) and return the outputs
+        that became final: float32 numpy (possibly empty), or with ``as_tensor`` a 1-D tensor on ``device``."""
+        if self._finished:
+            raise RuntimeError("StreamResampler.push after finish(): call reset() to start another signal")
+        x = self._take(samples)
+        if self.up == self.down:
+            self.samples_in += x.numel()
+            self.samples_out += x.numel()
+            return x if as_tensor else x.cpu().numpy()
+        self._append(x)
+        out = self._emit(stream_plan(self.samples_in, self.up, self.down), -1)
+        self._drop(max((self.half + self.samples_out * self.down) // self.up - (self.P - 1), 0))
+        return out if as_tensor else out.cpu().numpy()
+
+    def finish(self, as_tensor=False):
+        """The signal has ended at ``samples_in``: return the remaining outputs, up to ``out_len(samples_in)``."""
+        if self._finished:
+            raise RuntimeError("StreamResampler.finish called twice: call reset() to start another signal")
+        if self.device is None:
+            self.device = torch.device("cpu")
+        out = self._emit(stream_plan(self.samples_in, self.up, self.down, finished=True), self.samples_in)
+        self._finished = True
+        self._m0 += self._n
+        self._n = 0
+        return out if as_tensor else out.cpu().numpy()
+
+    # ---- internals --------------------------------------------------------------------------------------------
+    def _take(self, samples):
+        if isinstance(samples, np.ndarray):
+            samples = torch.from_numpy(np.ascontiguousarray(samples))
+        if not torch.is_tensor(samples) or samples.dtype != torch.float32:
+            raise TypeError("StreamResampler.push takes float32 samples (numpy array or tensor), got "
+                            f"{getattr(samples, 'dtype', type(samples).__name__)}")
+        if samples.dim() == 2 and samples.size(0) == 1:
+            samples = samples[0]
+        if samples.dim() != 1:
+            raise ValueError(f"StreamResampler.push takes one row, 1-D or [1, n], got {tuple(samples.shape)}")
+        if self.device is None:
+            self.device = samples.device
+        return samples.to(self.device)
+
+    def _append(self, x):
+        n = x.numel()
+        if n == 0:
+            return
+        if self._buf is None or self._n + n > self._buf.numel():   # grow once per new largest push; contents stay in front
+            grown = torch.empty(max(self._n, self.P - 1) + n, dtype=torch.float32, device=self.device)
+            if self._n:
+                grown[:self._n] = self._buf[:self._n]
+            self._buf = grown
+        self._buf[self._n:self._n + n] = x
+        self._n += n
+        self.samples_in += n
+
+    def _emit(self, n1, L_total):
+        """The outputs [samples_out, n1) from the buffer; ``L_total``: -1 while the signal is open."""
+        n0 = self.samples_out
+        if n1 <= n0:
+            return torch.empty(0, dtype=torch.float32, device=self.device)
+        self.samples_out = n1
+        if self.device.type != "cuda":
+            ref = resample_reference(self._buf[:self._n].numpy(), self.sr_in, self.sr_out, n0, n1, self._m0)
+            return torch.from_numpy(ref.astype(np.float32))
+        out = torch.empty(n1 - n0, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.flowse_resample_poly_window(_lib.ptr(self._buf), self._m0, self._n, L_total, self.up, self.down,
+                                                            _lib.ptr(out), n0, n1 - n0, _lib.current_stream()))
+        return out
+
+    def _drop(self, upto):
+        """Forget the samples before ``upto``: the rest moves to the front of the same buffer."""
+        cut = min(upto, self._m0 + self._n) - self._m0
+        if cut <= 0:
+            return
+        rest = self._buf[cut:self._n].clone()
+        self._buf[:rest.numel()] = rest
+        self._m0 += cut
+        self._n -= cut

@@ -406,10 +406,28 @@ int flowse_istft_decompress_ensemble(const void* chunks_c64, int S, int D, int K
  * call allocates; later calls on other streams wait for the upload by event).  Enqueues only, no host synchronisation --
  * but for the first call of a ratio on a device: it designs the taps on the host, allocates, and copies the table from
  * pageable memory, which the runtime may wait for, and it records an event, so make it outside stream capture (one short
- * call per ratio warms the cache).  Every later call for that ratio may be captured. */
+ * call per ratio warms the cache).  Every later call for that ratio may be captured.
+ * flowse_resample_poly_window: the outputs [n0, n0 + n_out) of ONE row from a window of it, for a signal that is still
+ * arriving or too long to hold: win (device, float32 [n_win]) holds the samples [m0, m0 + n_win), out (device, float32
+ * [n_out]) receives out[n0 ..], each bit for bit what flowse_resample_poly writes at that index for the whole signal (one
+ * tap loop serves both kernels).  L_total is the row's length once it is known (the signal is closed: x is zero at and
+ * past L_total) and -1 while it is open.  m0, n0, c, q and every sample index are 64-bit on the host and on the device.
+ * Checked before anything is launched, with the numbers in flowse_last_error(), the output untouched:
+ *   a null pointer, a negative m0, n_win, n0 or n_out, L_total < -1 -> FLOWSE_ERR_ARG; the ratio as in every entry;
+ *   m0, n_win, n0 or L_total > 2^50, n_out > 2^31 - 1 -> FLOWSE_ERR_SHAPE;
+ *   closed: m0 + n_win > L_total or n0 + n_out > ceil(L_total up / down) -> FLOWSE_ERR_SHAPE;
+ *   open: an output with q >= m0 + n_win (it reads a sample that has not arrived) -> FLOWSE_ERR_SHAPE;
+ *   the samples the outputs read, [q(n0) - (P - 1), q(n0 + n_out - 1)] clamped to the signal -- all P taps of every
+ *   output, the zero table entries past 2 half included -- not inside the window -> FLOWSE_ERR_SHAPE.
+ * n_out == 0 returns FLOWSE_OK and launches nothing.  up == down copies the samples [n0, n0 + n_out) out of the window
+ * (which must hold them).  One launch, in the same four forms and under the same test as flowse_resample_poly; the table
+ * is that call's: the first call for a ratio on a device (through either entry) uploads it and must not be made under
+ * stream capture, every later one enqueues only. */
 int flowse_resample_num_taps(int up, int down);
 int flowse_resample_taps(int up, int down, double* taps, int cap);
 int flowse_resample_poly(const float* sig, int B, int L, int up, int down, float* out, int L_out, void* stream);
+int flowse_resample_poly_window(const float* win, int64_t m0, int64_t n_win, int64_t L_total, int up, int down, float* out,
+                                int64_t n0, int64_t n_out, void* stream);
 
 /* ---- evaluation metrics on the device: ESTOI and SI-SDR / SI-SIR / SI-SAR (opt-in: evaluate --metrics device) ----
  * ESTOI is DEFINED here, step by step after pystoi.stoi(x, y, 16000, extended=True) (pystoi 0.3 / 0.4); the package is
