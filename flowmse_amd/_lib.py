@@ -19,6 +19,7 @@ FLOWSE_MAX_LEVELS = 8
 FLOWSE_MAX_ATTN = 4
 FLOWSE_MAX_LANES = 4
 FLOWSE_MAX_SPEC_ROWS = 64
+FLOWSE_MAX_WINDOW_ROWS = 16
 FLOWSE_MAX_DRAWS = 64
 FLOWSE_BYTES_WEIGHTS, FLOWSE_BYTES_OWNED = 0, 1
 FLOWSE_LOSS_MSE, FLOWSE_LOSS_MAE = 0, 1
@@ -36,6 +37,17 @@ class flowse_config(C.Structure):
 
 class flowse_spec_row(C.Structure):
     _fields_ = [("sig", C.c_void_p), ("L", C.c_int32), ("frame0", C.c_int32), ("scale_in", C.c_float)]
+
+
+class flowse_window_row(C.Structure):
+    _fields_ = [("buf", C.c_void_p), ("s0", C.c_int64), ("n", C.c_int64), ("frame0", C.c_int64), ("L_total", C.c_int64),
+                ("scale_in", C.c_float)]
+
+
+class flowse_window_out(C.Structure):
+    _fields_ = [("prev2_c64", C.c_void_p), ("prev_c64", C.c_void_p), ("cur_c64", C.c_void_p), ("out", C.c_void_p),
+                ("k", C.c_int64), ("L", C.c_int64), ("e0", C.c_int64), ("n_out", C.c_int64), ("last", C.c_int32),
+                ("scale_out", C.c_float)]
 
 
 if not os.path.exists(LIB_PATH):
@@ -89,6 +101,8 @@ SIGNATURES = {
     "flowse_istft_decompress_ensemble": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _i64, _f, _f, _fp, _i, _f, _fp, _vp]),
     "flowse_stft_compress_window": (_i, [_fp, _i64, _i64, _f, _i64, _i, _i64, _vp, _f, _f, _vp]),
     "flowse_istft_decompress_window": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i64, _f, _f, _fp, _i64, _i64, _f, _vp]),
+    "flowse_stft_compress_window_rows": (_i, [C.POINTER(flowse_window_row), _i, _i, _vp, _f, _f, _vp]),
+    "flowse_istft_decompress_window_rows": (_i, [C.POINTER(flowse_window_out), _i, _i, _i, _f, _f, _vp]),
     "flowse_resample_num_taps": (_i, [_i, _i]),
     "flowse_resample_taps": (_i, [_i, _i, C.POINTER(_d), _i]),
     "flowse_resample_poly": (_i, [_fp, _i, _i, _i, _i, _fp, _i, _vp]),

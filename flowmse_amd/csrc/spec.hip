@@ -7,6 +7,7 @@
 // (SURVEY.md section 8(f), rank 1).  O(n_fft^2) direct DFTs with an exact 510-entry twiddle table: 0.13 MFLOP per
 // frame -- microseconds per utterance, no FFT library, no intermediate tensors.
 #include <cmath>
+#include <cstdio>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -310,6 +311,51 @@ __global__ __launch_bounds__(256) void stft_compress_window_kernel(const float* 
                exponent, s0);
 }
 
+// The same two kernels for the rows of SEVERAL live sessions (flowmse_amd.livepool): the descriptors travel by value in the
+// argument block, as SpecRowTable does, already checked and reduced on the host to what the device code reads.
+struct WindowInRow {
+    const float* buf;
+    int64_t s0, L, frame0, T;                           // L, T: INT64_MAX / 4 while the recording is open
+    float scale_in;
+};
+struct WindowInTable {
+    WindowInRow row[FLOWSE_MAX_WINDOW_ROWS];
+};
+struct WindowOutRow {
+    WindowRows rows;
+    int64_t T, base, t_lo, t_hi;                        // WindowFrames' own, per row
+    float* out;
+    int64_t e0, n_out;
+    int Kw;
+    float scale_out;
+};
+struct WindowOutTable {
+    WindowOutRow row[FLOWSE_MAX_WINDOW_ROWS];
+};
+static_assert(sizeof(WindowInRow) == 48 && sizeof(WindowOutRow) == 88 && sizeof(WindowInTable) <= 2048 &&
+              sizeof(WindowOutTable) <= 2048, "the tables must fit the argument block");
+
+// grid (Tw, R), 256 threads = 256 bins: row r = frames [frame0_r, frame0_r + Tw) from the window of session r
+__global__ __launch_bounds__(256) void stft_compress_window_rows_kernel(const WindowInTable rows,
+                                                                        const float* __restrict__ tab,
+                                                                        float2* __restrict__ out, int Tw, float factor,
+                                                                        float exponent) {
+    const WindowInRow& w = rows.row[blockIdx.y];
+    stft_frame(w.buf, w.L, w.scale_in, tab, out + ((int64_t)blockIdx.y * NBIN + threadIdx.x) * Tw + blockIdx.x,
+               w.frame0 + blockIdx.x, w.T, factor, exponent, w.s0);
+}
+
+// grid (largest block count of any row, R), 256 threads: a block past its row's range returns without storing
+__global__ __launch_bounds__(256) void istft_decompress_window_rows_kernel(const WindowOutTable rows,
+                                                                           const float* __restrict__ tab, int Tc, int hop,
+                                                                           float factor, float exponent) {
+    const WindowOutRow& w = rows.row[blockIdx.y];
+    const int64_t b0 = w.e0 / HOP;
+    if ((int64_t)blockIdx.x > (w.e0 + w.n_out - 1) / HOP - b0) return;
+    const WindowFrames frames{w.rows, w.T, w.base, w.t_lo, w.t_hi, w.Kw, Tc, hop, factor, exponent};
+    istft_gather(frames, tab, w.out, (b0 + blockIdx.x) * HOP, w.e0, w.e0 + w.n_out, w.scale_out);
+}
+
 // Per-frame agreement tracks of an ensemble: grid (ceil(Tg / 64), S), 256 threads = 64 frames (lanes along t, the
 // contiguous axis of a row) x 4 quarters of the bins.  tracks [S][2][Tg]: dev[t] = sum_f sum_d |Z_d - M|^2 / (D - 1), then
 // pow[t] = sum_f |M|^2, with M the mean the iSTFT kernel transforms (the same mean_value).  Two passes over the draws per
@@ -544,18 +590,14 @@ int flowse_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, void* 
 // samples [s0, s0 + n); the output samples [e0, e0 + n_out) from chunks k-2, k-1, k
 constexpr int64_t WINDOW_MAX = (int64_t)1 << 40;        // frames and chunk indices: every product below stays in 64 bits
 
-int flowse_stft_compress_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t frame0, int Tc,
-                                int64_t L_total, void* out_c64, float factor, float exponent, void* stream) {
-    if (!buf || !out_c64) {
-        set_error("flowse_stft_compress_window: null argument");
-        return ERR_ARG;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// The shape checks of one STFT window, shared by the single entry and the row table (`who` names the entry, and the row, in
+// the error text).  On success *T is the frame count the kernel takes: L_total / 128 + 1, or INT64_MAX / 4 while open.
+static int check_stft_window(const char* who, int64_t s0, int64_t n, int64_t frame0, int Tc, int64_t L_total, int64_t* T_out) {
     const bool closed = L_total >= 0;
     if (s0 < 0 || n < 1 || s0 > WINDOW_MAX * HOP || n > WINDOW_MAX * HOP || frame0 < 0 || frame0 > WINDOW_MAX || Tc < 1 ||
         Tc > (1 << 23) || L_total < -1 || (closed && (L_total <= PADC || s0 + n > L_total))) {
-        set_error("stft window: need s0 >= 0, n >= 1, 0 <= frame0 <= 2^40, 1 <= Tc <= 2^23 and L_total = -1 or 255 < "
-                  "s0 + n <= L_total (got s0=%lld n=%lld frame0=%lld Tc=%d L_total=%lld)", (long long)s0, (long long)n,
+        set_error("%s: need s0 >= 0, n >= 1, 0 <= frame0 <= 2^40, 1 <= Tc <= 2^23 and L_total = -1 or 255 < "
+                  "s0 + n <= L_total (got s0=%lld n=%lld frame0=%lld Tc=%d L_total=%lld)", who, (long long)s0, (long long)n,
                   (long long)frame0, Tc, (long long)L_total);
         return ERR_SHAPE;
     }
@@ -565,8 +607,8 @@ int flowse_stft_compress_window(const float* buf, int64_t s0, int64_t n, float s
     if (t_end > frame0) {
         const int64_t j_lo = frame0 * HOP - PADC, j_hi = (t_end - 1) * HOP + (NFFT - 1 - PADC);   // before reflection
         if (j_lo < 0 && s0 != 0) {
-            set_error("stft window: frame %lld reflects about sample 0 and needs samples [0, %lld], the window starts at "
-                      "s0=%lld", (long long)frame0, (long long)-j_lo, (long long)s0);
+            set_error("%s: frame %lld reflects about sample 0 and needs samples [0, %lld], the window starts at "
+                      "s0=%lld", who, (long long)frame0, (long long)-j_lo, (long long)s0);
             return ERR_SHAPE;
         }
         int64_t need_lo = j_lo < 0 ? 0 : j_lo, need_hi = j_hi;
@@ -577,40 +619,50 @@ int flowse_stft_compress_window(const float* buf, int64_t s0, int64_t n, float s
             need_hi = L_total - 1;
         }
         if (need_lo < s0 || need_hi >= s0 + n) {
-            set_error("stft window: frames [%lld, %lld) need samples [%lld, %lld], the window holds [%lld, %lld) "
-                      "(L_total=%lld)", (long long)frame0, (long long)t_end, (long long)need_lo, (long long)need_hi,
+            set_error("%s: frames [%lld, %lld) need samples [%lld, %lld], the window holds [%lld, %lld) "
+                      "(L_total=%lld)", who, (long long)frame0, (long long)t_end, (long long)need_lo, (long long)need_hi,
                       (long long)s0, (long long)(s0 + n), (long long)L_total);
             return ERR_SHAPE;
         }
     }
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
+    *T_out = T;
+    return OK;
+}
+
+int flowse_stft_compress_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t frame0, int Tc,
+                                int64_t L_total, void* out_c64, float factor, float exponent, void* stream) {
+    if (!buf || !out_c64) {
+        set_error("flowse_stft_compress_window: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int64_t T = 0;
+    int rc = check_stft_window("stft window", s0, n, frame0, Tc, L_total, &T);
     if (rc != OK) return rc;
-    hipLaunchKernelGGL(stft_compress_window_kernel, dim3(Tc), dim3(256), 0, s, buf, s0, closed ? L_total : INT64_MAX / 4,
+    float* tab = nullptr;
+    rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(stft_compress_window_kernel, dim3(Tc), dim3(256), 0, s, buf, s0, L_total >= 0 ? L_total : INT64_MAX / 4,
                        scale_in, tab, reinterpret_cast<float2*>(out_c64), frame0, T, Tc, factor, exponent);
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }
 
-int flowse_istft_decompress_window(const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k, int Tc,
-                                   int hop, int last, int64_t L, float factor, float exponent, float* out, int64_t e0,
-                                   int64_t n_out, float scale_out, void* stream) {
-    if (!cur_c64 || !out) {
-        set_error("flowse_istft_decompress_window: null argument");
-        return ERR_ARG;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// The shape checks of one output range, shared likewise; on success *fr is what the kernel reads for it.
+static int check_istft_window(const char* who, const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k,
+                              int Tc, int hop, int last, int64_t L, float factor, float exponent, int64_t e0, int64_t n_out,
+                              WindowFrames* fr) {
     if (k < 0 || k > WINDOW_MAX || Tc < 1 || Tc > (1 << 23) || hop < 1 || hop > Tc || 2 * (int64_t)hop < Tc || e0 < 0 ||
         n_out < 1 || n_out > ((int64_t)1 << 30) || e0 > WINDOW_MAX * HOP || factor == 0.f) {
-        set_error("istft window: need 0 <= k <= 2^40, 1 <= hop <= Tc <= 2 hop, Tc <= 2^23, e0 >= 0, 1 <= n_out <= 2^30 and "
-                  "factor != 0 (got k=%lld Tc=%d hop=%d e0=%lld n_out=%lld)", (long long)k, Tc, hop, (long long)e0,
+        set_error("%s: need 0 <= k <= 2^40, 1 <= hop <= Tc <= 2 hop, Tc <= 2^23, e0 >= 0, 1 <= n_out <= 2^30 and "
+                  "factor != 0 (got k=%lld Tc=%d hop=%d e0=%lld n_out=%lld)", who, (long long)k, Tc, hop, (long long)e0,
                   (long long)n_out);
         return ERR_SHAPE;
     }
     const int64_t Tg = k * hop + Tc, To = Tc - hop;
     if (last && (e0 + n_out > L || L > (Tg - 1) * HOP + NFFT - PADC)) {
-        set_error("istft window: after the last chunk need e0 + n_out <= L <= 128 (Tg - 1) + 255 (got e0=%lld n_out=%lld "
-                  "L=%lld Tg=%lld)", (long long)e0, (long long)n_out, (long long)L, (long long)Tg);
+        set_error("%s: after the last chunk need e0 + n_out <= L <= 128 (Tg - 1) + 255 (got e0=%lld n_out=%lld "
+                  "L=%lld Tg=%lld)", who, (long long)e0, (long long)n_out, (long long)L, (long long)Tg);
         return ERR_SHAPE;
     }
     // the frames over the samples [e0, e0 + n_out): the index range of istft_gather for one sample, over all of them
@@ -623,33 +675,128 @@ int flowse_istft_decompress_window(const void* prev2_c64, const void* prev_c64, 
     if (c_lo > 0 && t_first - c_lo * hop < To) c_lo -= 1;
     const int64_t m = k >= 2 ? k - 2 : 0;
     if (c_hi > k || c_lo < m || (c_lo <= k - 1 && !prev_c64) || (c_lo <= k - 2 && !prev2_c64)) {
-        set_error("istft window: samples [%lld, %lld) lie under frames [%lld, %lld], which the seam rule takes from chunks "
-                  "%lld..%lld; given are chunk k=%lld%s%s%s", (long long)e0, (long long)(e0 + n_out), (long long)t_first,
+        set_error("%s: samples [%lld, %lld) lie under frames [%lld, %lld], which the seam rule takes from chunks "
+                  "%lld..%lld; given are chunk k=%lld%s%s%s", who, (long long)e0, (long long)(e0 + n_out), (long long)t_first,
                   (long long)t_last, (long long)c_lo, (long long)c_hi, (long long)k,
                   (k >= 1 && prev_c64) ? ", k-1" : "", (k >= 2 && prev2_c64) ? ", k-2" : "",
                   last ? " (the last)" : " (not the last: frames from (k+1) hop on wait for chunk k+1)");
         return ERR_SHAPE;
     }
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    WindowFrames fr;
     const float2* given[3] = {reinterpret_cast<const float2*>(prev2_c64), reinterpret_cast<const float2*>(prev_c64),
                               reinterpret_cast<const float2*>(cur_c64)};
     const int held = (int)(k - m) + 1;                  // chunks m .. k
-    for (int i = 0; i < 3; ++i) fr.rows.c[i] = i < held ? given[3 - held + i] : nullptr;
-    fr.T = last ? Tg : INT64_MAX / 4;
-    fr.base = m * hop;
-    fr.t_lo = t_first;
-    fr.t_hi = t_last + 1;
-    fr.Kw = held + (last ? 0 : 1);
-    fr.Tc = Tc;
-    fr.hop = hop;
-    fr.factor = factor;
-    fr.exponent = exponent;
+    for (int i = 0; i < 3; ++i) fr->rows.c[i] = i < held ? given[3 - held + i] : nullptr;
+    fr->T = last ? Tg : INT64_MAX / 4;
+    fr->base = m * hop;
+    fr->t_lo = t_first;
+    fr->t_hi = t_last + 1;
+    fr->Kw = held + (last ? 0 : 1);
+    fr->Tc = Tc;
+    fr->hop = hop;
+    fr->factor = factor;
+    fr->exponent = exponent;
+    return OK;
+}
+
+int flowse_istft_decompress_window(const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k, int Tc,
+                                   int hop, int last, int64_t L, float factor, float exponent, float* out, int64_t e0,
+                                   int64_t n_out, float scale_out, void* stream) {
+    if (!cur_c64 || !out) {
+        set_error("flowse_istft_decompress_window: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    WindowFrames fr;
+    int rc = check_istft_window("istft window", prev2_c64, prev_c64, cur_c64, k, Tc, hop, last, L, factor, exponent, e0, n_out,
+                                &fr);
+    if (rc != OK) return rc;
+    float* tab = nullptr;
+    rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
     const int64_t blocks = (e0 + n_out - 1) / HOP - e0 / HOP + 1;
     hipLaunchKernelGGL(istft_decompress_window_kernel, dim3((unsigned)blocks), dim3(256), 0, s, fr, tab, out, e0, n_out,
                        scale_out);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+// ---- the windows of several sessions in one launch each (flowmse_amd.livepool); `rows`: HOST tables ---------------------
+int flowse_stft_compress_window_rows(const flowse_window_row* rows, int R, int Tw, void* out_c64, float factor,
+                                     float exponent, void* stream) {
+    if (!rows || !out_c64) {
+        set_error("flowse_stft_compress_window_rows: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (R < 1 || R > FLOWSE_MAX_WINDOW_ROWS) {
+        set_error("stft window rows: need 1 <= R <= %d (got R=%d)", FLOWSE_MAX_WINDOW_ROWS, R);
+        return ERR_SHAPE;
+    }
+    WindowInTable t;
+    char who[48];
+    for (int r = 0; r < FLOWSE_MAX_WINDOW_ROWS; ++r) {
+        if (r >= R) {
+            t.row[r] = t.row[0];                        // the slots past R are never read; keep them defined
+            continue;
+        }
+        const flowse_window_row& w = rows[r];
+        if (!w.buf) {
+            set_error("stft window rows: row %d has a null buf", r);
+            return ERR_ARG;
+        }
+        snprintf(who, sizeof(who), "stft window rows: row %d", r);
+        int64_t T = 0;
+        const int rc = check_stft_window(who, w.s0, w.n, w.frame0, Tw, w.L_total, &T);
+        if (rc != OK) return rc;
+        t.row[r] = WindowInRow{w.buf, w.s0, w.L_total >= 0 ? w.L_total : INT64_MAX / 4, w.frame0, T, w.scale_in};
+    }
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(stft_compress_window_rows_kernel, dim3(Tw, R), dim3(256), 0, s, t, tab,
+                       reinterpret_cast<float2*>(out_c64), Tw, factor, exponent);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+int flowse_istft_decompress_window_rows(const flowse_window_out* rows, int R, int Tc, int hop, float factor, float exponent,
+                                        void* stream) {
+    if (!rows) {
+        set_error("flowse_istft_decompress_window_rows: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (R < 1 || R > FLOWSE_MAX_WINDOW_ROWS) {
+        set_error("istft window rows: need 1 <= R <= %d (got R=%d)", FLOWSE_MAX_WINDOW_ROWS, R);
+        return ERR_SHAPE;
+    }
+    WindowOutTable t;
+    char who[48];
+    int64_t blocks = 0;
+    for (int r = 0; r < FLOWSE_MAX_WINDOW_ROWS; ++r) {
+        if (r >= R) {
+            t.row[r] = t.row[0];                        // never read: the grid has R rows
+            continue;
+        }
+        const flowse_window_out& w = rows[r];
+        if (!w.cur_c64 || !w.out) {
+            set_error("istft window rows: row %d has a null cur_c64 or out", r);
+            return ERR_ARG;
+        }
+        snprintf(who, sizeof(who), "istft window rows: row %d", r);
+        WindowFrames fr;
+        const int rc = check_istft_window(who, w.prev2_c64, w.prev_c64, w.cur_c64, w.k, Tc, hop, w.last, w.L, factor, exponent,
+                                          w.e0, w.n_out, &fr);
+        if (rc != OK) return rc;
+        t.row[r] = WindowOutRow{fr.rows, fr.T, fr.base, fr.t_lo, fr.t_hi, w.out, w.e0, w.n_out, fr.Kw, w.scale_out};
+        const int64_t b = (w.e0 + w.n_out - 1) / HOP - w.e0 / HOP + 1;
+        if (b > blocks) blocks = b;
+    }
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(istft_decompress_window_rows_kernel, dim3((unsigned)blocks, R), dim3(256), 0, s, t, tab, Tc, hop, factor,
+                       exponent);
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

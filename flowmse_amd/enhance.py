@@ -61,6 +61,11 @@ with ``--output_rate input`` the enhanced stream is resampled back, as many samp
 -r 48000``.  The bytes are then those of the file mode under ``--resample`` with the same ``--output_rate`` (at ``--batch 1``,
 ``--live_norm`` the peak of the resampled recording).  ``--live_block`` and the latency count samples at ``--live_rate``;
 a rate whose ratio to 16 kHz the resampler does not support is refused by name.  ``--resample`` itself stays a file-mode flag.
+``--live_channels C`` (default 1; ``flowmse_amd.livepool``) reads and writes interleaved frames of ``C`` channels: ``arecord -t
+raw -f S16_LE -r 16000 -c 2 | python -m flowmse_amd.enhance --live --live_channels 2 --ckpt m.ckpt | aplay -t raw -f S16_LE -r
+16000 -c 2``.  The stream is one session of a ``LivePool`` of width ``C`` under the keys ``channel_key("live", c)``, normalised by
+one factor over all channels, and the bytes are those of ``--pool --channels all --batch C`` on the finished recording alone.
+``C = 1`` is the path above, byte for byte.  ``C > 1`` runs at 16 kHz only: with another ``--live_rate`` it is refused by name.
 """
 import argparse
 import csv
@@ -74,8 +79,9 @@ import torch
 from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, enhance_long, plan_chunks
 from flowmse_amd.ensemble import samples_arg
 from flowmse_amd.evaluate import _load_model, _seconds_arg, _synthetic_pairs, _write_wav
-from flowmse_amd.live import PCM_FORMATS, pcm_decode, pcm_encode
-from flowmse_amd.pooled import MAX_BATCH, enhance_pooled
+from flowmse_amd.live import PCM_FORMATS, pcm_decode, pcm_deinterleave, pcm_encode, pcm_interleave
+from flowmse_amd.livepool import MAX_WIDTH
+from flowmse_amd.pooled import MAX_BATCH, channel_key, enhance_pooled
 from flowmse_amd.resample import out_len, rational, resample
 from flowmse_amd.util.noise import utterance_key
 from flowmse_amd.util.other import read_wav, read_wav_channels
@@ -158,6 +164,10 @@ def build_parser():
                     help="needs --live. Sample rate of stdin (default 16000): the stream is resampled to 16 kHz on the device "
                          "as it arrives (the ratio to 16 kHz at most 1024 after reduction). stdout is at 16 kHz, or with "
                          "--output_rate input at this rate, as many samples as were read")
+    ap.add_argument("--live_channels", type=int, default=1, metavar="C",
+                    help="needs --live. Channels of stdin and stdout, interleaved frame after frame (default 1). C > 1 enhances "
+                         "the channels independently in sampler calls of C rows (flowmse_amd.livepool), one normalisation "
+                         "for all of them; 16 kHz only")
     return ap
 
 
@@ -186,6 +196,11 @@ def _check_live(args, ap):
         rational(args.live_rate, SAMPLE_RATE)
     except ValueError as e:
         ap.error(f"--live_rate: {e}")
+    if not 1 <= args.live_channels <= MAX_WIDTH:
+        ap.error(f"--live_channels must be 1..{MAX_WIDTH}, got {args.live_channels}")
+    if args.live_channels > 1 and args.live_rate != SAMPLE_RATE:
+        ap.error(f"--live_channels {args.live_channels} does not take --live_rate {args.live_rate}: the live pool runs at "
+                 f"{SAMPLE_RATE} Hz only")
     if not args.synthetic and not args.ckpt:
         ap.error("--live needs --ckpt (or --synthetic 1 for synthetic weights)")
     if args.N < 1:
@@ -204,6 +219,8 @@ def parse_args(argv=None, ap=None):
         return _check_live(args, ap)
     if args.live_rate != SAMPLE_RATE:
         ap.error(f"--live_rate {args.live_rate} needs --live (files at other rates take --resample)")
+    if args.live_channels != 1:
+        ap.error(f"--live_channels {args.live_channels} needs --live (files with several channels take --pool --channels all)")
     if args.output is None:
         ap.error("the following arguments are required: --output")
     if args.synthetic < 0:
@@ -389,6 +406,8 @@ def run_live(args, ap):
         model, _ = _load_model(types.SimpleNamespace(synthetic=args.synthetic, ckpt=args.ckpt, test_dir="stdin",
                                                      precision=args.precision), ap)
         seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(8), "little")
+        if args.live_channels > 1:
+            return _run_live_channels(args, model, seed, stdin, stdout)
         live = LiveEnhancer(model, norm=args.live_norm, key=utterance_key("live"), seed=seed, chunk_frames=args.chunk_frames,
                             overlap_frames=args.overlap_frames, N=args.N, T_rev=args.reverse_starting_point,
                             t_eps=args.last_eval_point, odesolver=args.odesolver, input_rate=args.live_rate,
@@ -411,6 +430,38 @@ def run_live(args, ap):
         return live.samples_out
     finally:
         sys.stdout = text_out
+
+
+def _run_live_channels(args, model, seed, stdin, stdout):
+    """``--live --live_channels C``, ``C > 1``: interleaved frames through one session of a ``LivePool`` of width ``C``, one
+    ``step()`` per block.  Returns the frames written."""
+    import sys
+    from flowmse_amd.live import latency_samples
+    from flowmse_amd.livepool import LivePool
+    C = args.live_channels
+    pool = LivePool(model, width=C, seed=seed, chunk_frames=args.chunk_frames, overlap_frames=args.overlap_frames, N=args.N,
+                    T_rev=args.reverse_starting_point, t_eps=args.last_eval_point, odesolver=args.odesolver)
+    session = pool.open([channel_key("live", c) for c in range(C)], args.live_norm)
+    latency = latency_samples(args.chunk_frames)
+    print(f"live: {C} channels, keyed noise seed {seed}, {args.live_pcm}, blocks of {args.live_block} frames, at most "
+          f"{latency} samples ({latency / SAMPLE_RATE:.2f} s) behind the input", file=sys.stderr)
+    width, t0 = PCM_FORMATS[args.live_pcm], time.time()
+
+    def deliver():
+        for _, x in pool.step():
+            stdout.write(pcm_encode(pcm_interleave(x), args.live_pcm))
+        stdout.flush()
+
+    while True:
+        data = stdin.read(args.live_block * width * C)
+        if not data:
+            break
+        session.push(pcm_deinterleave(pcm_decode(data, args.live_pcm), C))
+        deliver()
+    session.finish()
+    deliver()
+    print(f"live: enhanced {session.samples_out} frames of {C} channels in {time.time() - t0:.2f} s", file=sys.stderr)
+    return session.samples_out
 
 
 def main(argv=None):

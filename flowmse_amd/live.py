@@ -59,9 +59,10 @@ input)`` are final at the input rate; ``latency_samples`` takes the worst case o
 ``3 (128 Tc + 382) + 58`` samples, 58 being the two filters' ``28 + 30``).  With the defaults nothing of this exists: the
 object makes the calls it made before and returns the same bytes.
 
-Out of scope: rows of several sessions pooled into one sampler call, ``--streams`` lanes, several GPUs, time-varying or
-non-rational rates, several channels, noise that is not keyed, and any CPU or oracle path -- the oracle composition is
-``enhance_long``'s, and this module is pinned to ``enhance_long``.
+Out of scope: ``--streams`` lanes, several GPUs, time-varying or non-rational rates, noise that is not keyed, and any CPU or
+oracle path -- the oracle composition is ``enhance_long``'s, and this module is pinned to ``enhance_long``.  Rows of several
+sessions pooled into one sampler call, and several channels, are ``flowmse_amd.livepool``'s, which imports this module's
+arithmetic; a ``LiveEnhancer`` stays one mono stream at width 1.
 """
 import numpy as np
 import torch
@@ -120,6 +121,27 @@ def pcm_encode(x, fmt):
     v = np.rint(x.astype(np.float64) * 32768.0)
     v = np.where(np.isfinite(v), v, 0.0)
     return np.clip(v, -32768.0, 32767.0).astype("<i2").tobytes()
+
+
+def pcm_deinterleave(x, channels):
+    """Interleaved samples ``[n * channels]`` (frame after frame, as PCM devices deliver them) -> ``[channels, n]``, contiguous.
+    Samples past the last whole frame are ignored."""
+    channels = int(channels)
+    if channels < 1:
+        raise ValueError(f"pcm_deinterleave: channels must be >= 1, got {channels}")
+    x = np.asarray(x)
+    if x.ndim != 1:
+        raise ValueError(f"pcm_deinterleave takes 1-D interleaved samples, got {x.shape}")
+    n = x.shape[0] // channels
+    return np.ascontiguousarray(x[:n * channels].reshape(n, channels).T)
+
+
+def pcm_interleave(x):
+    """``[channels, n]`` -> interleaved ``[n * channels]``, the inverse of ``pcm_deinterleave``."""
+    x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError(f"pcm_interleave takes [channels, n] samples, got {x.shape}")
+    return np.ascontiguousarray(x.T).reshape(-1)
 
 
 def latency_samples(Tc=CHUNK_FRAMES, input_rate=RATE, output_rate="16000", To=OVERLAP_FRAMES):

@@ -359,6 +359,39 @@ int flowse_istft_decompress_window(const void* prev2_c64, const void* prev_c64, 
                                    int hop, int last, int64_t L, float factor, float exponent, float* out, int64_t e0,
                                    int64_t n_out, float scale_out, void* stream);
 
+/* ---- the windows of several live sessions in one launch each (opt-in: flowmse_amd.livepool, `--live --live_channels C`) --
+ * The two window calls above for sampler calls whose rows come from SEVERAL sessions and channels.  `rows` is a HOST table
+ * of R descriptors, each the arguments of the single-window call; it is copied into the kernel's argument block, so the
+ * calls do not allocate, upload or synchronise, and the caller may reuse the table as soon as they return.
+ * flowse_stft_compress_window_rows: the R input rows complex64 [R,1,256,Tw] of ONE sampler call; row r is, bit for bit, what
+ * flowse_stft_compress_window(buf, s0, n, scale_in, frame0, Tw, L_total, ...) writes (the same per-frame code).  Two rows
+ * may name one buffer.
+ * flowse_istft_decompress_window_rows: R output ranges of one geometry (Tc, hop); range r is, bit for bit, what
+ * flowse_istft_decompress_window(prev2_c64, prev_c64, cur_c64, k, Tc, hop, last, L, ..., out, e0, n_out, scale_out) writes.
+ * The ranges may have different lengths (the grid covers the longest; the blocks past a row's range store nothing), and
+ * every row's own k, last, L, e0 and n_out decide its frames and chunks.  The ranges must not overlap in memory.
+ * Every row passes the checks of the single-window call, all rows before any launch: the first row that fails answers
+ * FLOWSE_ERR_ARG (a null buf, cur_c64 or out) or FLOWSE_ERR_SHAPE with its index and values in flowse_last_error(), and
+ * every output is left untouched.  A null table or out_c64 -> FLOWSE_ERR_ARG; R outside 1..FLOWSE_MAX_WINDOW_ROWS ->
+ * FLOWSE_ERR_SHAPE. */
+#define FLOWSE_MAX_WINDOW_ROWS 16
+typedef struct flowse_window_row {             /* one input row: the arguments of flowse_stft_compress_window */
+    const float* buf;                          /* device, float32 [n]: samples [s0, s0 + n) of the recording */
+    int64_t s0, n, frame0, L_total;            /* L_total = -1 while the recording is open */
+    float scale_in;
+} flowse_window_row;
+typedef struct flowse_window_out {             /* one output range: the arguments of flowse_istft_decompress_window */
+    const void *prev2_c64, *prev_c64, *cur_c64;    /* device, complex64 [1,256,Tc]; a chunk the range does not read may be null */
+    float* out;                                /* device, float32 [n_out] */
+    int64_t k, L, e0, n_out;
+    int32_t last;
+    float scale_out;
+} flowse_window_out;
+int flowse_stft_compress_window_rows(const flowse_window_row* rows, int R, int Tw, void* out_c64, float factor,
+                                     float exponent, void* stream);
+int flowse_istft_decompress_window_rows(const flowse_window_out* rows, int R, int Tc, int hop, float factor, float exponent,
+                                        void* stream);
+
 /* ---- ensembles of draws (opt-in: flowmse_amd.ensemble, `--samples D`; NOT the reference's computation, which draws once)
  * flowse_istft_decompress_ensemble: flowse_istft_decompress_stacks over D draws per stack.  Chunk k of draw d of stack s is
  * row s * stack_stride + d * draw_stride + k of chunks_c64 (rows of 256 * Tc complex64 values; offsets in 64 bits).  The
