@@ -20,6 +20,7 @@ FLOWSE_MAX_ATTN = 4
 FLOWSE_MAX_LANES = 4
 FLOWSE_MAX_SPEC_ROWS = 64
 FLOWSE_MAX_WINDOW_ROWS = 16
+FLOWSE_MAX_RESAMPLE_ROWS = 32
 FLOWSE_MAX_DRAWS = 64
 FLOWSE_BYTES_WEIGHTS, FLOWSE_BYTES_OWNED = 0, 1
 FLOWSE_LOSS_MSE, FLOWSE_LOSS_MAE = 0, 1
@@ -48,6 +49,11 @@ class flowse_window_out(C.Structure):
     _fields_ = [("prev2_c64", C.c_void_p), ("prev_c64", C.c_void_p), ("cur_c64", C.c_void_p), ("out", C.c_void_p),
                 ("k", C.c_int64), ("L", C.c_int64), ("e0", C.c_int64), ("n_out", C.c_int64), ("last", C.c_int32),
                 ("scale_out", C.c_float)]
+
+
+class flowse_resample_row(C.Structure):
+    _fields_ = [("win", C.c_void_p), ("m0", C.c_int64), ("n_win", C.c_int64), ("L_total", C.c_int64), ("out", C.c_void_p),
+                ("n0", C.c_int64), ("n_out", C.c_int64)]
 
 
 if not os.path.exists(LIB_PATH):
@@ -107,6 +113,7 @@ SIGNATURES = {
     "flowse_resample_taps": (_i, [_i, _i, C.POINTER(_d), _i]),
     "flowse_resample_poly": (_i, [_fp, _i, _i, _i, _i, _fp, _i, _vp]),
     "flowse_resample_poly_window": (_i, [_fp, _i64, _i64, _i64, _i, _i, _fp, _i64, _i64, _vp]),
+    "flowse_resample_poly_window_rows": (_i, [C.POINTER(flowse_resample_row), _i, _i, _i, _vp]),
     "flowse_estoi_num_taps": (_i, []),
     "flowse_estoi_taps": (_i, [C.POINTER(_d), _i]),
     "flowse_metrics_workspace_bytes": (_i64, [_i]),

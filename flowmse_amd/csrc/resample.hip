@@ -11,6 +11,7 @@
 // c passes 2^31 after 4.87 M outputs at down = 441 (five minutes of 44.1 kHz audio): c, q and every sample index are
 // 64-bit, on the device and on the host.
 #include <cmath>
+#include <cstdio>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -143,21 +144,21 @@ __global__ __launch_bounds__(RESAMPLE_THREADS) void resample_poly_kernel(const f
     }
 }
 
-// The same outputs from a window of ONE row: `win` holds the samples [m0, m0 + n_win) of the signal, the grid covers the
-// outputs [n0, n0 + n_out), a block `run` consecutive ones, and out[0] is output n0.  The host has checked that every
-// sample of the signal an output needs lies in the window, so a sample outside the window is a zero of the definition
-// (below 0, or at or past the end of a closed signal).  Every index is 64-bit: m0, n0, c and q are absolute.
+// The same outputs from a window of ONE row: `win` holds the samples [m0, m0 + n_win) of the signal, block `block` owns the
+// `run` consecutive outputs from n0 + block * run on (below n0 + n_out), and out[0] is output n0.  The host has checked
+// that every sample of the signal an output needs lies in the window, so a sample outside the window is a zero of the
+// definition (below 0, or at or past the end of a closed signal).  Every index is 64-bit: m0, n0, c and q are absolute.
+// The one body of both window kernels below: a row of the table entry is the single entry's row by construction.
 template <bool X_LDS, bool H_LDS>
-__global__ __launch_bounds__(RESAMPLE_THREADS) void resample_poly_window_kernel(const float* __restrict__ win, int64_t m0,
-                                                                                int64_t n_win, const float* __restrict__ H,
-                                                                                float* __restrict__ out, int64_t n0,
-                                                                                int64_t n_out, int up, int down, int half,
-                                                                                int P, int run, int span) {
+__device__ __forceinline__ void resample_window_block(const float* __restrict__ win, int64_t m0, int64_t n_win,
+                                                      const float* __restrict__ H, float* __restrict__ out, int64_t n0,
+                                                      int64_t n_out, int up, int down, int half, int P, int run, int span,
+                                                      int64_t block) {
     extern __shared__ float lds[];
     float* xs = lds;                               // [span] when X_LDS
     float* hs = lds + (X_LDS ? span : 0);          // [up][P] when H_LDS
     const int64_t m1 = m0 + n_win;
-    const int64_t na = n0 + (int64_t)blockIdx.x * run;
+    const int64_t na = n0 + block * run;
     const int64_t nb = na + run < n0 + n_out ? na + run : n0 + n_out;
     const int64_t q_lo = ((int64_t)half + na * down) / up - (P - 1);      // the first sample the run touches
     if (X_LDS) {
@@ -177,6 +178,43 @@ __global__ __launch_bounds__(RESAMPLE_THREADS) void resample_poly_window_kernel(
         const float* xq = xs + (int)(q - q_lo);                           // in [P - 1, span) when X_LDS
         out[n - n0] = resample_output<X_LDS>(h, P, xq, win, q, m0, m1);
     }
+}
+
+// grid (ceil(n_out / run)): the outputs [n0, n0 + n_out) of one row
+template <bool X_LDS, bool H_LDS>
+__global__ __launch_bounds__(RESAMPLE_THREADS) void resample_poly_window_kernel(const float* __restrict__ win, int64_t m0,
+                                                                                int64_t n_win, const float* __restrict__ H,
+                                                                                float* __restrict__ out, int64_t n0,
+                                                                                int64_t n_out, int up, int down, int half,
+                                                                                int P, int run, int span) {
+    resample_window_block<X_LDS, H_LDS>(win, m0, n_win, H, out, n0, n_out, up, down, half, P, run, span, blockIdx.x);
+}
+
+// The windows of SEVERAL rows at one ratio (flowmse_amd.resample.flush): the descriptors travel by value in the argument
+// block, as the window tables of spec.hip do, already checked on the host.
+struct ResampleRow {
+    const float* win;
+    int64_t m0, n_win;
+    float* out;
+    int64_t n0, n_out;
+};
+struct ResampleRowTable {
+    ResampleRow row[FLOWSE_MAX_RESAMPLE_ROWS];
+};
+static_assert(sizeof(flowse_resample_row) == 56 && sizeof(ResampleRow) == 48 && sizeof(ResampleRowTable) <= 2048,
+              "the table must fit the argument block");
+
+// grid (ceil(largest n_out of any row / run), R): a block past its row's outputs (every block of a row with n_out == 0)
+// returns before it touches LDS; the test is uniform over the block, so no thread waits at the barrier for one that left
+template <bool X_LDS, bool H_LDS>
+__global__ __launch_bounds__(RESAMPLE_THREADS) void resample_poly_window_rows_kernel(const ResampleRowTable rows,
+                                                                                     const float* __restrict__ H, int up,
+                                                                                     int down, int half, int P, int run,
+                                                                                     int span) {
+    const ResampleRow& w = rows.row[blockIdx.y];
+    if ((int64_t)blockIdx.x * run >= w.n_out) return;
+    resample_window_block<X_LDS, H_LDS>(w.win, w.m0, w.n_win, H, w.out, w.n0, w.n_out, up, down, half, P, run, span,
+                                        blockIdx.x);
 }
 
 // the fp32 polyphase table of a reduced ratio on one device: built once per process and device, uploaded on the stream of
@@ -233,7 +271,14 @@ static void launch_window(dim3 grid, size_t lds_bytes, hipStream_t s, const floa
                        H, out, n0, n_out, r.up, r.down, r.half, r.P, run, span);
 }
 
-// The form of a launch, one test for both entries: the outputs per block, and what of the input span and the table a
+template <bool X_LDS, bool H_LDS>
+static void launch_window_rows(dim3 grid, size_t lds_bytes, hipStream_t s, const ResampleRowTable& t, const float* H,
+                               const Ratio& r, int run, int span) {
+    hipLaunchKernelGGL((resample_poly_window_rows_kernel<X_LDS, H_LDS>), grid, dim3(RESAMPLE_THREADS), lds_bytes, s, t, H, r.up,
+                       r.down, r.half, r.P, run, span);
+}
+
+// The form of a launch, one test for all entries: the outputs per block, and what of the input span and the table a
 // block holds in LDS.
 struct LaunchForm {
     int run, span;
@@ -252,6 +297,61 @@ static LaunchForm launch_form(const Ratio& r) {
     f.span = f.x_lds ? (int)span_of(f.run) : 0;
     f.lds_bytes = ((size_t)f.span + (f.h_lds ? (size_t)r.up * r.P : 0)) * sizeof(float);
     return f;
+}
+
+// The checks of one window, for the single entry and for every row of the table entry (`who` names the entry, and the
+// row): nothing is enqueued before they pass.  The reduced ratio comes back in *ratio.
+static int check_window(const char* who, const float* win, int64_t m0, int64_t n_win, int64_t L_total, int up, int down,
+                        const float* out, int64_t n0, int64_t n_out, Ratio* ratio) {
+    if (!win || !out || m0 < 0 || n_win < 0 || n0 < 0 || n_out < 0 || L_total < -1) {
+        set_error("%s: null pointer or a negative count (m0 %lld, n_win %lld, L_total %lld, n0 %lld, n_out %lld)", who,
+                  (long long)m0, (long long)n_win, (long long)L_total, (long long)n0, (long long)n_out);
+        return ERR_ARG;
+    }
+    if (const int rc = make_ratio(who, up, down, ratio)) return rc;
+    const Ratio& r = *ratio;
+    const int64_t reach = (int64_t)1 << 50;        // every product below stays inside 64 bits (up, down <= 2^10)
+    if (m0 > reach || n_win > reach || n0 > reach || L_total > reach || n_out > 0x7fffffff) {
+        set_error("%s: m0 %lld, n_win %lld, n0 %lld and L_total %lld may reach 2^50, n_out %lld 2^31 - 1", who, (long long)m0,
+                  (long long)n_win, (long long)n0, (long long)L_total, (long long)n_out);
+        return ERR_SHAPE;
+    }
+    const int64_t m1 = m0 + n_win, n1 = n0 + n_out;
+    if (L_total >= 0) {
+        const int64_t L_out = (L_total * r.up + r.down - 1) / r.down;
+        if (m1 > L_total || n1 > L_out) {
+            set_error("%s: a signal of %lld samples has %lld outputs at %d / %d; the window [%lld, %lld) or the outputs "
+                      "[%lld, %lld) pass its end", who, (long long)L_total, (long long)L_out, r.up, r.down, (long long)m0,
+                      (long long)m1, (long long)n0, (long long)n1);
+            return ERR_SHAPE;
+        }
+    }
+    if (n_out == 0) return OK;
+    if (r.up == r.down) {                          // out[n] = x[n]: the slice [n0, n1) of the window
+        if (n0 < m0 || n1 > m1) {
+            set_error("%s: at %d / %d the outputs [%lld, %lld) are those samples; the window holds [%lld, %lld)", who, r.up,
+                      r.down, (long long)n0, (long long)n1, (long long)m0, (long long)m1);
+            return ERR_SHAPE;
+        }
+        return OK;
+    }
+    // what the outputs read: x[q(n0) - (P - 1) .. q(n1 - 1)], all P taps of each (a table entry past 2 half is a zero
+    // that still multiplies its sample), clamped to the signal
+    const int64_t q_first = ((int64_t)r.half + n0 * r.down) / r.up, q_last = ((int64_t)r.half + (n1 - 1) * r.down) / r.up;
+    if (L_total < 0 && q_last >= m1) {
+        set_error("%s: output %lld of an open signal reads sample %lld, the window [%lld, %lld) ends before it (has it "
+                  "arrived?)", who, (long long)(n1 - 1), (long long)q_last, (long long)m0, (long long)m1);
+        return ERR_SHAPE;
+    }
+    const int64_t need_lo = q_first - (r.P - 1) > 0 ? q_first - (r.P - 1) : 0;
+    const int64_t need_hi = L_total >= 0 && q_last > L_total - 1 ? L_total - 1 : q_last;       // inclusive
+    if (need_lo < m0 || need_hi >= m1) {
+        set_error("%s: the outputs [%lld, %lld) at %d / %d read the samples [%lld, %lld], the window holds [%lld, %lld)", who,
+                  (long long)n0, (long long)n1, r.up, r.down, (long long)need_lo, (long long)need_hi, (long long)m0,
+                  (long long)m1);
+        return ERR_SHAPE;
+    }
+    return OK;
 }
 
 }  // namespace flowse
@@ -315,55 +415,13 @@ int flowse_resample_poly(const float* sig, int B, int L, int up, int down, float
 int flowse_resample_poly_window(const float* win, int64_t m0, int64_t n_win, int64_t L_total, int up, int down, float* out,
                                 int64_t n0, int64_t n_out, void* stream) {
     const char* who = "flowse_resample_poly_window";
-    if (!win || !out || m0 < 0 || n_win < 0 || n0 < 0 || n_out < 0 || L_total < -1) {
-        set_error("%s: null pointer or a negative count (m0 %lld, n_win %lld, L_total %lld, n0 %lld, n_out %lld)", who,
-                  (long long)m0, (long long)n_win, (long long)L_total, (long long)n0, (long long)n_out);
-        return ERR_ARG;
-    }
     Ratio r;
-    if (const int rc = make_ratio(who, up, down, &r)) return rc;
-    const int64_t reach = (int64_t)1 << 50;        // every product below stays inside 64 bits (up, down <= 2^10)
-    if (m0 > reach || n_win > reach || n0 > reach || L_total > reach || n_out > 0x7fffffff) {
-        set_error("%s: m0 %lld, n_win %lld, n0 %lld and L_total %lld may reach 2^50, n_out %lld 2^31 - 1", who, (long long)m0,
-                  (long long)n_win, (long long)n0, (long long)L_total, (long long)n_out);
-        return ERR_SHAPE;
-    }
-    const int64_t m1 = m0 + n_win, n1 = n0 + n_out;
-    if (L_total >= 0) {
-        const int64_t L_out = (L_total * r.up + r.down - 1) / r.down;
-        if (m1 > L_total || n1 > L_out) {
-            set_error("%s: a signal of %lld samples has %lld outputs at %d / %d; the window [%lld, %lld) or the outputs "
-                      "[%lld, %lld) pass its end", who, (long long)L_total, (long long)L_out, r.up, r.down, (long long)m0,
-                      (long long)m1, (long long)n0, (long long)n1);
-            return ERR_SHAPE;
-        }
-    }
+    if (const int rc = check_window(who, win, m0, n_win, L_total, up, down, out, n0, n_out, &r)) return rc;
     if (n_out == 0) return OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (r.up == r.down) {                          // out[n] = x[n]: the slice [n0, n1) of the window
-        if (n0 < m0 || n1 > m1) {
-            set_error("%s: at %d / %d the outputs [%lld, %lld) are those samples; the window holds [%lld, %lld)", who, r.up,
-                      r.down, (long long)n0, (long long)n1, (long long)m0, (long long)m1);
-            return ERR_SHAPE;
-        }
+    if (r.up == r.down) {                          // out[n] = x[n]: the slice [n0, n0 + n_out) of the window
         FLOWSE_HIP(hipMemcpyAsync(out, win + (n0 - m0), (size_t)n_out * sizeof(float), hipMemcpyDeviceToDevice, s));
         return OK;
-    }
-    // what the outputs read: x[q(n0) - (P - 1) .. q(n1 - 1)], all P taps of each (a table entry past 2 half is a zero
-    // that still multiplies its sample), clamped to the signal
-    const int64_t q_first = ((int64_t)r.half + n0 * r.down) / r.up, q_last = ((int64_t)r.half + (n1 - 1) * r.down) / r.up;
-    if (L_total < 0 && q_last >= m1) {
-        set_error("%s: output %lld of an open signal reads sample %lld, the window [%lld, %lld) ends before it (has it "
-                  "arrived?)", who, (long long)(n1 - 1), (long long)q_last, (long long)m0, (long long)m1);
-        return ERR_SHAPE;
-    }
-    const int64_t need_lo = q_first - (r.P - 1) > 0 ? q_first - (r.P - 1) : 0;
-    const int64_t need_hi = L_total >= 0 && q_last > L_total - 1 ? L_total - 1 : q_last;       // inclusive
-    if (need_lo < m0 || need_hi >= m1) {
-        set_error("%s: the outputs [%lld, %lld) at %d / %d read the samples [%lld, %lld], the window holds [%lld, %lld)", who,
-                  (long long)n0, (long long)n1, r.up, r.down, (long long)need_lo, (long long)need_hi, (long long)m0,
-                  (long long)m1);
-        return ERR_SHAPE;
     }
     const float* H = nullptr;
     if (const int rc = get_table(r, s, &H)) return rc;
@@ -373,6 +431,51 @@ int flowse_resample_poly_window(const float* win, int64_t m0, int64_t n_win, int
     else if (f.x_lds) launch_window<true, false>(grid, f.lds_bytes, s, win, m0, n_win, H, out, n0, n_out, r, f.run, f.span);
     else if (f.h_lds) launch_window<false, true>(grid, f.lds_bytes, s, win, m0, n_win, H, out, n0, n_out, r, f.run, f.span);
     else launch_window<false, false>(grid, f.lds_bytes, s, win, m0, n_win, H, out, n0, n_out, r, f.run, f.span);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+int flowse_resample_poly_window_rows(const flowse_resample_row* rows, int R, int up, int down, void* stream) {
+    if (!rows) {
+        set_error("flowse_resample_poly_window_rows: null table");
+        return ERR_ARG;
+    }
+    if (R < 1 || R > FLOWSE_MAX_RESAMPLE_ROWS) {
+        set_error("flowse_resample_poly_window_rows: need 1 <= R <= %d (got R=%d)", FLOWSE_MAX_RESAMPLE_ROWS, R);
+        return ERR_SHAPE;
+    }
+    // every row passes the single entry's checks before anything is enqueued
+    Ratio r;
+    ResampleRowTable t;
+    char who[64];
+    int64_t longest = 0;
+    for (int i = 0; i < R; ++i) {
+        const flowse_resample_row& w = rows[i];
+        snprintf(who, sizeof(who), "flowse_resample_poly_window_rows: row %d", i);
+        if (const int rc = check_window(who, w.win, w.m0, w.n_win, w.L_total, up, down, w.out, w.n0, w.n_out, &r)) return rc;
+        t.row[i] = ResampleRow{w.win, w.m0, w.n_win, w.out, w.n0, w.n_out};
+        if (w.n_out > longest) longest = w.n_out;
+    }
+    for (int i = R; i < FLOWSE_MAX_RESAMPLE_ROWS; ++i) t.row[i] = t.row[0];    // never read: the grid has R rows
+    if (longest == 0) return OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (r.up == r.down) {                          // per row the single entry's copy
+        for (int i = 0; i < R; ++i) {
+            const ResampleRow& w = t.row[i];
+            if (w.n_out == 0) continue;
+            FLOWSE_HIP(hipMemcpyAsync(w.out, w.win + (w.n0 - w.m0), (size_t)w.n_out * sizeof(float), hipMemcpyDeviceToDevice,
+                                      s));
+        }
+        return OK;
+    }
+    const float* H = nullptr;
+    if (const int rc = get_table(r, s, &H)) return rc;
+    const LaunchForm f = launch_form(r);
+    const dim3 grid((unsigned)((longest + f.run - 1) / f.run), (unsigned)R);
+    if (f.x_lds && f.h_lds) launch_window_rows<true, true>(grid, f.lds_bytes, s, t, H, r, f.run, f.span);
+    else if (f.x_lds) launch_window_rows<true, false>(grid, f.lds_bytes, s, t, H, r, f.run, f.span);
+    else if (f.h_lds) launch_window_rows<false, true>(grid, f.lds_bytes, s, t, H, r, f.run, f.span);
+    else launch_window_rows<false, false>(grid, f.lds_bytes, s, t, H, r, f.run, f.span);
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

@@ -5,6 +5,7 @@
                                   [--chunk_frames 256] [--overlap_frames 32] [--noise keyed|torch] [--seed S]
                                   [--resample [--output_rate 16000|input]] [--pool [--channels first|all] [--samples D]]
     ... | python -m flowmse_amd.enhance --live --ckpt MODEL.ckpt [--live_rate HZ [--output_rate input]] | ...
+    ... | python -m flowmse_amd.enhance --live --ckpt MODEL.ckpt --live_channels C [--live_rate HZ --live_resample] | ...
 
 Unlike ``flowmse_amd.evaluate`` it needs no clean files and reports no metrics.  Every recording goes through
 ``flowmse_amd.chunked.enhance_long``: one that fits a single chunk is enhanced exactly as ``evaluate`` would; a longer
@@ -65,7 +66,13 @@ a rate whose ratio to 16 kHz the resampler does not support is refused by name. 
 raw -f S16_LE -r 16000 -c 2 | python -m flowmse_amd.enhance --live --live_channels 2 --ckpt m.ckpt | aplay -t raw -f S16_LE -r
 16000 -c 2``.  The stream is one session of a ``LivePool`` of width ``C`` under the keys ``channel_key("live", c)``, normalised by
 one factor over all channels, and the bytes are those of ``--pool --channels all --batch C`` on the finished recording alone.
-``C = 1`` is the path above, byte for byte.  ``C > 1`` runs at 16 kHz only: with another ``--live_rate`` it is refused by name.
+``C = 1`` is the path above, byte for byte.  ``C > 1`` runs at 16 kHz only: with another ``--live_rate`` it is refused by name,
+unless ``--live_resample`` is given.  ``--live_resample`` (needs ``--live``, ``C > 1`` and a ``--live_rate`` other than 16000)
+opens the session at ``--live_rate``: stdin is interleaved PCM at that rate, the pool resamples all channels to 16 kHz in one
+launch per step, and with ``--output_rate input`` back again in a second one, as many frames out as came in: ``arecord -t raw
+-f S16_LE -r 48000 -c 2 | python -m flowmse_amd.enhance --live --live_channels 2 --live_rate 48000 --live_resample --output_rate
+input --ckpt m.ckpt | aplay -t raw -f S16_LE -r 48000 -c 2``.  ``--live_norm`` applies to the 16 kHz signal; ``--live_block``
+and the latency line count frames at ``--live_rate``.
 """
 import argparse
 import csv
@@ -167,7 +174,11 @@ def build_parser():
     ap.add_argument("--live_channels", type=int, default=1, metavar="C",
                     help="needs --live. Channels of stdin and stdout, interleaved frame after frame (default 1). C > 1 enhances "
                          "the channels independently in sampler calls of C rows (flowmse_amd.livepool), one normalisation "
-                         "for all of them; 16 kHz only")
+                         "for all of them; 16 kHz only, unless --live_resample is given")
+    ap.add_argument("--live_resample", action="store_true",
+                    help="needs --live, --live_channels C > 1 and a --live_rate other than 16000. stdin is interleaved PCM at "
+                         "--live_rate: the live pool resamples all channels to 16 kHz in one launch per step, and with "
+                         "--output_rate input back again, as many frames out as came in")
     return ap
 
 
@@ -198,9 +209,14 @@ def _check_live(args, ap):
         ap.error(f"--live_rate: {e}")
     if not 1 <= args.live_channels <= MAX_WIDTH:
         ap.error(f"--live_channels must be 1..{MAX_WIDTH}, got {args.live_channels}")
-    if args.live_channels > 1 and args.live_rate != SAMPLE_RATE:
+    if args.live_resample and args.live_rate == SAMPLE_RATE:
+        ap.error(f"--live_resample needs a --live_rate other than {SAMPLE_RATE}: at {SAMPLE_RATE} Hz there is nothing to resample")
+    if args.live_resample and args.live_channels == 1:
+        ap.error("--live_resample needs --live_channels C > 1 (the live pool's resamplers); one channel at another "
+                 "--live_rate takes no flag")
+    if args.live_channels > 1 and args.live_rate != SAMPLE_RATE and not args.live_resample:
         ap.error(f"--live_channels {args.live_channels} does not take --live_rate {args.live_rate}: the live pool runs at "
-                 f"{SAMPLE_RATE} Hz only")
+                 f"{SAMPLE_RATE} Hz only (--live_resample puts its resamplers around it)")
     if not args.synthetic and not args.ckpt:
         ap.error("--live needs --ckpt (or --synthetic 1 for synthetic weights)")
     if args.N < 1:
@@ -221,6 +237,8 @@ def parse_args(argv=None, ap=None):
         ap.error(f"--live_rate {args.live_rate} needs --live (files at other rates take --resample)")
     if args.live_channels != 1:
         ap.error(f"--live_channels {args.live_channels} needs --live (files with several channels take --pool --channels all)")
+    if args.live_resample:
+        ap.error("--live_resample needs --live (files at other rates take --resample)")
     if args.output is None:
         ap.error("the following arguments are required: --output")
     if args.synthetic < 0:
@@ -441,10 +459,17 @@ def _run_live_channels(args, model, seed, stdin, stdout):
     C = args.live_channels
     pool = LivePool(model, width=C, seed=seed, chunk_frames=args.chunk_frames, overlap_frames=args.overlap_frames, N=args.N,
                     T_rev=args.reverse_starting_point, t_eps=args.last_eval_point, odesolver=args.odesolver)
-    session = pool.open([channel_key("live", c) for c in range(C)], args.live_norm)
-    latency = latency_samples(args.chunk_frames)
+    if args.live_resample:                                         # frames at --live_rate in, and with --output_rate input out
+        session = pool.open([channel_key("live", c) for c in range(C)], args.live_norm, input_rate=args.live_rate,
+                            output_rate=args.output_rate)
+        latency = session.latency_samples
+        print(f"live: {args.live_rate} Hz in, {args.live_rate if args.output_rate == 'input' else SAMPLE_RATE} Hz out",
+              file=sys.stderr)
+    else:
+        session = pool.open([channel_key("live", c) for c in range(C)], args.live_norm)
+        latency = latency_samples(args.chunk_frames)
     print(f"live: {C} channels, keyed noise seed {seed}, {args.live_pcm}, blocks of {args.live_block} frames, at most "
-          f"{latency} samples ({latency / SAMPLE_RATE:.2f} s) behind the input", file=sys.stderr)
+          f"{latency} samples ({latency / args.live_rate:.2f} s) behind the input", file=sys.stderr)
     width, t0 = PCM_FORMATS[args.live_pcm], time.time()
 
     def deliver():

@@ -33,11 +33,32 @@ if the stream ends earlier; 1.0 if that peak is 0), read back once, in the first
 buffer holds the samples divided by ``norm`` -- one elementwise torch division by the Python float, as ``enhance_pooled``
 divides the file -- so the rows carry ``scale_in = 1``.
 
-State per session: a ``[C, capacity]`` sample buffer and one or two previous chunks per channel (``state_bytes()``, per
-session and per pool).  A finished session whose tail was delivered is closed, leaves the pool and returns its memory.
+State per session: a ``[C, capacity]`` sample buffer, one or two previous chunks per channel and, at another rate, the
+``[C, capacity]`` buffers of its resamplers (``state_bytes()``, per session and per pool).  A finished session whose tail was
+delivered is closed, leaves the pool and returns its memory.
 
-16 kHz only: a caller at another rate puts a ``resample.StreamResampler`` per channel in front.  Out of scope: adaptive
-width, pooled resampling, ``--streams`` lanes, several GPUs.
+Other rates.  ``pool.open(keys, norm, input_rate=HZ, output_rate="16000" | "input")``: every session has its own rates, and a
+pool may mix them; the defaults are the 16 kHz path above, which makes the calls it made before.  ``push`` takes samples at
+``input_rate`` and still only appends, into the session's ``resample.RowsResampler``; ``SessionPlan`` counts what was pushed,
+and its 16 kHz ``samples_in`` is ``resample.stream_plan`` of that count (``out_len`` once finished), so readiness stays a host
+query.  ``step()`` then has three stages:
+
+(a) one ``resample.flush`` over the in-resamplers of all sessions: ONE ``flowse_resample_poly_window_rows`` launch per distinct
+    ratio and 32 rows, whatever the number of sessions and channels.  The new 16 kHz samples are divided by ``norm`` -- after
+    the resampling, as the file mode divides, so a float ``norm`` applies to the 16 kHz signal and ``norm="first"`` is the peak
+    over all channels of the resampled ``[0, n_0)`` -- and appended to the session buffer;
+(b) the schedule and the sampler calls above, unchanged;
+(c) one ``flush`` over the out-resamplers of the sessions with ``output_rate="input"`` that got samples, finishing those that
+    closed; such a session gets exactly as many samples back as were pushed (the trim of ``live.LiveEnhancer``).
+
+``stats`` / ``last_step`` count the launches of (a) and (c) as ``resample_launches``: eight mono sessions at 48 kHz in and out
+make two per step that samples.  **Contract:** a session's concatenated output is, bit for bit, ``resample(y, rate, 16000)``,
+then ``enhance_pooled`` as above on that alone (``norm`` the peak of the resampled recording), then with ``"input"``
+``resample(x_hat, 16000, rate)[:, :L]`` -- and so the bytes of a ``resample.StreamResampler`` per channel before and behind a
+16 kHz session.  ``session.latency_samples`` is ``live.latency_samples(Tc, input_rate, output_rate, To)``; ``samples_in`` and
+``samples_out`` of a session count at its own rates, those of its ``plan`` at 16 kHz.
+
+Out of scope: adaptive width, resampling fused into the STFT rows kernel, ``--streams`` lanes, several GPUs.
 """
 import collections
 
@@ -45,7 +66,8 @@ import numpy as np
 import torch
 
 from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, plan_chunks
-from flowmse_amd.live import KEEP, PADC, _ready_at, live_plan
+from flowmse_amd.live import KEEP, PADC, RATE, _ready_at, latency_samples, live_plan
+from flowmse_amd.resample import RowsResampler, flush, out_len, rational, stream_plan
 
 MAX_WIDTH = 16                      # FLOWSE_MAX_WINDOW_ROWS: the rows one window launch builds
 
@@ -73,6 +95,18 @@ def check_keys(keys):
     return tuple(int(k) for k in ks)
 
 
+def check_rates(input_rate, output_rate):
+    """``(input_rate, up, down)`` of a session: ``up / down`` takes it to 16 kHz.  A ratio ``resample.rational`` does not admit
+    and an ``output_rate`` other than ``"16000"`` or ``"input"`` are refused by name."""
+    if output_rate not in ("16000", "input"):
+        raise ValueError(f"LivePool.open: output_rate is '16000' or 'input', got {output_rate!r}")
+    try:
+        up, down = rational(input_rate, RATE)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"LivePool.open: input_rate {input_rate!r}: {e}")
+    return int(input_rate), up, down
+
+
 def check_norm(norm):
     if isinstance(norm, str):
         if norm != "first":
@@ -86,18 +120,32 @@ def check_norm(norm):
 class SessionPlan:
     """What the schedule knows of one session: host counters only (no device, no samples).  ``samples_in`` / ``samples_out``
     follow ``live.live_plan`` as a ``LiveEnhancer``'s do, with "sampled" in place of "arrived": ``samples_out`` moves when a
-    ``step()`` has sampled the chunk."""
+    ``step()`` has sampled the chunk.  Both count at 16 kHz.  ``pushed`` counts what was pushed, at ``input_rate``, and
+    ``samples_in`` is what of the 16 kHz signal those samples make final: ``stream_plan(pushed)``, after ``finish()``
+    ``out_len(pushed)`` -- at 16 kHz ``pushed`` itself."""
 
-    def __init__(self, keys, norm, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES):
+    def __init__(self, keys, norm, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES, input_rate=RATE,
+                 output_rate="16000"):
         _, self.hop, _ = plan_chunks(1, chunk_frames, overlap_frames)
         self.Tc, self.To = int(chunk_frames), int(overlap_frames)
         self.keys = check_keys(keys)
         self.channels = len(self.keys)
         self.norm_arg = check_norm(norm)
-        self.samples_in = self.samples_out = 0
+        self.input_rate, self.up, self.down = check_rates(input_rate, output_rate)
+        self.output_rate = output_rate
+        self.pushed = self.samples_out = 0
         self.k = 0                                          # next chunk to sample
         self.finished = self.closed = False
         self.L = self.K = None
+
+    @property
+    def samples_in(self):
+        return stream_plan(self.pushed, self.up, self.down, finished=self.finished)
+
+    @property
+    def latency_samples(self):
+        """Worst algorithmic latency in samples at ``input_rate`` (``live.latency_samples``)."""
+        return latency_samples(self.Tc, self.input_rate, self.output_rate, self.To)
 
     def accept(self, shape):
         """A push of ``shape`` ([C, n]; 1-D or [1, n] at one channel): counted, and ``n`` returned."""
@@ -109,16 +157,18 @@ class SessionPlan:
         if len(shape) != 2 or shape[0] != self.channels:
             raise ValueError(f"LiveSession.push takes [{self.channels}, n] samples (this session has {self.channels} "
                              f"channel{'s' if self.channels > 1 else ''}), got {list(shape)}")
-        self.samples_in += shape[1]
+        self.pushed += shape[1]
         return shape[1]
 
     def finish(self):
         if self.finished:
             raise RuntimeError("LiveSession.finish called twice")
-        if self.samples_in <= PADC:
+        L = out_len(self.pushed, self.up, self.down)
+        if L <= PADC:
             raise ValueError(f"LiveSession.finish: a recording needs more than {PADC} samples (n_fft // 2 of the centred "
-                             f"STFT), got {self.samples_in}")
-        self.finished, self.L = True, self.samples_in
+                             f"STFT), got {L}" + (f" at 16 kHz ({self.pushed} at {self.input_rate} Hz)" if self.up != self.down
+                                                  else ""))
+        self.finished, self.L = True, L
         self.K = live_plan(self.L, self.Tc, self.To, finished=True)[0]
 
     def pending(self):
@@ -169,30 +219,50 @@ class LiveSession:
     """One stream of ``C`` channels in a ``LivePool`` (``pool.open``).  ``push`` and ``finish`` only record; the samples
     come back from ``pool.step()``."""
 
-    def __init__(self, pool, keys, norm):
+    def __init__(self, pool, keys, norm, input_rate=RATE, output_rate="16000"):
         self.pool = pool
-        self.plan = SessionPlan(keys, norm, pool.Tc, pool.To)
+        self.plan = SessionPlan(keys, norm, pool.Tc, pool.To, input_rate, output_rate)
         self.norm = None if isinstance(self.plan.norm_arg, str) else self.plan.norm_arg
         self._buf = torch.empty(self.channels, 0, dtype=torch.float32, device=pool.device)
         self._s0 = self._n = 0                              # the buffer holds samples [s0, s0 + n) of every channel
         self._prev = [None] * self.channels                 # chunk k - 1 (and k - 2) per channel
         self._prev2 = [None] * self.channels
+        self._rs_in = self._rs_out = None                   # input_rate != 16000: the resamplers around the 16 kHz path
+        self._delivered = 0                                 # output_rate="input": samples returned, at the input rate
+        self._back = output_rate == "input" and self.plan.up != self.plan.down
+        if self.plan.up != self.plan.down:
+            self._rs_in = RowsResampler(self.input_rate, RATE, self.channels, pool.device)
+            if self._back:
+                self._rs_out = RowsResampler(RATE, self.input_rate, self.channels, pool.device)
 
     channels = property(lambda self: self.plan.channels)
     keys = property(lambda self: self.plan.keys)
-    samples_in = property(lambda self: self.plan.samples_in)
-    samples_out = property(lambda self: self.plan.samples_out)
+    input_rate = property(lambda self: self.plan.input_rate)
+    output_rate = property(lambda self: self.plan.output_rate)
+    latency_samples = property(lambda self: self.plan.latency_samples)
     finished = property(lambda self: self.plan.finished)
     closed = property(lambda self: self.plan.closed)
 
+    @property
+    def samples_in(self):
+        """Samples pushed, at ``input_rate``."""
+        return self.plan.pushed
+
+    @property
+    def samples_out(self):
+        """Samples returned, at the session's output rate."""
+        return self._delivered if self._back else self.plan.samples_out
+
     def state_bytes(self):
-        """Device bytes held between steps: the sample buffer (its capacity) and the previous chunks."""
+        """Device bytes held between steps: the sample buffer (its capacity), the previous chunks and the buffers of the
+        resamplers, if any."""
         kept = [c for c in self._prev + self._prev2 if c is not None]
-        return self._buf.numel() * 4 + sum(c.numel() * 8 for c in kept)
+        rs = sum(r.state_bytes() for r in (self._rs_in, self._rs_out) if r is not None)
+        return self._buf.numel() * 4 + sum(c.numel() * 8 for c in kept) + rs
 
     def push(self, samples):
-        """Append ``samples``: float32 ``[C, n]`` (1-D or ``[1, n]`` at one channel), numpy, CPU or device tensor.  No sampler
-        call and no device synchronisation; returns None."""
+        """Append ``samples`` at ``input_rate``: float32 ``[C, n]`` (1-D or ``[1, n]`` at one channel), numpy, CPU or device
+        tensor.  No sampler or resampler call and no device synchronisation; returns None."""
         if isinstance(samples, np.ndarray):
             samples = torch.from_numpy(np.ascontiguousarray(samples))
         if not torch.is_tensor(samples) or samples.dtype != torch.float32:
@@ -202,6 +272,14 @@ class LiveSession:
         if n == 0:
             return
         samples = samples.reshape(self.channels, n).to(self.pool.device)
+        if self._rs_in is not None:                         # the 16 kHz samples come from the next step()'s flush
+            self._rs_in.append(samples)
+            return
+        self._take(samples)
+
+    def _take(self, samples):
+        """``[C, n]`` samples of the 16 kHz signal on the device, n > 0: divided by ``norm`` (once it is known) into the buffer."""
+        n = samples.size(1)
         if self._n + n > self._buf.size(1):                 # grow once per new largest backlog; contents move to the front
             grown = torch.empty(self.channels, self._n + n, dtype=torch.float32, device=self.pool.device)
             grown[:, :self._n] = self._buf[:, :self._n]
@@ -210,8 +288,16 @@ class LiveSession:
         self._n += n
 
     def finish(self):
-        """The stream has ended (more than 255 samples, as everywhere): its remaining chunks become ready."""
+        """The stream has ended (more than 255 samples at 16 kHz, as everywhere): its remaining chunks become ready."""
         self.plan.finish()
+
+    def _trimmed(self, x):
+        """``output_rate="input"``: what the out-resampler made of this step's 16 kHz samples, trimmed so that the total is
+        the pushed count, as ``enhance_recording`` trims (``live.LiveEnhancer._back``: before the end nothing is cut, an
+        output at the input rate is final later than the input sample under it)."""
+        x = x[:, :max(self.plan.pushed - self._delivered, 0)]
+        self._delivered += x.size(1)
+        return x
 
     # ---- what step() does to a session ----------------------------------------------------------------------------
     def _fix_norm(self):
@@ -238,6 +324,7 @@ class LiveSession:
         self._prev2 = [None] * self.channels
         self._s0 += self._n
         self._n = 0
+        self._rs_in = self._rs_out = None
 
 
 class LivePool:
@@ -271,12 +358,15 @@ class LivePool:
         with torch.cuda.device(self.device):
             dnn.reserve(self.width, 256, self.Tc)
         self.sessions = []                                  # open sessions, in the order they were opened
-        self.stats = dict(steps=0, calls=0, rows=0, fillers=0)
-        self.last_step = dict(calls=0, rows=0, fillers={})  # fillers: per bucket width
+        self.stats = dict(steps=0, calls=0, rows=0, fillers=0, resample_launches=0)
+        self.last_step = dict(calls=0, rows=0, fillers={}, resample_launches=0)     # fillers: per bucket width
 
-    def open(self, keys, norm):
-        """A new session: ``keys`` one 64-bit key, or one per channel; ``norm`` a positive float or ``"first"``."""
-        s = LiveSession(self, keys, norm)
+    def open(self, keys, norm, input_rate=RATE, output_rate="16000"):
+        """A new session: ``keys`` one 64-bit key, or one per channel; ``norm`` a positive float or ``"first"`` (it applies to
+        the 16 kHz signal); ``input_rate``: the rate of what is pushed, any ratio to 16 kHz that ``resample.rational`` admits
+        (another is refused here, by name); ``output_rate``: ``"16000"``, or ``"input"`` for as many samples back as were
+        pushed, at their rate."""
+        s = LiveSession(self, keys, norm, input_rate, output_rate)
         self.sessions.append(s)
         return s
 
@@ -295,10 +385,25 @@ class LivePool:
         from flowmse_amd import _lib
         from flowmse_amd.sampling import get_white_box_solver
         sessions = list(self.sessions)
+        self.last_step = dict(calls=0, rows=0, fillers={}, resample_launches=0)
+        # (a) what was pushed at other rates becomes 16 kHz samples: one launch per ratio and 32 rows, over all sessions
+        feeds = [s for s in sessions if s._rs_in is not None and not s._rs_in.finished
+                 and (s.plan.finished or s._rs_in.pending() > 0)]
+        if feeds:
+            with torch.cuda.device(self.device):
+                new = flush([s._rs_in for s in feeds], finished=[s._rs_in for s in feeds if s.plan.finished],
+                            stats=self.last_step)
+                for s, x in zip(feeds, new):
+                    if x.size(1):
+                        s._take(x)
+                    assert s._s0 + s._n == s.plan.samples_in
+            self.stats["resample_launches"] += self.last_step["resample_launches"]
+        # (b) the sampler calls of everything that is ready
         calls = plan_step([s.plan for s in sessions], self.width)
-        self.last_step = dict(calls=len(calls), rows=0, fillers={})
+        self.last_step["calls"] = len(calls)
         if not calls:
             return []
+        launched = self.last_step["resample_launches"]
         factor, exponent = float(self._dm.spec_factor), float(self._dm.spec_abs_exponent)
         with torch.cuda.device(self.device):
             # per session: the output of this step, and where each of its chunks lies in it
@@ -350,17 +455,30 @@ class LivePool:
                 self.last_step["rows"] += len(real)
                 self.last_step["fillers"][Tw] = self.last_step["fillers"].get(Tw, 0) + W - len(real)
             # the counters move, the samples behind the next chunk are dropped, finished sessions leave
-            results = []
+            back = []
             for i in sorted(outs):
                 s = sessions[i]
                 for k, _ in s.plan.pending():
                     s.plan.sampled(k)
+                if not s.plan.closed:
+                    s._drop(max(s.plan.samples_out + PADC - KEEP, 0))
+                if s._rs_out is not None:
+                    s._rs_out.append(outs[i])
+                    back.append(i)
+            # (c) output_rate="input": what came out goes back to the sessions' rates, again one launch per ratio and 32 rows
+            if back:
+                new = flush([sessions[i]._rs_out for i in back],
+                            finished=[sessions[i]._rs_out for i in back if sessions[i].plan.closed], stats=self.last_step)
+                for i, x in zip(back, new):
+                    outs[i] = sessions[i]._trimmed(x)
+            results = []
+            for i in sorted(outs):
+                s = sessions[i]
                 if s.plan.closed:
                     s._release()
                     self.sessions.remove(s)
-                else:
-                    s._drop(max(s.plan.samples_out + PADC - KEEP, 0))
                 results.append((s, outs[i] if as_tensor else outs[i].cpu().numpy()))
+        self.stats["resample_launches"] += self.last_step["resample_launches"] - launched
         self.stats["steps"] += 1
         self.stats["calls"] += len(calls)
         self.stats["rows"] += self.last_step["rows"]

@@ -17,7 +17,9 @@ a Python int or an int64.
 
 A signal that is still arriving (``flowmse_amd.live`` at 44.1 or 48 kHz) goes through ``StreamResampler``: the same
 outputs from a window of the signal, one ``flowse_resample_poly_window`` launch per push; ``stream_plan`` says how many
-outputs are final after ``n`` samples.
+outputs are final after ``n`` samples.  Several such signals (the channels and sessions of ``flowmse_amd.livepool``) go
+through ``RowsResampler`` s and ``flush``: the rows of all of them at one ratio in one
+``flowse_resample_poly_window_rows`` launch, ``plan_flush`` being the host side of that grouping.
 """
 import ctypes as C
 import math
@@ -257,3 +259,176 @@ class StreamResampler:
         self._buf[:rest.numel()] = rest
         self._m0 += cut
         self._n -= cut
+
+
+# ---- several signals that are still arriving: one launch per ratio ------------------------------------------------
+MAX_ROWS = _lib.FLOWSE_MAX_RESAMPLE_ROWS            # the rows one flowse_resample_poly_window_rows launch takes
+
+
+class RowsResampler:
+    """``resample`` for ``rows`` signals that arrive TOGETHER (the channels of a live session): one ``[rows, capacity]``
+    float32 buffer under one set of counters.  ``append`` only copies into the buffer; the outputs are made by
+    ``flush``, which serves any number of these objects with one ``flowse_resample_poly_window_rows`` launch per ratio and
+    ``MAX_ROWS`` rows.  ``push`` and ``finish`` are ``append`` plus ``flush([self])``.
+
+    **Contract** (``StreamResampler``'s, per row): the concatenation of everything the flushes returned for row ``r``
+    equals ``resample(x[None], sr_in, sr_out)[0]`` for the row's finished signal -- on a HIP device bit for bit, whatever
+    the push sizes (empty ones and single samples included), whenever the flushes happen and whatever else is flushed with
+    it.  On the CPU the outputs are ``StreamResampler``'s: ``resample_reference(..., n0, n1, m0)`` rounded to float32.
+
+    State: after a flush the samples before ``q(next output) - (P - 1)`` are dropped, once for all rows; the capacity is
+    ``P - 1`` plus the largest backlog between two flushes, per row.  Equal rates pass the samples through."""
+
+    def __init__(self, sr_in, sr_out, rows, device=None):
+        self.sr_in, self.sr_out = int(sr_in), int(sr_out)
+        self.up, self.down = rational(sr_in, sr_out)
+        _, _, self.half, self.P = _geometry(self.up, self.down)
+        self.rows = int(rows)
+        if self.rows < 1:
+            raise ValueError(f"RowsResampler: rows must be >= 1, got {rows}")
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._buf = None
+        self.reset()
+
+    def state_bytes(self):
+        """Bytes of samples this object holds between flushes (the buffer's capacity, all rows)."""
+        return 0 if self._buf is None else self._buf.numel() * 4
+
+    def reset(self):
+        """Forget the signals; the buffer keeps its capacity."""
+        self.samples_in = self.samples_out = 0
+        self._m0 = self._n = 0                                     # the buffer holds samples [m0, m0 + n) of every row
+        self._finished = False
+
+    @property
+    def finished(self):
+        return self._finished
+
+    def pending(self, finished=False):
+        """The outputs per row the next flush makes (``finished``: the signals end at ``samples_in``): host arithmetic."""
+        if self._finished:
+            return 0
+        return stream_plan(self.samples_in, self.up, self.down, finished=finished) - self.samples_out
+
+    def append(self, samples):
+        """Append ``samples``: float32 ``[rows, n]`` (1-D at one row), n >= 0, numpy, CPU or device tensor.  Copies into the
+        buffer and nothing else: no launch of the resampler, no synchronisation."""
+        if self._finished:
+            raise RuntimeError("RowsResampler.append after the signals were finished: call reset() to start others")
+        if isinstance(samples, np.ndarray):
+            samples = torch.from_numpy(np.ascontiguousarray(samples))
+        if not torch.is_tensor(samples) or samples.dtype != torch.float32:
+            raise TypeError("RowsResampler.append takes float32 samples (numpy array or tensor), got "
+                            f"{getattr(samples, 'dtype', type(samples).__name__)}")
+        if samples.dim() == 1 and self.rows == 1:
+            samples = samples[None]
+        if samples.dim() != 2 or samples.size(0) != self.rows:
+            raise ValueError(f"RowsResampler.append takes [{self.rows}, n] samples, got {tuple(samples.shape)}")
+        if self.device is None:
+            self.device = samples.device
+        n = samples.size(1)
+        if n == 0:
+            return
+        if self._buf is None or self._n + n > self._buf.size(1):   # grow once per new largest backlog; contents stay in front
+            keep = self.P - 1 if self.up != self.down else 0
+            grown = torch.empty(self.rows, max(self._n, keep) + n, dtype=torch.float32, device=self.device)
+            if self._n:
+                grown[:, :self._n] = self._buf[:, :self._n]
+            self._buf = grown
+        self._buf[:, self._n:self._n + n] = samples.to(self.device)
+        self._n += n
+        self.samples_in += n
+
+    def push(self, samples, as_tensor=False):
+        """``append`` and ``flush([self])``: the ``[rows, n_new]`` outputs that became final, numpy or a tensor on ``device``."""
+        self.append(samples)
+        out = flush([self])[0]
+        return out if as_tensor else out.cpu().numpy()
+
+    def finish(self, as_tensor=False):
+        """The signals have ended at ``samples_in``: the remaining outputs, up to ``out_len(samples_in)``."""
+        if self._finished:
+            raise RuntimeError("RowsResampler.finish called twice: call reset() to start other signals")
+        out = flush([self], finished=[self])[0]
+        return out if as_tensor else out.cpu().numpy()
+
+    # ---- what flush() does to a stream ------------------------------------------------------------------------
+    def _flushed(self, n1, finished):
+        """The outputs up to ``n1`` were made: the counters move and the samples no later output reads are dropped."""
+        self.samples_out = n1
+        if finished:
+            self._finished = True
+            self._m0 += self._n
+            self._n = 0
+            return
+        upto = self.samples_in if self.up == self.down else max((self.half + n1 * self.down) // self.up - (self.P - 1), 0)
+        cut = min(upto, self._m0 + self._n) - self._m0
+        if cut <= 0:
+            return
+        if cut < self._n:
+            rest = self._buf[:, cut:self._n].clone()
+            self._buf[:, :rest.size(1)] = rest
+        self._m0 += cut
+        self._n -= cut
+
+
+def plan_flush(entries, max_rows=MAX_ROWS):
+    """The launches of one ``flush``.  ``entries``: per stream ``(device, up, down, rows, n_new)``.  The rows of the streams
+    with ``n_new > 0`` at unequal rates are grouped by ``(device, up, down)``, groups in the order of their first stream and
+    rows in stream order; each group is cut into tables of at most ``max_rows`` rows.  Returns ``[((device, up, down),
+    [(stream index, row), ...]), ...]``, one launch each.  Host only."""
+    groups = {}
+    for i, (device, up, down, rows, n_new) in enumerate(entries):
+        if n_new > 0 and up != down:
+            groups.setdefault((device, int(up), int(down)), []).extend((i, r) for r in range(int(rows)))
+    return [(key, rows[a:a + max_rows]) for key, rows in groups.items() for a in range(0, len(rows), max_rows)]
+
+
+def flush(streams, finished=(), stats=None):
+    """Make the outputs that are final in every ``RowsResampler`` of ``streams``; those also in ``finished`` have ended
+    and deliver their last outputs.  Returns one float32 ``[rows, n_new]`` tensor per stream, on the stream's device
+    (``n_new`` may be 0).  On HIP devices: one ``flowse_resample_poly_window_rows`` launch per table of ``plan_flush`` on the
+    current stream, no synchronisation; ``stats["resample_launches"]``, when a dict is given, grows by their number.  CPU
+    streams take ``StreamResampler``'s CPU path row by row."""
+    streams, ended = list(streams), {id(s) for s in finished}
+    if len({id(s) for s in streams}) != len(streams):
+        raise ValueError("resample.flush: a stream is named twice")
+    if not ended <= {id(s) for s in streams}:
+        raise ValueError("resample.flush: finished names a stream that is not among streams")
+    todo, outs = [], []
+    for s in streams:
+        if s._finished:
+            raise RuntimeError("resample.flush: a stream was finished before: call reset() to start other signals")
+        if s.device is None:
+            s.device = torch.device("cpu")
+        n1 = stream_plan(s.samples_in, s.up, s.down, finished=id(s) in ended)
+        todo.append((n1, id(s) in ended))
+        if s.up == s.down:                                         # the samples themselves
+            outs.append(s._buf[:, :s._n].clone() if s._n else torch.empty(s.rows, 0, dtype=torch.float32, device=s.device))
+        else:
+            outs.append(torch.empty(s.rows, n1 - s.samples_out, dtype=torch.float32, device=s.device))
+    plan = plan_flush([(s.device, s.up, s.down, s.rows, out.size(1)) for s, out in zip(streams, outs)])
+    launches = 0
+    for (device, up, down), rows in plan:
+        if device.type != "cuda":
+            for i, r in rows:
+                s, n1 = streams[i], todo[i][0]
+                ref = resample_reference(s._buf[r, :s._n].numpy(), s.sr_in, s.sr_out, s.samples_out, n1, s._m0)
+                outs[i][r] = torch.from_numpy(ref.astype(np.float32))
+            continue
+        table = (_lib.flowse_resample_row * len(rows))()
+        for d, (i, r) in zip(table, rows):
+            s, out = streams[i], outs[i]
+            d.win, d.m0, d.n_win = s._buf.data_ptr() + 4 * r * s._buf.size(1), s._m0, s._n
+            d.L_total = s.samples_in if todo[i][1] else -1
+            d.out, d.n0, d.n_out = out.data_ptr() + 4 * r * out.size(1), s.samples_out, out.size(1)
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib.flowse_resample_poly_window_rows(table, len(rows), up, down, _lib.current_stream()))
+        launches += 1
+    for s, (n1, end) in zip(streams, todo):
+        s._flushed(n1, end)
+    if stats is not None:
+        stats["resample_launches"] = stats.get("resample_launches", 0) + launches
+    return outs

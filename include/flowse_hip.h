@@ -455,7 +455,27 @@ int flowse_istft_decompress_ensemble(const void* chunks_c64, int S, int D, int K
  * n_out == 0 returns FLOWSE_OK and launches nothing.  up == down copies the samples [n0, n0 + n_out) out of the window
  * (which must hold them).  One launch, in the same four forms and under the same test as flowse_resample_poly; the table
  * is that call's: the first call for a ratio on a device (through either entry) uploads it and must not be made under
- * stream capture, every later one enqueues only. */
+ * stream capture, every later one enqueues only.
+ * flowse_resample_poly_window_rows: the window call above for R rows at ONE ratio in one launch (flowmse_amd.resample.flush,
+ * flowmse_amd.livepool): the channels of a session, the sessions of a pool.  `rows` is a HOST table of R descriptors, each
+ * the arguments of the single-window call; it is copied into the kernel's argument block, so the call does not allocate,
+ * upload or synchronise (but for the ratio's table, as above), and the caller may reuse the table as soon as it returns.
+ * Row r receives, bit for bit, what flowse_resample_poly_window(win, m0, n_win, L_total, up, down, out, n0, n_out) writes:
+ * one device function is the body of both kernels, in the same four forms under the same test.  The grid is
+ * (ceil(largest n_out / run), R): a block past its row's n_out returns at once, and a row with n_out == 0 is legal and is
+ * skipped.  Two rows may name one window; the output ranges must not overlap in memory.  Every row passes the checks of the
+ * single-window call, all rows before anything is enqueued: the first row that fails answers FLOWSE_ERR_ARG (a null win
+ * or out, a negative count) or FLOWSE_ERR_SHAPE with `row %d` and its values in flowse_last_error(), and every output is
+ * left untouched.  A null table -> FLOWSE_ERR_ARG; R outside 1..FLOWSE_MAX_RESAMPLE_ROWS -> FLOWSE_ERR_SHAPE.  up == down
+ * copies per row, as the single call does.  All n_out == 0 returns FLOWSE_OK and launches nothing. */
+#define FLOWSE_MAX_RESAMPLE_ROWS 32
+typedef struct flowse_resample_row {           /* one row: the arguments of flowse_resample_poly_window */
+    const float* win;                          /* device, float32 [n_win]: samples [m0, m0 + n_win) of this row's signal */
+    int64_t m0, n_win, L_total;                /* L_total = -1 while the signal is open */
+    float* out;                                /* device, float32 [n_out]: outputs [n0, n0 + n_out) */
+    int64_t n0, n_out;
+} flowse_resample_row;
+int flowse_resample_poly_window_rows(const flowse_resample_row* rows, int R, int up, int down, void* stream);
 int flowse_resample_num_taps(int up, int down);
 int flowse_resample_taps(int up, int down, double* taps, int cap);
 int flowse_resample_poly(const float* sig, int B, int L, int up, int down, float* out, int L_out, void* stream);
