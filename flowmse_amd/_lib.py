@@ -109,6 +109,11 @@ SIGNATURES = {
     "flowse_istft_decompress_window": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i64, _f, _f, _fp, _i64, _i64, _f, _vp]),
     "flowse_stft_compress_window_rows": (_i, [C.POINTER(flowse_window_row), _i, _i, _vp, _f, _f, _vp]),
     "flowse_istft_decompress_window_rows": (_i, [C.POINTER(flowse_window_out), _i, _i, _i, _f, _f, _vp]),
+    "flowse_stft_compress_trailing": (_i, [_fp, _i, _f, _vp, _i, _i, _i, _f, _f, _vp]),
+    "flowse_istft_decompress_trailing": (_i, [_vp, _i, _i, _i, _i, _f, _f, _fp, _i, _f, _vp]),
+    "flowse_stft_compress_trailing_window": (_i, [_fp, _i64, _i64, _f, _i64, _i, _i, _i64, _vp, _f, _f, _vp]),
+    "flowse_istft_decompress_trailing_window": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i64, _f, _f, _fp, _i64, _i64, _f,
+                                                     _vp]),
     "flowse_resample_num_taps": (_i, [_i, _i]),
     "flowse_resample_taps": (_i, [_i, _i, C.POINTER(_d), _i]),
     "flowse_resample_poly": (_i, [_fp, _i, _i, _i, _i, _fp, _i, _vp]),

@@ -311,6 +311,63 @@ __global__ __launch_bounds__(256) void stft_compress_window_kernel(const float* 
                exponent, s0);
 }
 
+// ---- trailing chunks (flowmse_amd.chunked.enhance_trailing): chunk k holds the recording's frames [k H - P, k H + H),
+// P = Tc - H lead frames of context, of which only the last H (+ X of cross-fade) are kept.
+// grid (Tc, rows), 256 threads = 256 bins: row b = chunk k0 + b, frame0 = k0 H - P (negative for the first chunks: the
+// frames before the recording are zero, like those >= T).  Every other frame is stft_frame's.
+__global__ __launch_bounds__(256) void stft_compress_trailing_kernel(const float* __restrict__ buf, int64_t s0, int64_t L,
+                                                                     float scale_in, const float* __restrict__ tab,
+                                                                     float2* __restrict__ out, int64_t frame0, int H,
+                                                                     int64_t T, int Tc, float factor, float exponent) {
+    const int b = blockIdx.y;
+    const int64_t t = frame0 + (int64_t)b * H + blockIdx.x;
+    float2* dst = out + ((int64_t)b * NBIN + threadIdx.x) * Tc + blockIdx.x;
+    if (t < 0) {                                        // the whole block: no barrier is skipped by part of it
+        *dst = make_float2(0.f, 0.f);
+        return;
+    }
+    stft_frame(buf, L, scale_in, tab, dst, t, T, factor, exponent, s0);
+}
+
+// Frame t of a recording held as trailing chunks [K][NBIN][Tc] (t counted from chunk `rows(0)`'s frame P): chunk
+// k = min((t + X) / H, K - 1) at j = t - k H + P; in the X frames before k H the linear cross-fade  a + w (b - a),
+// w = (i + 0.5) / X,  i = t - (k H - X), from chunk k - 1 (a, at j + H) to chunk k (b) -- on the compressed value, before
+// spec_back.  H + X <= Tc keeps j >= 0 and j + H < Tc.
+template <class Rows>
+__device__ __forceinline__ float2 trailing_frame(const Rows& rows, int f, int t, int K, int Tc, int H, int X) {
+    int k = (t + X) / H;
+    if (k > K - 1) k = K - 1;
+    const int j = t - k * H + Tc - H;
+    const float2 b = rows(k)[(int64_t)f * Tc + j];
+    if (k == 0 || t >= k * H) return b;
+    const float2 a = rows(k - 1)[(int64_t)f * Tc + j + H];
+    const float w = ((float)(t - (k * H - X)) + 0.5f) / (float)X;
+    return make_float2(a.x + w * (b.x - a.x), a.y + w * (b.y - a.y));
+}
+
+// Rows: StackRows for the K chunks of a file (base = 0, every frame < T = Tg is served), WindowRows for the chunks a live
+// session holds (as WindowFrames: chunk m + i, base = m H, and only the frames [t_lo, t_hi) the host admitted).
+template <class Rows>
+struct TrailingFrames {
+    Rows rows;
+    int64_t T, base, t_lo, t_hi;
+    int Kw, Tc, H, X;
+    float factor, exponent;
+    __device__ __forceinline__ float2 operator()(int64_t t, int f) const {
+        if (t < t_lo || t >= t_hi) return make_float2(0.f, 0.f);
+        return spec_back_value(trailing_frame(rows, f, (int)(t - base), Kw, Tc, H, X), factor, exponent);
+    }
+};
+
+// grid (blocks of 128 samples that meet [e0, e0 + n_out)), 256 threads: out[i] = sample e0 + i of the recording
+template <class Rows>
+__global__ __launch_bounds__(256) void istft_decompress_trailing_kernel(const TrailingFrames<Rows> frames,
+                                                                        const float* __restrict__ tab,
+                                                                        float* __restrict__ out, int64_t e0, int64_t n_out,
+                                                                        float scale_out) {
+    istft_gather(frames, tab, out, (e0 / HOP + blockIdx.x) * HOP, e0, e0 + n_out, scale_out);
+}
+
 // The same two kernels for the rows of SEVERAL live sessions (flowmse_amd.livepool): the descriptors travel by value in the
 // argument block, as SpecRowTable does, already checked and reduced on the host to what the device code reads.
 struct WindowInRow {
@@ -716,6 +773,154 @@ int flowse_istft_decompress_window(const void* prev2_c64, const void* prev_c64, 
     const int64_t blocks = (e0 + n_out - 1) / HOP - e0 / HOP + 1;
     hipLaunchKernelGGL(istft_decompress_window_kernel, dim3((unsigned)blocks), dim3(256), 0, s, fr, tab, out, e0, n_out,
                        scale_out);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+// ---- trailing chunks: the file pair and the window pair (flowmse_amd.chunked.enhance_trailing, flowmse_amd.live) -----------
+// geometry: Tc a positive multiple of 64, H even in 4..Tc, 0 <= X <= H, H + X <= Tc (X < 0: the entry has no fade)
+static bool trailing_ok(int Tc, int H, int X) {
+    return Tc >= 64 && Tc <= (1 << 23) && Tc % 64 == 0 && H >= 4 && H <= Tc && H % 2 == 0 &&
+           (X < 0 || (X <= H && (int64_t)H + X <= Tc));
+}
+#define TRAILING_GEOMETRY "Tc a multiple of 64 in 64..2^23, H even in 4..Tc"
+
+int flowse_stft_compress_trailing(const float* sig, int L, float scale_in, void* out_c64, int K, int Tc, int H, float factor,
+                                  float exponent, void* stream) {
+    if (!sig || !out_c64) {
+        set_error("flowse_stft_compress_trailing: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int T = L / HOP + 1;
+    if (L <= PADC || !trailing_ok(Tc, H, -1) || K < 1 || K > 65535 || (int64_t)K * H < T || (int64_t)K * H + Tc > (1 << 23)) {
+        set_error("flowse_stft_compress_trailing: need L > %d, " TRAILING_GEOMETRY ", 1 <= K <= 65535 and L / %d + 1 <= K H <= "
+                  "2^23 - Tc (got L=%d K=%d Tc=%d H=%d)", PADC, HOP, L, K, Tc, H);
+        return ERR_SHAPE;
+    }
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(stft_compress_trailing_kernel, dim3(Tc, K), dim3(256), 0, s, sig, (int64_t)0, (int64_t)L, scale_in, tab,
+                       reinterpret_cast<float2*>(out_c64), (int64_t)H - Tc, H, (int64_t)T, Tc, factor, exponent);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+int flowse_istft_decompress_trailing(const void* chunks_c64, int K, int Tc, int H, int X, float factor, float exponent,
+                                     float* out, int Lout, float scale_out, void* stream) {
+    if (!chunks_c64 || !out) {
+        set_error("flowse_istft_decompress_trailing: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t Tg = (int64_t)K * H;
+    if (!trailing_ok(Tc, H, X) || X < 0 || K < 1 || K > 65535 || Tg + Tc > (1 << 23) || Lout < 1 ||
+        Lout > (Tg - 1) * HOP + NFFT - PADC || factor == 0.f) {
+        set_error("flowse_istft_decompress_trailing: need " TRAILING_GEOMETRY ", 0 <= X <= H, H + X <= Tc, 1 <= K <= 65535, "
+                  "K H <= 2^23 - Tc, 1 <= Lout <= 128 (K H - 1) + 255 and factor != 0 (got K=%d Tc=%d H=%d X=%d Lout=%d)", K, Tc,
+                  H, X, Lout);
+        return ERR_SHAPE;
+    }
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    const TrailingFrames<StackRows> fr{StackRows{reinterpret_cast<const float2*>(chunks_c64), Tc}, Tg, 0, 0, Tg, K, Tc, H, X,
+                                       factor, exponent};
+    hipLaunchKernelGGL(istft_decompress_trailing_kernel<StackRows>, dim3((Lout + HOP - 1) / HOP), dim3(256), 0, s, fr, tab, out,
+                       (int64_t)0, (int64_t)Lout, scale_out);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+int flowse_stft_compress_trailing_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t k, int Tc, int H,
+                                         int64_t L_total, void* out_c64, float factor, float exponent, void* stream) {
+    if (!buf || !out_c64) {
+        set_error("flowse_stft_compress_trailing_window: null argument");
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!trailing_ok(Tc, H, -1) || k < 0 || k > WINDOW_MAX / H - 1) {
+        set_error("flowse_stft_compress_trailing_window: need " TRAILING_GEOMETRY " and 0 <= k, (k + 1) H <= 2^40 (got k=%lld "
+                  "Tc=%d H=%d)", (long long)k, Tc, H);
+        return ERR_SHAPE;
+    }
+    // the frames that read samples start at max(k H - P, 0): the checks of the plain window over those
+    const int64_t frame0 = k * H - (Tc - H), first = frame0 < 0 ? 0 : frame0;
+    int64_t T = 0;
+    int rc = check_stft_window("flowse_stft_compress_trailing_window", s0, n, first, (int)(frame0 + Tc - first), L_total, &T);
+    if (rc != OK) return rc;
+    float* tab = nullptr;
+    rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(stft_compress_trailing_kernel, dim3(Tc, 1), dim3(256), 0, s, buf, s0,
+                       L_total >= 0 ? L_total : INT64_MAX / 4, scale_in, tab, reinterpret_cast<float2*>(out_c64), frame0, H, T, Tc,
+                       factor, exponent);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+int flowse_istft_decompress_trailing_window(const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k, int Tc,
+                                            int H, int X, int last, int64_t L, float factor, float exponent, float* out,
+                                            int64_t e0, int64_t n_out, float scale_out, void* stream) {
+    const char* who = "flowse_istft_decompress_trailing_window";
+    if (!cur_c64 || !out) {
+        set_error("%s: null argument", who);
+        return ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!trailing_ok(Tc, H, X) || X < 0 || k < 0 || k > WINDOW_MAX / H - 1 || e0 < 0 || n_out < 1 ||
+        n_out > ((int64_t)1 << 30) || e0 > WINDOW_MAX * HOP || factor == 0.f) {
+        set_error("%s: need " TRAILING_GEOMETRY ", 0 <= X <= H, H + X <= Tc, 0 <= k, (k + 1) H <= 2^40, e0 >= 0, 1 <= n_out <= "
+                  "2^30 and factor != 0 (got k=%lld Tc=%d H=%d X=%d e0=%lld n_out=%lld)", who, (long long)k, Tc, H, X,
+                  (long long)e0, (long long)n_out);
+        return ERR_SHAPE;
+    }
+    const int64_t Tg = (k + 1) * H;
+    if (last && (e0 + n_out > L || L > (Tg - 1) * HOP + NFFT - PADC)) {
+        set_error("%s: after the last chunk need e0 + n_out <= L <= 128 (Tg - 1) + 255 (got e0=%lld n_out=%lld L=%lld "
+                  "Tg=%lld)", who, (long long)e0, (long long)n_out, (long long)L, (long long)Tg);
+        return ERR_SHAPE;
+    }
+    // the frames over the samples [e0, e0 + n_out): the index range of istft_gather for one sample, over all of them
+    const int64_t t_first = e0 <= NFFT - 1 - PADC ? 0 : (e0 - (NFFT - 1 - PADC) + HOP - 1) / HOP;
+    int64_t t_last = (e0 + n_out - 1 + PADC) / HOP;
+    if (last && t_last > Tg - 1) t_last = Tg - 1;
+    // the chunks the seam rule reads for them: the owner of a frame, and the chunk before it inside the fade; both grow with t
+    int64_t c_hi = (t_last + X) / H, c_lo = (t_first + X) / H;
+    if (last && c_hi > k) c_hi = k;
+    if (last && c_lo > k) c_lo = k;
+    if (c_lo > 0 && t_first < c_lo * H) c_lo -= 1;
+    const int64_t m = k >= 2 ? k - 2 : 0;
+    if (c_hi > k || c_lo < m || (c_lo <= k - 1 && !prev_c64) || (c_lo <= k - 2 && !prev2_c64)) {
+        set_error("%s: samples [%lld, %lld) lie under frames [%lld, %lld], which the seam rule takes from chunks %lld..%lld; "
+                  "given are chunk k=%lld%s%s%s", who, (long long)e0, (long long)(e0 + n_out), (long long)t_first,
+                  (long long)t_last, (long long)c_lo, (long long)c_hi, (long long)k, (k >= 1 && prev_c64) ? ", k-1" : "",
+                  (k >= 2 && prev2_c64) ? ", k-2" : "",
+                  last ? " (the last)" : " (not the last: frames from (k+1) H - X on wait for chunk k+1)");
+        return ERR_SHAPE;
+    }
+    const float2* given[3] = {reinterpret_cast<const float2*>(prev2_c64), reinterpret_cast<const float2*>(prev_c64),
+                              reinterpret_cast<const float2*>(cur_c64)};
+    const int held = (int)(k - m) + 1;                  // chunks m .. k
+    TrailingFrames<WindowRows> fr;
+    for (int i = 0; i < 3; ++i) fr.rows.c[i] = i < held ? given[3 - held + i] : nullptr;
+    fr.T = last ? Tg : INT64_MAX / 4;
+    fr.base = m * H;
+    fr.t_lo = t_first;
+    fr.t_hi = t_last + 1;
+    fr.Kw = held + (last ? 0 : 1);
+    fr.Tc = Tc;
+    fr.H = H;
+    fr.X = X;
+    fr.factor = factor;
+    fr.exponent = exponent;
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    const int64_t blocks = (e0 + n_out - 1) / HOP - e0 / HOP + 1;
+    hipLaunchKernelGGL(istft_decompress_trailing_kernel<WindowRows>, dim3((unsigned)blocks), dim3(256), 0, s, fr, tab, out, e0,
+                       n_out, scale_out);
     FLOWSE_LAUNCH_CHECK();
     return OK;
 }

@@ -127,6 +127,39 @@ class SpecTransform:
                                                                float(scale), _lib.current_stream()))
         return out
 
+    # ---- one recording as trailing chunks (flowmse_amd.chunked.enhance_trailing) ----------------------
+    def analyze_trailing(self, sig, Tc, H, scale=1.0):
+        """The trailing rows of ONE recording in one kernel: sig float32 [1, L] on 'cuda' -> complex64 [K, 1, 256, Tc], row k
+        = frames [k H - P, k H + H) of ``analyze(sig)`` bit for bit, P = Tc - H, zeros before frame 0 and past L // 128 + 1;
+        K = ``chunked.plan_trailing(L // 128 + 1, Tc, H, 0)[0]``."""
+        from flowmse_amd import _lib
+        from flowmse_amd.chunked import plan_trailing
+        sig = sig.contiguous().float()
+        if sig.dim() != 2 or sig.shape[0] != 1:
+            raise ValueError(f"analyze_trailing takes one recording [1, L], got {tuple(sig.shape)}")
+        L = sig.shape[1]
+        K = plan_trailing(L // self.hop_length + 1, Tc, H, 0)[0]
+        out = torch.empty(K, 1, 256, int(Tc), dtype=torch.complex64, device=sig.device)
+        with torch.cuda.device(sig.device):
+            _lib.check(_lib.lib.flowse_stft_compress_trailing(_lib.ptr(sig), L, float(scale), _lib.ptr(out), K, int(Tc), int(H),
+                                                              float(self.spec_factor), float(self.spec_abs_exponent),
+                                                              _lib.current_stream()))
+        return out
+
+    def synthesize_trailing(self, chunks, H, X, length, scale=1.0):
+        """Trailing seam rule + spec_back + istft + rescale in one kernel: chunks complex64 [K, 1, 256, Tc] that slide by
+        ``H`` frames and cross-fade over ``X`` -> [1, length] (``chunked.blend_trailing_reference`` states the rule); all
+        K H frames take part in the overlap-add."""
+        from flowmse_amd import _lib
+        chunks = chunks.contiguous()
+        K, _, F, Tc = chunks.shape
+        out = torch.empty(1, length, dtype=torch.float32, device=chunks.device)
+        with torch.cuda.device(chunks.device):
+            _lib.check(_lib.lib.flowse_istft_decompress_trailing(_lib.ptr(chunks), K, Tc, int(H), int(X),
+                                                                 float(self.spec_factor), float(self.spec_abs_exponent),
+                                                                 _lib.ptr(out), length, float(scale), _lib.current_stream()))
+        return out
+
     # ---- rows and stacks from many recordings (flowmse_amd.pooled) ------------------------------------
     def analyze_rows(self, rows, Tw):
         """The input rows of ONE sampler call from several signals in one kernel: ``rows`` is a list of

@@ -73,6 +73,19 @@ launch per step, and with ``--output_rate input`` back again in a second one, as
 -f S16_LE -r 48000 -c 2 | python -m flowmse_amd.enhance --live --live_channels 2 --live_rate 48000 --live_resample --output_rate
 input --ckpt m.ckpt | aplay -t raw -f S16_LE -r 48000 -c 2``.  ``--live_norm`` applies to the 16 kHz signal; ``--live_block``
 and the latency line count frames at ``--live_rate``.
+
+Trailing chunks.  ``--hop_frames H [--fade_frames X]`` (``flowmse_amd.chunked.enhance_trailing``; opt-in and NOT the
+reference's computation) slides the chunk of ``--chunk_frames`` frames by ``H`` frames (even, 4 .. chunk_frames), uses its
+older ``chunk_frames - H`` frames as context only and keeps its tail, cross-faded over the ``X`` frames (default 0; at most
+``H``, ``H + X <= chunk_frames``) before each hop.  With ``--live`` the output then trails the input by ``128 (H + X) + 382``
+samples instead of ``128 chunk_frames + 382`` -- 0.184 s at ``--chunk_frames 64 --hop_frames 16 --fade_frames 4`` -- at
+``chunk_frames / H`` network rows per ``H`` frames: ``arecord -t raw -f S16_LE -r 16000 | python -m flowmse_amd.enhance --live
+--chunk_frames 64 --hop_frames 16 --fade_frames 4 --ckpt m.ckpt | aplay ...``.  In file mode every recording goes through
+``enhance_trailing`` (``--resample`` works around it as around ``enhance_long``), and the bytes of ``--batch 1`` are those of
+``--live`` with the same flags when ``--live_norm`` is the recording's peak.  One mono recording or stream under keyed noise:
+with ``--pool``, ``--samples`` > 1, ``--channels all``, ``--live_channels`` > 1, ``--noise torch`` or an explicit
+``--overlap_frames`` the flags are refused by name before anything is enhanced, as is ``--fade_frames`` without
+``--hop_frames``.  ``H`` and ``X`` have not been chosen by listening: no released checkpoint was at hand.
 """
 import argparse
 import csv
@@ -83,7 +96,7 @@ import types
 
 import torch
 
-from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, enhance_long, plan_chunks
+from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, enhance_long, enhance_trailing, plan_chunks, plan_trailing
 from flowmse_amd.ensemble import samples_arg
 from flowmse_amd.evaluate import _load_model, _seconds_arg, _synthetic_pairs, _write_wav
 from flowmse_amd.live import PCM_FORMATS, pcm_decode, pcm_deinterleave, pcm_encode, pcm_interleave
@@ -127,8 +140,18 @@ def build_parser():
                          "values a file agrees to fp32 tolerance (about 1e-5 relative), not byte for byte")
     ap.add_argument("--chunk_frames", type=int, default=CHUNK_FRAMES,
                     help="frames per chunk, a multiple of 64 (default 256, the training crop)")
-    ap.add_argument("--overlap_frames", type=int, default=OVERLAP_FRAMES,
-                    help="frames two neighbouring chunks share and cross-fade over: even, at most chunk_frames / 2")
+    ap.add_argument("--overlap_frames", type=int, default=None,
+                    help=f"frames two neighbouring chunks share and cross-fade over: even, at most chunk_frames / 2 (default "
+                         f"{OVERLAP_FRAMES})")
+    ap.add_argument("--hop_frames", type=int, default=None, metavar="H",
+                    help="trailing chunks (flowmse_amd.chunked.enhance_trailing; not the reference's computation): slide the "
+                         "chunk by H frames (even, 4..chunk_frames), use its older chunk_frames - H frames as context only and "
+                         "keep its tail. With --live the output trails the input by 128 (H + X) + 382 samples instead of 128 "
+                         "chunk_frames + 382, at chunk_frames / H network rows per H frames. One mono recording or stream, keyed "
+                         "noise; not with --overlap_frames, --pool, --samples > 1, --channels all or --live_channels > 1")
+    ap.add_argument("--fade_frames", type=int, default=0, metavar="X",
+                    help="needs --hop_frames. Frames before each hop that are cross-faded from the chunk before (0..H, H + X "
+                         "<= chunk_frames; default 0)")
     ap.add_argument("--noise", choices=("keyed", "torch"), default="keyed",
                     help="prior noise. keyed: the counter-based stream addressed by (seed, file name, bin, absolute "
                          "frame). torch: the process-wide generator, consumed in processing order")
@@ -228,9 +251,33 @@ def _check_live(args, ap):
     return args
 
 
+def _check_trailing(args, ap):
+    """``--hop_frames`` / ``--fade_frames``: one mono recording or stream under keyed noise, in the geometry of
+    ``plan_trailing``; everything that pools rows, draws several times or names the other geometry is refused by name."""
+    if args.hop_frames is None:
+        if args.fade_frames:
+            ap.error(f"--fade_frames {args.fade_frames} needs --hop_frames")
+        return
+    for given, name in ((args.pool, "--pool"), (args.samples > 1, f"--samples {args.samples}"),
+                        (args.channels == "all", "--channels all"),
+                        (args.live_channels > 1, f"--live_channels {args.live_channels}"),
+                        (args.noise != "keyed", f"--noise {args.noise}"),
+                        (args.overlap_frames is not None, f"--overlap_frames {args.overlap_frames}")):
+        if given:
+            ap.error(f"--hop_frames does not take {name}: trailing chunks enhance one mono recording or stream with keyed "
+                     "noise, and their overlap is chunk_frames - hop_frames")
+    try:
+        plan_trailing(1, args.chunk_frames, args.hop_frames, args.fade_frames)
+    except ValueError as e:
+        ap.error(str(e))
+
+
 def parse_args(argv=None, ap=None):
     ap = ap or build_parser()
     args = ap.parse_args(argv)
+    _check_trailing(args, ap)
+    if args.overlap_frames is None:
+        args.overlap_frames = OVERLAP_FRAMES
     if args.live:
         return _check_live(args, ap)
     if args.live_rate != SAMPLE_RATE:
@@ -382,16 +429,23 @@ def resampling_rates(files):
     return rates
 
 
-def enhance_recording(model, y, sr, output_rate="16000", **kw):
+def enhance_recording(model, y, sr, output_rate="16000", hop_frames=None, fade_frames=0, **kw):
     """One recording ``y`` [1, samples] on the device at ``sr`` Hz through resample -> ``enhance_long(**kw)`` [-> resample
     back].  Returns (waveform as numpy, its sample rate, frames of the 16 kHz signal).  At 16 kHz this is ``enhance_long``
     and nothing else.  ``output_rate="input"``: the enhanced waveform stays on the device, is resampled to ``sr`` there and
-    trimmed to the input's sample count."""
+    trimmed to the input's sample count.  With ``hop_frames`` the core is ``enhance_trailing(hop_frames, fade_frames, **kw)``
+    (``overlap_frames`` is not read)."""
+    core = enhance_long
+    if hop_frames is not None:
+        kw.pop("overlap_frames", None)
+
+        def core(model, y16, **kw):
+            return enhance_trailing(model, y16, hop_frames=hop_frames, fade_frames=fade_frames, **kw)
     y16 = resample(y, sr, SAMPLE_RATE)
     frames = y16.size(1) // 128 + 1
     if output_rate != "input" or sr == SAMPLE_RATE:
-        return enhance_long(model, y16, **kw), SAMPLE_RATE, frames
-    x_hat = enhance_long(model, y16, as_tensor=True, **kw)
+        return core(model, y16, **kw), SAMPLE_RATE, frames
+    x_hat = core(model, y16, as_tensor=True, **kw)
     return resample(x_hat[None], SAMPLE_RATE, sr)[0, :y.size(1)].cpu().numpy(), sr, frames
 
 
@@ -403,6 +457,8 @@ def write_settings(out_dir, args, model, epoch, noise_seed, resampled=()):
         f.write(f"sigma_min: {model.ode.sigma_min}\nsigma_max: {model.ode.sigma_max}\nN: {args.N}\n")
         f.write(f"precision: {args.precision}\nbatch: {args.batch}\n")
         f.write(f"chunk_frames: {args.chunk_frames}\noverlap_frames: {args.overlap_frames}\n")
+        if getattr(args, "hop_frames", None) is not None:          # without the flag the file is what it always was
+            f.write(f"hop_frames: {args.hop_frames}\nfade_frames: {args.fade_frames}\n")
         f.write(f"resample: {args.resample}\noutput_rate: {args.output_rate}\n")
         if args.pool:                                              # without the flag the file is what it always was
             f.write(f"pool: {args.pool}\nchannels: {args.channels}\n")
@@ -429,7 +485,7 @@ def run_live(args, ap):
         live = LiveEnhancer(model, norm=args.live_norm, key=utterance_key("live"), seed=seed, chunk_frames=args.chunk_frames,
                             overlap_frames=args.overlap_frames, N=args.N, T_rev=args.reverse_starting_point,
                             t_eps=args.last_eval_point, odesolver=args.odesolver, input_rate=args.live_rate,
-                            output_rate=args.output_rate)
+                            output_rate=args.output_rate, hop_frames=args.hop_frames, fade_frames=args.fade_frames)
         if args.live_rate != SAMPLE_RATE:
             print(f"live: {args.live_rate} Hz in, {args.live_rate if args.output_rate == 'input' else SAMPLE_RATE} Hz out",
                   file=sys.stderr)
@@ -541,7 +597,7 @@ def main(argv=None):
                 model, y, rates[i], args.output_rate, chunk_frames=args.chunk_frames, overlap_frames=args.overlap_frames,
                 batch=args.batch, N=args.N, T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
                 odesolver=args.odesolver, noise_key=utterance_key(name) if keyed else None,
-                noise_seed=seed if keyed else 0)
+                noise_seed=seed if keyed else 0, hop_frames=args.hop_frames, fade_frames=args.fade_frames)
             _write_wav(os.path.join(args.output, name), x_hat, sr_out)
             frames += n_frames
     write_settings(args.output, args, model, epoch, seed,

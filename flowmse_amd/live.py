@@ -59,6 +59,38 @@ input)`` are final at the input rate; ``latency_samples`` takes the worst case o
 ``3 (128 Tc + 382) + 58`` samples, 58 being the two filters' ``28 + 30``).  With the defaults nothing of this exists: the
 object makes the calls it made before and returns the same bytes.
 
+Trailing chunks (``hop_frames=H``, ``fade_frames=X``; opt-in, NOT the reference's computation).  The latency above is the
+chunk: what chunk ``k`` makes final starts at its first frame.  With ``hop_frames`` the chunk of ``Tc`` frames slides by a
+small hop ``H`` instead; its older ``P = Tc - H`` frames are context only and only its tail is kept (``chunked.plan_trailing``
+has the geometry and the seam rule, ``chunked.enhance_trailing`` is the file call).  **Contract:** the concatenated output
+is, bit for bit, ``enhance_trailing(model, y, chunk_frames, hop_frames, fade_frames, batch=1, noise_key=key,
+noise_seed=seed, ...)`` of the finished recording when ``norm`` equals ``max|y|``, whatever the push sizes; through the
+library's ``flowse_stft_compress_trailing_window`` and ``flowse_istft_decompress_trailing_window``.  Schedule, checked against
+the same index ranges:
+
+* Chunk ``k`` holds frames ``[k H - P, k H + H)`` (those ``< 0`` are zero: the first chunks are right-aligned, so the latency
+  holds from the first sample on) and is ready at ``n_k = 128 (k H + H - 1) + 255`` samples.  A chunk that became ready this
+  way is never the last: ``L >= n_k`` gives ``L // 128 + 1 > (k + 1) H`` frames, so ``K = ceil(T / H) >= k + 2``.
+* After chunk ``k`` (not the last) frames ``< (k + 1) H - X`` are final -- the ``X`` frames before ``(k + 1) H`` wait for the
+  cross-fade into chunk ``k + 1`` -- and so are the samples ``s < E_k = 128 ((k + 1) H - X) - 255``, clamped at 0; the samples
+  ``[E_{k-1}, E_k)`` are returned then.  They lie under frames from ``k H - X - 3`` on, which chunk ``k - 1`` owns
+  (``(k H - 3) // H = k - 1``); those are plain frames of it when ``H - X >= 3``, and chunk ``k - 1`` suffices as history.
+  Otherwise (``(8, 8)``, ``(4, 2)``, ...) they are faded frames whose other half is chunk ``k - 2``: two previous chunks are kept.
+* Worst algorithmic latency ``n_k - E_{k-1} = 128 (H + X) + 382`` samples: 0.184 s at ``(16, 4)``, 0.104 s at ``(8, 2)``; the
+  sampler's compute time comes on top, and it is spent ``Tc / H`` times as often (``Tc / H`` network rows per ``H`` frames).
+* After chunk ``k`` the samples before ``128 ((k + 1) H - P) - 256`` are dropped (clamped at 0): one more than the first
+  frame of chunk ``k + 1`` reads, for the same right reflection as above.  Before a push at most ``128 Tc + 382`` samples are
+  held, so the buffer is sized to that plus the largest push from the first push on.
+* ``finish()`` fixes ``L`` and ``K = ceil(T / H)``, samples the waiting chunks with the right reflection and the zero frames
+  ``>= T``, and returns ``[E_last, L)``.  There is no ``K = 1`` case: a recording shorter than one hop is one right-aligned
+  chunk.  A stream so long that ``k H + Tc`` passes ``2^31 - 2``, the last frame the keyed noise addresses, is refused by name.
+* ``input_rate`` / ``output_rate`` work unchanged through the resamplers around this 16 kHz path, and ``latency_samples`` takes
+  the worst case over ``k`` by the method above with this schedule's ``n_k`` and ``E_k``.
+
+Not in this geometry: ``LivePool`` / ``--live_channels`` (trailing rows of several sessions in one call are the obvious
+follow-up; ``LivePool.open`` refuses the keywords by name), ``--streams``, several GPUs, ensembles.  ``H`` and ``X`` were not
+chosen by listening -- no released checkpoint is at hand -- so the defaults are chosen values, not tuned ones.
+
 Out of scope: ``--streams`` lanes, several GPUs, time-varying or non-rational rates, noise that is not keyed, and any CPU or
 oracle path -- the oracle composition is ``enhance_long``'s, and this module is pinned to ``enhance_long``.  Rows of several
 sessions pooled into one sampler call, and several channels, are ``flowmse_amd.livepool``'s, which imports this module's
@@ -67,7 +99,7 @@ arithmetic; a ``LiveEnhancer`` stays one mono stream at width 1.
 import numpy as np
 import torch
 
-from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, plan_chunks
+from flowmse_amd.chunked import CHUNK_FRAMES, NOISE_FRAME_MAX, OVERLAP_FRAMES, plan_chunks, plan_trailing
 
 HOP, PADC = 128, 255                # hop_length and n_fft // 2 of the released STFT, the only one the kernels cover
 RATE = 16000                        # the network's sample rate
@@ -79,13 +111,33 @@ def _ready_at(k, Tc, hop):
     return HOP * (k * hop + Tc - 1) + PADC
 
 
-def live_plan(n_samples, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES, finished=False):
+def _ready_trailing(k, H):
+    """``n_k`` of the trailing schedule: chunk ``k`` ends with frame ``k H + H - 1``."""
+    return HOP * (k * H + H - 1) + PADC
+
+
+def _final_trailing(k, H, X):
+    """``E_k`` of the trailing schedule (``E_{-1} = 0``): the output samples final once chunk ``k`` is sampled."""
+    return max(HOP * ((k + 1) * H - X) - PADC, 0) if k >= 0 else 0
+
+
+def live_plan(n_samples, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES, finished=False, hop_frames=None, fade_frames=0):
     """``(chunks_ready, samples_final)`` after ``n_samples`` samples of a recording (module docstring): how many chunks a
     ``LiveEnhancer`` has sampled and how many output samples it has returned.  ``finished``: the recording has ended at
-    ``n_samples`` -- all ``K`` chunks, all samples.  Host arithmetic only; geometry errors are ``plan_chunks``'."""
+    ``n_samples`` -- all ``K`` chunks, all samples.  Host arithmetic only; geometry errors are ``plan_chunks``'.  With
+    ``hop_frames`` the trailing schedule (``To`` is not read; geometry errors are ``plan_trailing``'s)."""
     n = int(n_samples)
     if n < 0:
         raise ValueError(f"live_plan: n_samples must be >= 0, got {n}")
+    if hop_frames is not None:
+        H, X = int(hop_frames), int(fade_frames)
+        plan_trailing(1, Tc, H, X)
+        if finished:
+            return plan_trailing(n // HOP + 1, Tc, H, X)[0], n
+        if n < _ready_trailing(0, H):
+            return 0, 0
+        ready = (n - _ready_trailing(0, H)) // (HOP * H) + 1
+        return ready, _final_trailing(ready - 1, H, X)
     _, hop, _ = plan_chunks(1, Tc, To)
     if finished:
         return plan_chunks(n // HOP + 1, Tc, To)[0], n
@@ -144,24 +196,34 @@ def pcm_interleave(x):
     return np.ascontiguousarray(x.T).reshape(-1)
 
 
-def latency_samples(Tc=CHUNK_FRAMES, input_rate=RATE, output_rate="16000", To=OVERLAP_FRAMES):
+def latency_samples(Tc=CHUNK_FRAMES, input_rate=RATE, output_rate="16000", To=OVERLAP_FRAMES, hop_frames=None, fade_frames=0):
     """Worst algorithmic latency in samples at ``input_rate``.  At 16 kHz: ``max_k (n_k - E_{k-1}) = 128 Tc + 382``; it does
     not depend on the overlap.  At another rate it follows from the three schedules (module docstring, "Other rates"): chunk
     ``k`` runs when ``A_k = q_in(n_k - 1) + 1`` input samples have arrived, and what was returned before it covers
     ``R_k`` input samples, ``stream_plan(E_{k-1}, 16000 -> input)`` under ``output_rate="input"`` and
     ``E_{k-1} input_rate div 16000`` at 16 kHz output; the value is ``max_k (A_k - R_k)``.  Both terms are floors over the
-    reduced ``up`` of the input ratio, so ``k = 0 .. up`` covers every case."""
+    reduced ``up`` of the input ratio, so ``k = 0 .. up`` covers every case.  With ``hop_frames`` (and ``fade_frames``) the
+    trailing schedule: ``128 (H + X) + 382`` at 16 kHz, and the same method with its ``n_k`` and ``E_k`` at another rate."""
     Tc = int(Tc)
+    trailing = hop_frames is not None
+    if trailing:
+        H, X = int(hop_frames), int(fade_frames)
+        plan_trailing(1, Tc, H, X)
     if int(input_rate) == RATE:
-        return HOP * Tc + 382
+        return HOP * (H + X) + 382 if trailing else HOP * Tc + 382
     from flowmse_amd.resample import rational, stream_plan
-    _, hop, _ = plan_chunks(1, Tc, To)
+    if not trailing:
+        _, hop, _ = plan_chunks(1, Tc, To)
     up, down = rational(input_rate, RATE)
     half = 10 * max(up, down)
     worst = 0
     for k in range(up + 1):
-        arrived = (half + (_ready_at(k, Tc, hop) - 1) * down) // up + 1
-        e = HOP * k * hop - PADC if k else 0
+        if trailing:
+            arrived = (half + (_ready_trailing(k, H) - 1) * down) // up + 1
+            e = _final_trailing(k - 1, H, X)
+        else:
+            arrived = (half + (_ready_at(k, Tc, hop) - 1) * down) // up + 1
+            e = HOP * k * hop - PADC if k else 0
         returned = stream_plan(e, down, up) if output_rate == "input" else e * down // up
         worst = max(worst, arrived - returned)
     return worst
@@ -175,9 +237,16 @@ class LiveEnhancer:
     returns the network's rate, ``"input"`` the input's (module docstring, "Other rates")."""
 
     def __init__(self, model, *, norm, key, seed=0, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES, N=5, T_rev=1.0,
-                 t_eps=0.03, odesolver="euler", device=None, input_rate=RATE, output_rate="16000"):
+                 t_eps=0.03, odesolver="euler", device=None, input_rate=RATE, output_rate="16000", hop_frames=None,
+                 fade_frames=0):
         _, self.hop, _ = plan_chunks(1, chunk_frames, overlap_frames)
         self.Tc, self.To = int(chunk_frames), int(overlap_frames)
+        self.H = self.X = None                              # hop_frames: the trailing schedule (module docstring)
+        if hop_frames is not None:
+            plan_trailing(1, chunk_frames, hop_frames, fade_frames)
+            self.H, self.X = int(hop_frames), int(fade_frames)
+        elif fade_frames:
+            raise ValueError(f"LiveEnhancer: fade_frames={fade_frames} needs hop_frames (the trailing schedule)")
         self.input_rate = int(input_rate)
         if output_rate not in ("16000", "input"):
             raise ValueError(f"LiveEnhancer: output_rate is '16000' or 'input', got {output_rate!r}")
@@ -211,6 +280,8 @@ class LiveEnhancer:
         self._solver = dict(N=int(N), T_rev=T_rev, t_eps=t_eps)
         self._odesolver, self._seed = odesolver, int(seed)
         self._keep_two = self.Tc - 2 * self.To < 3          # To = Tc / 2: the emitted range reaches a blended frame of chunk k-1
+        if self.H is not None:
+            self._keep_two = self.H - self.X < 3
         with torch.cuda.device(self.device):
             dnn.reserve(1, 256, self.Tc)
         self._buf = torch.empty(0, dtype=torch.float32, device=self.device)
@@ -225,7 +296,7 @@ class LiveEnhancer:
     # ---- public state -----------------------------------------------------------------------------------------
     @property
     def latency_samples(self):
-        return latency_samples(self.Tc, self.input_rate, self.output_rate, self.To)
+        return latency_samples(self.Tc, self.input_rate, self.output_rate, self.To, self.H, self.X or 0)
 
     def state_bytes(self):
         """Device bytes this object holds between pushes: the sample buffer (its capacity), the previous chunks and the
@@ -263,7 +334,10 @@ class LiveEnhancer:
         self._append(samples)
         out = []
         with torch.cuda.device(self.device):
-            while self._in16 >= _ready_at(self._k, self.Tc, self.hop):
+            if self.H is not None:
+                while self._in16 >= _ready_trailing(self._k, self.H):
+                    out.append(self._chunk_trailing(self._k, None))
+            while self.H is None and self._in16 >= _ready_at(self._k, self.Tc, self.hop):
                 out.append(self._chunk(self._k, None))
         return self._deliver(out, as_tensor)
 
@@ -282,10 +356,16 @@ class LiveEnhancer:
         if self._rs_in is not None:
             with torch.cuda.device(self.device):
                 self._append(self._rs_in.finish(as_tensor=True))
-        K = plan_chunks(L // HOP + 1, self.Tc, self.To)[0]
+        if self.H is not None:
+            K = plan_trailing(L // HOP + 1, self.Tc, self.H, self.X)[0]
+        else:
+            K = plan_chunks(L // HOP + 1, self.Tc, self.To)[0]
         out = []
         with torch.cuda.device(self.device):
-            if K == 1:                                      # chunk 0 never became ready: enhance_waveform's one padded row
+            if self.H is not None:                          # no K = 1 case: a short recording is one right-aligned chunk
+                while self._k < K:
+                    out.append(self._chunk_trailing(self._k, L, last=self._k == K - 1))
+            elif K == 1:                                   # chunk 0 never became ready: enhance_waveform's one padded row
                 out.append(self._single(L))
             else:
                 while self._k < K:
@@ -311,7 +391,10 @@ class LiveEnhancer:
         if n == 0:
             return
         if self._n + n > self._buf.numel():                 # grow once per new largest push; contents move to the front
-            grown = torch.empty(self._n + n, dtype=torch.float32, device=self.device)
+            size = self._n + n
+            if self.H is not None:                          # before a push at most n_k - 1 - (128 (k H - P) - 256) samples are held,
+                size = max(size, HOP * self.Tc + 382 + n)   # whatever k: the capacity follows the largest push from the first one on
+            grown = torch.empty(size, dtype=torch.float32, device=self.device)
             grown[:self._n] = self._buf[:self._n]
             self._buf = grown
         self._buf[self._n:self._n + n] = samples.to(self.device)
@@ -322,7 +405,8 @@ class LiveEnhancer:
         """Samples [lo, hi) of the recording divided by ``norm`` as ``enhance_long`` divides them: on the device, one
         elementwise torch division by the Python float."""
         if self.norm is None:                               # norm="first": the peak of [0, n_0), or of all there is
-            n0 = min(_ready_at(0, self.Tc, self.hop), self._in16)
+            n0 = _ready_at(0, self.Tc, self.hop) if self.H is None else _ready_trailing(0, self.H)
+            n0 = min(n0, self._in16)
             peak = self._buf[:n0].abs().max().item()
             self.norm = peak if peak > 0.0 else 1.0
         return self._buf[lo - self._s0:hi - self._s0] / self.norm
@@ -367,6 +451,38 @@ class LiveEnhancer:
         self._prev2, self._prev = (self._prev if self._keep_two else None), cur
         self._k = k + 1
         self._drop(max(HOP * (k + 1) * hop - KEEP, 0))
+        return out
+
+    def _chunk_trailing(self, k, L, last=False):
+        """``_chunk`` on the trailing schedule: chunk ``k`` = frames ``[k H - P, k H + H)``, the keyed stream at ``k H``."""
+        from flowmse_amd import _lib
+        Tc, H, X = self.Tc, self.H, self.X
+        if k * H + Tc > NOISE_FRAME_MAX:
+            raise ValueError(f"LiveEnhancer: the noise stream is addressed up to frame {NOISE_FRAME_MAX}; chunk {k} ends at "
+                             f"stream frame k hop_frames + chunk_frames = {k * H + Tc}")
+        lo = max(HOP * max(k * H - (Tc - H), 0) - PADC, 0)
+        hi = _ready_trailing(k, H) if L is None else min(_ready_trailing(k, H), L)
+        if L is not None:                                   # the right reflection may read one sample before the first frame
+            lo = max(min(lo, L - KEEP), self._s0)
+        win = self._normalised(lo, hi)
+        Y = torch.empty(1, 1, 256, Tc, dtype=torch.complex64, device=self.device)
+        _lib.check(_lib.lib.flowse_stft_compress_trailing_window(_lib.ptr(win), lo, hi - lo, 1.0, k, Tc, H,
+                                                                 -1 if L is None else L, _lib.ptr(Y),
+                                                                 float(self._dm.spec_factor), float(self._dm.spec_abs_exponent),
+                                                                 _lib.current_stream()))
+        cur = self._sample(Y, k * H)
+        e0 = self._out16
+        e1 = L if last else _final_trailing(k, H, X)
+        out = torch.empty(e1 - e0, dtype=torch.float32, device=self.device)
+        if e1 > e0:                                         # E_0 = 0 when the fade reaches back to the first frames
+            _lib.check(_lib.lib.flowse_istft_decompress_trailing_window(
+                _lib.ptr(self._prev2), _lib.ptr(self._prev), _lib.ptr(cur), k, Tc, H, X, int(last), L if last else 0,
+                float(self._dm.spec_factor), float(self._dm.spec_abs_exponent), _lib.ptr(out), e0, e1 - e0, float(self.norm),
+                _lib.current_stream()))
+        self._out16 = e1
+        self._prev2, self._prev = (self._prev if self._keep_two else None), cur
+        self._k = k + 1
+        self._drop(max(HOP * ((k + 1) * H - (Tc - H)) - KEEP, 0))
         return out
 
     def _single(self, L):

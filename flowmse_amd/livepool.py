@@ -361,11 +361,15 @@ class LivePool:
         self.stats = dict(steps=0, calls=0, rows=0, fillers=0, resample_launches=0)
         self.last_step = dict(calls=0, rows=0, fillers={}, resample_launches=0)     # fillers: per bucket width
 
-    def open(self, keys, norm, input_rate=RATE, output_rate="16000"):
+    def open(self, keys, norm, input_rate=RATE, output_rate="16000", hop_frames=None, fade_frames=0):
         """A new session: ``keys`` one 64-bit key, or one per channel; ``norm`` a positive float or ``"first"`` (it applies to
         the 16 kHz signal); ``input_rate``: the rate of what is pushed, any ratio to 16 kHz that ``resample.rational`` admits
         (another is refused here, by name); ``output_rate``: ``"16000"``, or ``"input"`` for as many samples back as were
-        pushed, at their rate."""
+        pushed, at their rate.  ``hop_frames`` / ``fade_frames`` (the trailing chunks of ``LiveEnhancer``) are refused by name:
+        the pool runs the two-chunks-over-a-frame geometry only."""
+        if hop_frames is not None or fade_frames:
+            raise ValueError(f"LivePool.open: hop_frames={hop_frames} fade_frames={fade_frames}: trailing chunks are not pooled "
+                             "(one LiveEnhancer(hop_frames=...) per mono stream runs them)")
         s = LiveSession(self, keys, norm, input_rate, output_rate)
         self.sessions.append(s)
         return s

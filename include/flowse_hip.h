@@ -392,6 +392,48 @@ int flowse_stft_compress_window_rows(const flowse_window_row* rows, int R, int T
 int flowse_istft_decompress_window_rows(const flowse_window_out* rows, int R, int Tc, int hop, float factor, float exponent,
                                         void* stream);
 
+/* ---- trailing chunks (opt-in: flowmse_amd.chunked.enhance_trailing, `enhance --hop_frames H`; NOT the reference's
+ * computation) -------------------------------------------------------------------------------------------------------
+ * A non-causal network on a stream with a latency set by a small hop: chunks of Tc frames (a multiple of 64) slide by H
+ * frames (even, 4 <= H <= Tc); the older P = Tc - H frames of a chunk are context only.  Chunk k holds the recording's
+ * frames [k H - P, k H + H); frames < 0 (the first chunks are right-aligned against zero frames before the recording) and
+ * frames >= T = L / 128 + 1 are zero.  K chunks make Tg = K H >= T frames.  Seam rule, with a cross-fade of X frames
+ * (0 <= X <= H, H + X <= Tc): frame t belongs to chunk k = min((t + X) / H, K - 1) at j = t - k H + P; for k > 0 and
+ * t < k H its value is a + w (b - a), a = chunk k - 1 at j + H, b = chunk k at j, w = (t - (k H - X) + 0.5) / X, taken on
+ * the compressed value before spec_back; otherwise chunk k at j (chunked.blend_trailing_reference states it in float64).
+ * All four calls only enqueue on `stream`, allocate nothing and do not synchronise.  Null pointers -> FLOWSE_ERR_ARG; a
+ * geometry outside the above, and every FLOWSE_ERR_SHAPE below, is answered before any launch with the entry's name and
+ * the values in flowse_last_error(), and leaves the output untouched.
+ * flowse_stft_compress_trailing: the K rows complex64 [K,1,256,Tc] of ONE recording sig float32 [L] in one launch, by the
+ * per-frame code of flowse_stft_compress_chunks: every frame 0 <= t < T is frame t of flowse_stft_compress(sig, B = 1) bit
+ * for bit.  L > 255, 1 <= K <= 65535, T <= K H <= 2^23 - Tc.
+ * flowse_istft_decompress_trailing: seam rule + spec_back + inverse STFT + rescale in one launch: chunks_c64
+ * [K,1,256,Tc] -> out float32 [Lout], 1 <= Lout <= 128 (Tg - 1) + 255.  All Tg frames take part in the overlap-add, as in
+ * flowse_istft_decompress_chunks, and the per-sample code is the same: chunks cut from one spectrogram [1,1,256,Tg] give
+ * flowse_istft_decompress of it bit for bit.  An output sample reads at most 4 frames from at most 2 chunks.
+ * flowse_stft_compress_trailing_window: row k alone, complex64 [1,1,256,Tc], from buf float32 [n] = samples [s0, s0 + n)
+ * of the recording; bit for bit row k of flowse_stft_compress_trailing on the whole recording.  L_total = -1 while the
+ * recording is open (no right reflection, no zero frames past the end), else its length (> 255, >= s0 + n).  The window
+ * must hold every sample the frames [max(k H - P, 0), min(k H + H, T)) read (flowse_stft_compress_window has the rules);
+ * (k + 1) H <= 2^40.
+ * flowse_istft_decompress_trailing_window: the output samples [e0, e0 + n_out) of flowse_istft_decompress_trailing on the
+ * whole stack, bit for bit, from the chunks k-2 (prev2_c64), k-1 (prev_c64) and k (cur_c64), each complex64 [1,256,Tc]; a
+ * chunk the range does not read may be null.  last != 0: chunk k is the last (K = k + 1) and L the recording's length,
+ * e0 + n_out <= L <= 128 (Tg - 1) + 255; last == 0: L is not read, and frames from (k + 1) H - X on are not final.  The
+ * samples [128 (k H - X) - 255, 128 ((k + 1) H - X) - 255) that become final with chunk k lie under frames from
+ * k H - X - 3 on: chunks k - 1 and k when H - X >= 3, chunk k - 2 as well otherwise.  A range under a frame that needs a
+ * chunk other than those given -> FLOWSE_ERR_SHAPE.  1 <= n_out <= 2^30, (k + 1) H <= 2^40.  All sample, frame and chunk
+ * indices of the two window calls are 64-bit; both are stateless. */
+int flowse_stft_compress_trailing(const float* sig, int L, float scale_in, void* out_c64, int K, int Tc, int H, float factor,
+                                  float exponent, void* stream);
+int flowse_istft_decompress_trailing(const void* chunks_c64, int K, int Tc, int H, int X, float factor, float exponent,
+                                     float* out, int Lout, float scale_out, void* stream);
+int flowse_stft_compress_trailing_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t k, int Tc, int H,
+                                         int64_t L_total, void* out_c64, float factor, float exponent, void* stream);
+int flowse_istft_decompress_trailing_window(const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k, int Tc,
+                                            int H, int X, int last, int64_t L, float factor, float exponent, float* out,
+                                            int64_t e0, int64_t n_out, float scale_out, void* stream);
+
 /* ---- ensembles of draws (opt-in: flowmse_amd.ensemble, `--samples D`; NOT the reference's computation, which draws once)
  * flowse_istft_decompress_ensemble: flowse_istft_decompress_stacks over D draws per stack.  Chunk k of draw d of stack s is
  * row s * stack_stride + d * draw_stride + k of chunks_c64 (rows of 256 * Tc complex64 values; offsets in 64 bits).  The
