@@ -72,17 +72,59 @@ def blend_chunks_reference(chunks, hop):
     return out
 
 
-def _chunk_noise(z, noise_key, Y_like, Tg):
-    """The one ``[1,1,F,Tg]`` noise tensor of a recording when the noise is not keyed (explicit ``z`` or one draw from
-    the process-wide generator), else None."""
+def _recording_noise(z, noise_key, Y_like, frames, who, what=""):
+    """The one ``[1,1,F,frames]`` noise tensor of a recording when the noise is not keyed (explicit ``z`` or one draw from
+    the process-wide generator), else None.  ``who`` / ``what``: the caller's name and its word for ``frames``."""
     if noise_key is not None:
         return None
     F = Y_like.shape[2]
     if z is None:
-        return torch.randn_like(torch.empty(1, 1, F, Tg, dtype=torch.complex64, device=Y_like.device))
-    if tuple(z.shape) != (1, 1, F, Tg):
-        raise ValueError(f"enhance_long: z must be the recording's noise [1,1,{F},{Tg}], got {tuple(z.shape)}")
+        return torch.randn_like(torch.empty(1, 1, F, frames, dtype=torch.complex64, device=Y_like.device))
+    if tuple(z.shape) != (1, 1, F, frames):
+        raise ValueError(f"{who}: z must be the recording's noise [1,1,{F},{frames}]{what}, got {tuple(z.shape)}")
     return z.to(Y_like.device)
+
+
+def _enhance_rows(model, y, sched, K, *, who, pad, analyze, synthesize, blend, what="", batch, odesolver, z, noise_key, noise_seed,
+                  VF_fn, device, as_tensor, **solver):
+    """The body of ``enhance_long`` and ``enhance_trailing``: ``K`` rows of ``sched.Tc`` frames cut at ``sched.noise_frame0(k)``,
+    sampled in groups of ``batch`` and put together.  Per geometry: ``analyze(y)`` -> the rows, ``synthesize(sample, norm)`` ->
+    the waveform, both one HIP launch; ``blend(sample)`` -> the float64 seam rule; ``pad = (left, frames)``: the zero frames
+    before the recording and the length of the stream the oracle path and the noise are cut from; ``solver``: ``N``,
+    ``T_rev``, ``t_eps``."""
+    from flowmse_amd.evaluate import _analyze, _fused_ok
+    from flowmse_amd.sampling import get_white_box_solver
+    Tc, L, (left, frames) = sched.Tc, y.size(1), pad
+    cut = lambda x, ks: torch.cat([x[..., sched.noise_frame0(k):sched.noise_frame0(k) + Tc] for k in ks], dim=0)  # noqa: E731
+    norm_factor = y.abs().max().item()
+    y = y.to(device)
+    fused = _fused_ok(model, [y], VF_fn)
+    if fused:                      # the chunk rows straight from the samples: one HIP kernel, no global spectrogram
+        Y = analyze(y / norm_factor)
+        with torch.cuda.device(device):
+            model.dnn.reserve(batch, Y.shape[2], Tc)     # the workspace of a full group, whatever K is
+    else:
+        S = _analyze(model, y / norm_factor, False, pad=False)
+        Y = cut(torch.nn.functional.pad(S, (left, frames - left - S.size(3), 0, 0)), range(K))
+    zg = _recording_noise(z, noise_key, Y, frames, who, what)
+    field = VF_fn if VF_fn is not None else model
+    rows = []
+    for k0 in range(0, K, batch):
+        k1 = min(k0 + batch, K)
+        Yg = Y[k0:k1].contiguous()
+        if zg is None:
+            kw = dict(noise_keys=[noise_key] * (k1 - k0), noise_seed=noise_seed,
+                      noise_frame0=[sched.noise_frame0(k) for k in range(k0, k1)])
+        else:
+            kw = dict(z=cut(zg, range(k0, k1)).contiguous())
+        rows.append(get_white_box_solver(odesolver, model.ode, field, Y=Yg, Y_prior=Yg, **solver, **kw)()[0])
+    sample = torch.cat(rows, dim=0)
+    if fused:                      # seam rule + decompression + iSTFT + rescale: one HIP kernel
+        x_hat = synthesize(sample, norm_factor).reshape(-1)
+    else:
+        spec = torch.from_numpy(blend(sample)).to(torch.complex64).to(sample.device)
+        x_hat = (model.to_audio(spec.squeeze(), L) * norm_factor).reshape(-1)
+    return x_hat if as_tensor else x_hat.cpu().numpy()
 
 
 def enhance_long(model, y, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES, batch=8, N=5, T_rev=1.0, t_eps=0.03,
@@ -101,8 +143,8 @@ def enhance_long(model, y, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRA
     the waveform from one ``flowse_istft_decompress_chunks`` launch; nothing of the recording's length but its samples,
     the chunk rows and the waveform is held.  With ``VF_fn`` or CPU tensors the same steps run as torch ops -- stft,
     spec_fwd, index, sampler, blend (float64, rounded to complex64), spec_back, istft: the oracle composition."""
-    from flowmse_amd.evaluate import _analyze, _fused_ok, enhance_waveform
-    from flowmse_amd.sampling import get_white_box_solver
+    from flowmse_amd.evaluate import enhance_waveform
+    from flowmse_amd.schedule import OverlapSchedule
     if int(batch) < 1:
         raise ValueError(f"enhance_long: batch must be >= 1, got {batch}")
     if z is not None and noise_key is not None:
@@ -118,37 +160,12 @@ def enhance_long(model, y, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRA
         return enhance_waveform(model, y, N=N, T_rev=T_rev, t_eps=t_eps, odesolver=odesolver, z=z, VF_fn=VF_fn,
                                 device=device, noise_keys=None if noise_key is None else [noise_key],
                                 noise_seed=noise_seed, as_tensor=as_tensor)
-    norm_factor = y.abs().max().item()
-    y = y.to(device)
-    fused = _fused_ok(model, [y], VF_fn)
-    if fused:                      # the chunk rows straight from the samples: one HIP kernel, no global spectrogram
-        Y = dm.analyze_chunks(y / norm_factor, Tc, hop)
-        with torch.cuda.device(device):
-            model.dnn.reserve(batch, Y.shape[2], Tc)     # the workspace of a full group, whatever K is
-    else:
-        S = _analyze(model, y / norm_factor, False, pad=False)
-        S = torch.nn.functional.pad(S, (0, Tg - S.size(3), 0, 0))
-        Y = torch.cat([S[..., k * hop:k * hop + Tc] for k in range(K)], dim=0)
-    zg = _chunk_noise(z, noise_key, Y, Tg)
-    field = VF_fn if VF_fn is not None else model
-    rows = []
-    for k0 in range(0, K, batch):
-        k1 = min(k0 + batch, K)
-        Yg = Y[k0:k1].contiguous()
-        if zg is None:
-            kw = dict(noise_keys=[noise_key] * (k1 - k0), noise_seed=noise_seed,
-                      noise_frame0=[k * hop for k in range(k0, k1)])
-        else:
-            kw = dict(z=torch.cat([zg[..., k * hop:k * hop + Tc] for k in range(k0, k1)], dim=0).contiguous())
-        rows.append(get_white_box_solver(odesolver, model.ode, field, Y=Yg, Y_prior=Yg, T_rev=T_rev, t_eps=t_eps, N=N,
-                                         **kw)()[0])
-    sample = torch.cat(rows, dim=0)
-    if fused:                      # cross-fade + decompression + iSTFT + rescale: one HIP kernel
-        x_hat = dm.synthesize_chunks(sample, hop, L, norm_factor).reshape(-1)
-    else:
-        spec = torch.from_numpy(blend_chunks_reference(sample, hop)).to(torch.complex64).to(sample.device)
-        x_hat = (model.to_audio(spec.squeeze(), L) * norm_factor).reshape(-1)
-    return x_hat if as_tensor else x_hat.cpu().numpy()
+    return _enhance_rows(model, y, OverlapSchedule(Tc, overlap_frames), K, who="enhance_long", pad=(0, Tg),
+                         analyze=lambda yn: dm.analyze_chunks(yn, Tc, hop),
+                         synthesize=lambda s, norm: dm.synthesize_chunks(s, hop, L, norm),
+                         blend=lambda s: blend_chunks_reference(s, hop), batch=batch, odesolver=odesolver, z=z,
+                         noise_key=noise_key, noise_seed=noise_seed, VF_fn=VF_fn, device=device, as_tensor=as_tensor,
+                         T_rev=T_rev, t_eps=t_eps, N=N)
 
 
 # ---- trailing chunks: latency set by the hop, not the chunk ------------------------------------------------------------
@@ -218,19 +235,6 @@ def blend_trailing_reference(chunks, H, X):
     return out
 
 
-def _trailing_noise(z, noise_key, Y_like, Tz):
-    """``_chunk_noise`` for the trailing stream of ``Tz = P + Tg`` frames."""
-    if noise_key is not None:
-        return None
-    F = Y_like.shape[2]
-    if z is None:
-        return torch.randn_like(torch.empty(1, 1, F, Tz, dtype=torch.complex64, device=Y_like.device))
-    if tuple(z.shape) != (1, 1, F, Tz):
-        raise ValueError(f"enhance_trailing: z must be the recording's noise [1,1,{F},{Tz}] (P + Tg frames), got "
-                         f"{tuple(z.shape)}")
-    return z.to(Y_like.device)
-
-
 def enhance_trailing(model, y, chunk_frames=64, hop_frames=HOP_FRAMES, fade_frames=FADE_FRAMES, batch=8, N=5, T_rev=1.0,
                      t_eps=0.03, odesolver="euler", z=None, noise_key=None, noise_seed=0, VF_fn=None, device=None,
                      as_tensor=False):
@@ -246,8 +250,7 @@ def enhance_trailing(model, y, chunk_frames=64, hop_frames=HOP_FRAMES, fade_fram
     waveform from one ``flowse_istft_decompress_trailing`` launch.  With ``VF_fn`` or CPU tensors the same steps run as torch
     ops -- stft, spec_fwd, slice with zero frames, sampler, blend (float64, rounded to complex64), spec_back, istft: the oracle
     composition."""
-    from flowmse_amd.evaluate import _analyze, _fused_ok
-    from flowmse_amd.sampling import get_white_box_solver
+    from flowmse_amd.schedule import TrailingSchedule
     if int(batch) < 1:
         raise ValueError(f"enhance_trailing: batch must be >= 1, got {batch}")
     if z is not None and noise_key is not None:
@@ -263,33 +266,9 @@ def enhance_trailing(model, y, chunk_frames=64, hop_frames=HOP_FRAMES, fade_fram
     if P + Tg > NOISE_FRAME_MAX:
         raise ValueError(f"enhance_trailing: the noise stream is addressed up to frame {NOISE_FRAME_MAX}; this recording's "
                          f"last chunk ends at stream frame (K - 1) hop_frames + chunk_frames = {P + Tg}")
-    norm_factor = y.abs().max().item()
-    y = y.to(device)
-    fused = _fused_ok(model, [y], VF_fn)
-    if fused:                      # the rows straight from the samples: one HIP kernel, no global spectrogram
-        Y = dm.analyze_trailing(y / norm_factor, Tc, H)
-        with torch.cuda.device(device):
-            model.dnn.reserve(batch, Y.shape[2], Tc)
-    else:
-        S = _analyze(model, y / norm_factor, False, pad=False)
-        S = torch.nn.functional.pad(S, (P, Tg - S.size(3), 0, 0))          # stream frame u = t + P
-        Y = torch.cat([S[..., k * H:k * H + Tc] for k in range(K)], dim=0)
-    zg = _trailing_noise(z, noise_key, Y, P + Tg)
-    field = VF_fn if VF_fn is not None else model
-    rows = []
-    for k0 in range(0, K, batch):
-        k1 = min(k0 + batch, K)
-        Yg = Y[k0:k1].contiguous()
-        if zg is None:
-            kw = dict(noise_keys=[noise_key] * (k1 - k0), noise_seed=noise_seed, noise_frame0=[k * H for k in range(k0, k1)])
-        else:
-            kw = dict(z=torch.cat([zg[..., k * H:k * H + Tc] for k in range(k0, k1)], dim=0).contiguous())
-        rows.append(get_white_box_solver(odesolver, model.ode, field, Y=Yg, Y_prior=Yg, T_rev=T_rev, t_eps=t_eps, N=N,
-                                         **kw)()[0])
-    sample = torch.cat(rows, dim=0)
-    if fused:                      # seam rule + decompression + iSTFT + rescale: one HIP kernel
-        x_hat = dm.synthesize_trailing(sample, H, X, L, norm_factor).reshape(-1)
-    else:
-        spec = torch.from_numpy(blend_trailing_reference(sample, H, X)).to(torch.complex64).to(sample.device)
-        x_hat = (model.to_audio(spec.squeeze(), L) * norm_factor).reshape(-1)
-    return x_hat if as_tensor else x_hat.cpu().numpy()
+    return _enhance_rows(model, y, TrailingSchedule(Tc, H, X), K, who="enhance_trailing", what=" (P + Tg frames)",
+                         pad=(P, P + Tg), analyze=lambda yn: dm.analyze_trailing(yn, Tc, H),
+                         synthesize=lambda s, norm: dm.synthesize_trailing(s, H, X, L, norm),
+                         blend=lambda s: blend_trailing_reference(s, H, X), batch=batch, odesolver=odesolver, z=z,
+                         noise_key=noise_key, noise_seed=noise_seed, VF_fn=VF_fn, device=device, as_tensor=as_tensor,
+                         T_rev=T_rev, t_eps=t_eps, N=N)

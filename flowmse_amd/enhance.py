@@ -217,6 +217,23 @@ def _live_norm_arg(v):
     return f
 
 
+def _check_solver(args, ap):
+    """``--N`` and the chunk geometry.  ``--live`` and the file mode each call this where they always checked them, so that an
+    argv that breaks several rules is still told the same one first."""
+    if args.N < 1:
+        ap.error(f"--N must be >= 1, got {args.N}")
+    try:
+        plan_chunks(1, args.chunk_frames, args.overlap_frames)
+    except ValueError as e:
+        ap.error(str(e))
+
+
+def _solver_kw(args):
+    """The geometry and solver keywords that every sampler entry takes."""
+    return dict(chunk_frames=args.chunk_frames, overlap_frames=args.overlap_frames, N=args.N,
+                T_rev=args.reverse_starting_point, t_eps=args.last_eval_point, odesolver=args.odesolver)
+
+
 def _check_live(args, ap):
     """``--live`` reads one open stream: every option that names files, pools rows or draws unkeyed noise is refused."""
     for given, name in ((args.input is not None, "--input"), (args.output is not None, "--output"), (args.pool, "--pool"),
@@ -242,12 +259,7 @@ def _check_live(args, ap):
                  f"{SAMPLE_RATE} Hz only (--live_resample puts its resamplers around it)")
     if not args.synthetic and not args.ckpt:
         ap.error("--live needs --ckpt (or --synthetic 1 for synthetic weights)")
-    if args.N < 1:
-        ap.error(f"--N must be >= 1, got {args.N}")
-    try:
-        plan_chunks(1, args.chunk_frames, args.overlap_frames)
-    except ValueError as e:
-        ap.error(str(e))
+    _check_solver(args, ap)
     return args
 
 
@@ -294,12 +306,7 @@ def parse_args(argv=None, ap=None):
         ap.error("--input and --ckpt are required unless --synthetic is given")
     if args.batch < 1:
         ap.error(f"--batch must be >= 1, got {args.batch}")
-    if args.N < 1:
-        ap.error(f"--N must be >= 1, got {args.N}")
-    try:
-        plan_chunks(1, args.chunk_frames, args.overlap_frames)
-    except ValueError as e:
-        ap.error(str(e))
+    _check_solver(args, ap)
     if args.channels == "all" and not args.pool:
         ap.error("--channels all needs --pool")
     if args.samples > 1 and not args.pool:
@@ -400,10 +407,8 @@ def run_pooled(model, args, names, rates, shapes, read, seed):
         _write_wav(os.path.join(args.output, names[i]), x[0] if x.shape[0] == 1 else x.T, sr)
 
     agree = {}
-    enhance_pooled(model, load, items, write, batch=args.batch, chunk_frames=args.chunk_frames,
-                   overlap_frames=args.overlap_frames, N=args.N, T_rev=args.reverse_starting_point,
-                   t_eps=args.last_eval_point, odesolver=args.odesolver, noise_seed=seed, draws=tuple(range(args.samples)),
-                   agreement=agree.__setitem__)
+    enhance_pooled(model, load, items, write, batch=args.batch, **_solver_kw(args), noise_seed=seed,
+                   draws=tuple(range(args.samples)), agreement=agree.__setitem__)
     if args.samples > 1:
         with open(os.path.join(args.output, "_ensemble.csv"), "w", newline="") as f:
             w = csv.writer(f)
@@ -482,10 +487,9 @@ def run_live(args, ap):
         seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(8), "little")
         if args.live_channels > 1:
             return _run_live_channels(args, model, seed, stdin, stdout)
-        live = LiveEnhancer(model, norm=args.live_norm, key=utterance_key("live"), seed=seed, chunk_frames=args.chunk_frames,
-                            overlap_frames=args.overlap_frames, N=args.N, T_rev=args.reverse_starting_point,
-                            t_eps=args.last_eval_point, odesolver=args.odesolver, input_rate=args.live_rate,
-                            output_rate=args.output_rate, hop_frames=args.hop_frames, fade_frames=args.fade_frames)
+        live = LiveEnhancer(model, norm=args.live_norm, key=utterance_key("live"), seed=seed, **_solver_kw(args),
+                            input_rate=args.live_rate, output_rate=args.output_rate, hop_frames=args.hop_frames,
+                            fade_frames=args.fade_frames)
         if args.live_rate != SAMPLE_RATE:
             print(f"live: {args.live_rate} Hz in, {args.live_rate if args.output_rate == 'input' else SAMPLE_RATE} Hz out",
                   file=sys.stderr)
@@ -513,8 +517,7 @@ def _run_live_channels(args, model, seed, stdin, stdout):
     from flowmse_amd.live import latency_samples
     from flowmse_amd.livepool import LivePool
     C = args.live_channels
-    pool = LivePool(model, width=C, seed=seed, chunk_frames=args.chunk_frames, overlap_frames=args.overlap_frames, N=args.N,
-                    T_rev=args.reverse_starting_point, t_eps=args.last_eval_point, odesolver=args.odesolver)
+    pool = LivePool(model, width=C, seed=seed, **_solver_kw(args))
     if args.live_resample:                                         # frames at --live_rate in, and with --output_rate input out
         session = pool.open([channel_key("live", c) for c in range(C)], args.live_norm, input_rate=args.live_rate,
                             output_rate=args.output_rate)
@@ -594,10 +597,9 @@ def main(argv=None):
         for i, name in enumerate(names):
             y = load(i).cuda()
             x_hat, sr_out, n_frames = enhance_recording(
-                model, y, rates[i], args.output_rate, chunk_frames=args.chunk_frames, overlap_frames=args.overlap_frames,
-                batch=args.batch, N=args.N, T_rev=args.reverse_starting_point, t_eps=args.last_eval_point,
-                odesolver=args.odesolver, noise_key=utterance_key(name) if keyed else None,
-                noise_seed=seed if keyed else 0, hop_frames=args.hop_frames, fade_frames=args.fade_frames)
+                model, y, rates[i], args.output_rate, batch=args.batch, **_solver_kw(args),
+                noise_key=utterance_key(name) if keyed else None, noise_seed=seed if keyed else 0,
+                hop_frames=args.hop_frames, fade_frames=args.fade_frames)
             _write_wav(os.path.join(args.output, name), x_hat, sr_out)
             frames += n_frames
     write_settings(args.output, args, model, epoch, seed,

@@ -13,28 +13,44 @@ back one chunk; the keyed noise is addressed at absolute frames; a frame's value
 sample's value on the frames over it only.  The two window entries of the library (``flowse_stft_compress_window``,
 ``flowse_istft_decompress_window``) run the per-frame and per-sample device code of the chunk calls on what is held here.
 
-Schedule (``n_fft = 510``, ``hop_length = 128``, ``center=True``; ``hop = Tc - To`` is the chunk hop in frames).  Checked
-against the index ranges of the kernels (``stft_frame`` reads ``[128 t - 255, 128 t + 254]``, reflected at both ends;
-``istft_gather`` puts frame ``t`` over the output samples ``[128 t - 255, 128 t + 254]``):
+Schedule (``n_fft = 510``, ``hop_length = 128``, ``center=True``).  ``stft_frame`` reads ``[128 t - 255, 128 t + 254]``,
+reflected at both ends, and ``istft_gather`` puts frame ``t`` over the same output samples; so frame ``t`` is computable
+without right padding once ``128 t + 255`` samples have arrived.  ``flowmse_amd.schedule`` holds one object per geometry
+that answers five questions for chunk ``k``, and tests/test_schedule_host.py holds its answers to those index ranges:
 
-* Frame ``t`` is computable without right padding once ``128 t + 255`` samples have arrived.
-* Chunk ``k`` (frames ``[k hop, k hop + Tc)``) is ready at ``n_k = 128 (k hop + Tc - 1) + 255`` samples.  A chunk that
-  became ready this way is never the recording's last: ``L >= n_k`` gives ``L // 128 + 1 > k hop + Tc`` frames.
-* Once chunk ``k`` is sampled and is not the last, frames ``< (k + 1) hop`` are final and so are the output samples
-  ``s < E_k = 128 (k + 1) hop - 255``; the samples ``[E_{k-1}, E_k)`` (``E_{-1} = 0``) are emitted then.  They lie under
-  frames from ``k hop - 3`` on.  With ``Tc - 2 To >= 3`` those are plain frames of chunk ``k - 1``, and chunks ``k - 1`` and
-  ``k`` suffice.  With ``To = Tc / 2`` (the only other geometry ``plan_chunks`` admits: ``Tc - 2 To`` is a multiple of 4)
-  frames ``k hop - 3 .. k hop - 1`` are BLENDED frames of chunk ``k - 1``, whose other half is chunk ``k - 2``: then two
-  previous chunks are kept, and the window entry takes all three.
-* Worst algorithmic latency ``n_k - E_{k-1} = 128 Tc + 382`` samples (``latency_samples``): 2.07 s at ``Tc = 256``, 0.54 s at
-  ``Tc = 64``.  The sampler's compute time comes on top.
-* After chunk ``k`` the samples before ``128 (k + 1) hop - 256`` are dropped (clamped at 0).  One more than chunk ``k + 1``
-  reads while the recording is open: if it ends at a multiple of 128 exactly one frame past chunk ``k`` (possible at
-  ``To = 0``), that frame's right reflection reads sample ``L - 256``.
+1. Which frames does it hold, and when is it ready (``n_k``: its last frame is computable)?  A chunk that became ready this
+   way is never the recording's last: ``L >= n_k`` gives ``L // 128 + 1`` frames, more than end with chunk ``k``.
+2. Which output samples are final once it is sampled and is not the last (``s < E_k``, ``E_{-1} = 0``)?  The samples
+   ``[E_{k-1}, E_k)`` are emitted then.
+3. How much history does that range need?  It lies under frames from three before the first frame that became final.  If
+   those are plain frames of chunk ``k - 1``, chunks ``k - 1`` and ``k`` suffice; if they are BLENDED frames of chunk
+   ``k - 1``, whose other half is chunk ``k - 2``, two previous chunks are kept and the window entry takes all three.
+4. Which samples does it read, and which may go after it?  Those before ``128 f - 256`` (clamped at 0), ``f`` the first
+   frame of chunk ``k + 1``: one more than that chunk reads while the recording is open.  If the recording ends at a
+   multiple of 128 exactly one frame past chunk ``k`` (possible at ``To = 0``), that frame's right reflection reads sample
+   ``L - 256``.
+5. What is the worst algorithmic latency ``max_k (n_k - E_{k-1})`` (``latency_samples``)?  The sampler's compute time comes on top.
 
-``finish()`` fixes ``L`` (``L > 255``, as every call of the package requires) and ``K = plan_chunks(L // 128 + 1, Tc, To)[0]``,
-samples the chunks that were waiting for samples that never came -- one or two, in order, at batch width 1, now with the
-right reflection and the zero frames ``>= T`` of ``flowse_stft_compress_chunks`` -- and emits ``[E_{last emitted}, L)``.
+===================  ==========================================  ====================================================
+..                   overlap (``hop = Tc - To``; the default)    trailing (``hop_frames=H``, ``fade_frames=X``; ``P = Tc - H``)
+===================  ==========================================  ====================================================
+frames of chunk k    ``[k hop, k hop + Tc)``                     ``[k H - P, k H + H)``, those ``< 0`` zero
+keyed noise from     stream frame ``k hop``                      stream frame ``k H``
+``n_k``              ``128 (k hop + Tc - 1) + 255``              ``128 (k H + H - 1) + 255``
+``E_k``              ``128 (k + 1) hop - 255``                   ``128 ((k + 1) H - X) - 255``, clamped at 0
+two chunks kept if   ``Tc - 2 To < 3``, i.e. ``To = Tc / 2``     ``H - X < 3``: ``(8, 8)``, ``(4, 2)``, ...
+dropped after k      before ``128 (k + 1) hop - 256``            before ``128 ((k + 1) H - P) - 256``
+held before a push   the backlog                                 at most ``128 Tc + 382`` samples
+latency              ``128 Tc + 382``: 2.07 s at ``Tc = 256``,   ``128 (H + X) + 382``: 0.184 s at ``(16, 4)``,
+                     0.54 s at ``Tc = 64``                       0.104 s at ``(8, 2)``
+``K``                ``plan_chunks(T, Tc, To)[0]``               ``ceil(T / H)``; there is no ``K = 1`` case
+===================  ==========================================  ====================================================
+
+(``Tc - 2 To`` is a multiple of 4, so ``To = Tc / 2`` is the only overlap geometry with blended history.)
+
+``finish()`` fixes ``L`` (``L > 255``, as every call of the package requires) and ``K`` from ``T = L // 128 + 1``, samples the
+chunks that were waiting for samples that never came -- in order, at batch width 1, now with the right reflection and the
+zero frames ``>= T`` of ``flowse_stft_compress_chunks`` -- and emits ``[E_{last emitted}, L)``.
 
 State: the sample buffer (one linear device tensor whose capacity follows the largest push), one or two previous chunks
 (512 KB each at ``Tc = 256``) and nothing else; every push returns all it produced, so no output is ever pending.
@@ -65,25 +81,16 @@ small hop ``H`` instead; its older ``P = Tc - H`` frames are context only and on
 has the geometry and the seam rule, ``chunked.enhance_trailing`` is the file call).  **Contract:** the concatenated output
 is, bit for bit, ``enhance_trailing(model, y, chunk_frames, hop_frames, fade_frames, batch=1, noise_key=key,
 noise_seed=seed, ...)`` of the finished recording when ``norm`` equals ``max|y|``, whatever the push sizes; through the
-library's ``flowse_stft_compress_trailing_window`` and ``flowse_istft_decompress_trailing_window``.  Schedule, checked against
-the same index ranges:
+library's ``flowse_stft_compress_trailing_window`` and ``flowse_istft_decompress_trailing_window``.  The schedule is the
+table's right column:
 
-* Chunk ``k`` holds frames ``[k H - P, k H + H)`` (those ``< 0`` are zero: the first chunks are right-aligned, so the latency
-  holds from the first sample on) and is ready at ``n_k = 128 (k H + H - 1) + 255`` samples.  A chunk that became ready this
-  way is never the last: ``L >= n_k`` gives ``L // 128 + 1 > (k + 1) H`` frames, so ``K = ceil(T / H) >= k + 2``.
-* After chunk ``k`` (not the last) frames ``< (k + 1) H - X`` are final -- the ``X`` frames before ``(k + 1) H`` wait for the
-  cross-fade into chunk ``k + 1`` -- and so are the samples ``s < E_k = 128 ((k + 1) H - X) - 255``, clamped at 0; the samples
-  ``[E_{k-1}, E_k)`` are returned then.  They lie under frames from ``k H - X - 3`` on, which chunk ``k - 1`` owns
-  (``(k H - 3) // H = k - 1``); those are plain frames of it when ``H - X >= 3``, and chunk ``k - 1`` suffices as history.
-  Otherwise (``(8, 8)``, ``(4, 2)``, ...) they are faded frames whose other half is chunk ``k - 2``: two previous chunks are kept.
-* Worst algorithmic latency ``n_k - E_{k-1} = 128 (H + X) + 382`` samples: 0.184 s at ``(16, 4)``, 0.104 s at ``(8, 2)``; the
-  sampler's compute time comes on top, and it is spent ``Tc / H`` times as often (``Tc / H`` network rows per ``H`` frames).
-* After chunk ``k`` the samples before ``128 ((k + 1) H - P) - 256`` are dropped (clamped at 0): one more than the first
-  frame of chunk ``k + 1`` reads, for the same right reflection as above.  Before a push at most ``128 Tc + 382`` samples are
-  held, so the buffer is sized to that plus the largest push from the first push on.
-* ``finish()`` fixes ``L`` and ``K = ceil(T / H)``, samples the waiting chunks with the right reflection and the zero frames
-  ``>= T``, and returns ``[E_last, L)``.  There is no ``K = 1`` case: a recording shorter than one hop is one right-aligned
-  chunk.  A stream so long that ``k H + Tc`` passes ``2^31 - 2``, the last frame the keyed noise addresses, is refused by name.
+* The first chunks are right-aligned against zero frames, so the latency holds from the first sample on, and a recording
+  shorter than one hop is one right-aligned chunk.
+* After chunk ``k`` (not the last) the ``X`` frames before ``(k + 1) H`` wait for the cross-fade into chunk ``k + 1``.  What is
+  emitted lies under frames from ``k H - X - 3`` on, which chunk ``k - 1`` owns (``(k H - 3) // H = k - 1``).
+* The sampler's compute time is spent ``Tc / H`` times as often (``Tc / H`` network rows per ``H`` frames).
+* The buffer is sized to what is held before a push plus the largest push, from the first push on.
+* A stream so long that ``k H + Tc`` passes ``2^31 - 2``, the last frame the keyed noise addresses, is refused by name.
 * ``input_rate`` / ``output_rate`` work unchanged through the resamplers around this 16 kHz path, and ``latency_samples`` takes
   the worst case over ``k`` by the method above with this schedule's ``n_k`` and ``E_k``.
 
@@ -93,32 +100,14 @@ chosen by listening -- no released checkpoint is at hand -- so the defaults are 
 
 Out of scope: ``--streams`` lanes, several GPUs, time-varying or non-rational rates, noise that is not keyed, and any CPU or
 oracle path -- the oracle composition is ``enhance_long``'s, and this module is pinned to ``enhance_long``.  Rows of several
-sessions pooled into one sampler call, and several channels, are ``flowmse_amd.livepool``'s, which imports this module's
-arithmetic; a ``LiveEnhancer`` stays one mono stream at width 1.
+sessions pooled into one sampler call, and several channels, are ``flowmse_amd.livepool``'s, which asks the same
+schedule object; a ``LiveEnhancer`` stays one mono stream at width 1.
 """
 import numpy as np
 import torch
 
-from flowmse_amd.chunked import CHUNK_FRAMES, NOISE_FRAME_MAX, OVERLAP_FRAMES, plan_chunks, plan_trailing
-
-HOP, PADC = 128, 255                # hop_length and n_fft // 2 of the released STFT, the only one the kernels cover
-RATE = 16000                        # the network's sample rate
-KEEP = PADC + 1                     # samples kept before the next chunk's first frame centre (module docstring)
-
-
-def _ready_at(k, Tc, hop):
-    """``n_k``: the sample count at which chunk ``k`` is ready."""
-    return HOP * (k * hop + Tc - 1) + PADC
-
-
-def _ready_trailing(k, H):
-    """``n_k`` of the trailing schedule: chunk ``k`` ends with frame ``k H + H - 1``."""
-    return HOP * (k * H + H - 1) + PADC
-
-
-def _final_trailing(k, H, X):
-    """``E_k`` of the trailing schedule (``E_{-1} = 0``): the output samples final once chunk ``k`` is sampled."""
-    return max(HOP * ((k + 1) * H - X) - PADC, 0) if k >= 0 else 0
+from flowmse_amd.chunked import CHUNK_FRAMES, NOISE_FRAME_MAX, OVERLAP_FRAMES, plan_chunks
+from flowmse_amd.schedule import HOP, KEEP, PADC, RATE, schedule_for            # noqa: F401  (HOP .. RATE: importable from here)
 
 
 def live_plan(n_samples, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES, finished=False, hop_frames=None, fade_frames=0):
@@ -126,26 +115,7 @@ def live_plan(n_samples, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES, finished=False, hop
     ``LiveEnhancer`` has sampled and how many output samples it has returned.  ``finished``: the recording has ended at
     ``n_samples`` -- all ``K`` chunks, all samples.  Host arithmetic only; geometry errors are ``plan_chunks``'.  With
     ``hop_frames`` the trailing schedule (``To`` is not read; geometry errors are ``plan_trailing``'s)."""
-    n = int(n_samples)
-    if n < 0:
-        raise ValueError(f"live_plan: n_samples must be >= 0, got {n}")
-    if hop_frames is not None:
-        H, X = int(hop_frames), int(fade_frames)
-        plan_trailing(1, Tc, H, X)
-        if finished:
-            return plan_trailing(n // HOP + 1, Tc, H, X)[0], n
-        if n < _ready_trailing(0, H):
-            return 0, 0
-        ready = (n - _ready_trailing(0, H)) // (HOP * H) + 1
-        return ready, _final_trailing(ready - 1, H, X)
-    _, hop, _ = plan_chunks(1, Tc, To)
-    if finished:
-        return plan_chunks(n // HOP + 1, Tc, To)[0], n
-    n0 = _ready_at(0, int(Tc), hop)
-    if n < n0:
-        return 0, 0
-    ready = (n - n0) // (HOP * hop) + 1
-    return ready, HOP * ready * hop - PADC
+    return schedule_for(Tc, To, hop_frames, fade_frames, "live_plan").plan(n_samples, finished)
 
 
 PCM_FORMATS = {"s16le": 2, "f32le": 4}                    # bytes per sample
@@ -204,29 +174,70 @@ def latency_samples(Tc=CHUNK_FRAMES, input_rate=RATE, output_rate="16000", To=OV
     ``E_{k-1} input_rate div 16000`` at 16 kHz output; the value is ``max_k (A_k - R_k)``.  Both terms are floors over the
     reduced ``up`` of the input ratio, so ``k = 0 .. up`` covers every case.  With ``hop_frames`` (and ``fade_frames``) the
     trailing schedule: ``128 (H + X) + 382`` at 16 kHz, and the same method with its ``n_k`` and ``E_k`` at another rate."""
-    Tc = int(Tc)
-    trailing = hop_frames is not None
-    if trailing:
-        H, X = int(hop_frames), int(fade_frames)
-        plan_trailing(1, Tc, H, X)
-    if int(input_rate) == RATE:
-        return HOP * (H + X) + 382 if trailing else HOP * Tc + 382
-    from flowmse_amd.resample import rational, stream_plan
-    if not trailing:
-        _, hop, _ = plan_chunks(1, Tc, To)
-    up, down = rational(input_rate, RATE)
-    half = 10 * max(up, down)
-    worst = 0
-    for k in range(up + 1):
-        if trailing:
-            arrived = (half + (_ready_trailing(k, H) - 1) * down) // up + 1
-            e = _final_trailing(k - 1, H, X)
-        else:
-            arrived = (half + (_ready_at(k, Tc, hop) - 1) * down) // up + 1
-            e = HOP * k * hop - PADC if k else 0
-        returned = stream_plan(e, down, up) if output_rate == "input" else e * down // up
-        worst = max(worst, arrived - returned)
-    return worst
+    return schedule_for(Tc, To, hop_frames, fade_frames, "latency_samples").latency(input_rate, output_rate)
+
+
+def check_norm(norm, who):
+    """``norm`` of a stream: ``"first"`` or a positive finite float, refused under the caller's name ``who``."""
+    if not (norm == "first" if isinstance(norm, str) else float(norm) > 0.0 and np.isfinite(float(norm))):
+        raise ValueError(f"{who}: norm is a positive float or 'first', got {norm!r}")
+    return norm if isinstance(norm, str) else float(norm)
+
+
+def require_hip_model(model, device, who):
+    """``(device, data_module)`` of a HIP-backed ``VFModel`` on a cuda device with the released STFT, for the module ``who``;
+    anything else is a ``RuntimeError``: there is no CPU fallback."""
+    dm = getattr(model, "data_module", None)
+    if not (torch.cuda.is_available() and callable(getattr(model, "rk_sample_", None))
+            and hasattr(getattr(model, "dnn", None), "reserve")):
+        raise RuntimeError(f"{who} runs on the MI355X HIP kernels only: a HIP-backed VFModel on a 'cuda' device (there is no "
+                           "CPU fallback)")
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"{who} runs on the MI355X HIP kernels only, got device {device} (there is no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if not (hasattr(dm, "fused_ok") and dm.fused_ok(torch.empty(0, device=device))):
+        raise RuntimeError(f"{who} needs the HIP spectrogram kernels: the released STFT configuration (n_fft 510, hop 128, hann, "
+                           "'exponent')")
+    return device, dm
+
+
+class SampleBuffer:
+    """The samples ``[s0, s0 + n)`` of ``C`` channels, at the front of one ``[C, capacity]`` float32 device tensor ``data``
+    that grows once per new largest backlog and never shrinks."""
+
+    def __init__(self, channels, device):
+        self.data = torch.empty(int(channels), 0, dtype=torch.float32, device=device)
+        self.s0 = self.n = 0
+
+    capacity = property(lambda self: self.data.size(1))
+
+    def append(self, x, min_capacity=0):
+        """``x``: ``[C, m]`` (or ``[m]`` at one channel) on the device, m > 0.  A buffer that has to grow takes at least
+        ``min_capacity + m``."""
+        m = x.size(-1)
+        if self.n + m > self.capacity:                      # contents move to the front of the new tensor
+            grown = torch.empty(self.data.size(0), max(self.n, min_capacity) + m, dtype=torch.float32, device=self.data.device)
+            grown[:, :self.n] = self.data[:, :self.n]
+            self.data = grown
+        self.data[:, self.n:self.n + m] = x
+        self.n += m
+
+    def drop(self, upto):
+        """Forget the samples before ``upto``: the rest moves to the front of the same tensor."""
+        cut = min(upto, self.s0 + self.n) - self.s0
+        if cut <= 0:
+            return
+        if cut < self.n:
+            rest = self.data[:, cut:self.n].clone()
+            self.data[:, :rest.size(1)] = rest
+        self.s0 += cut
+        self.n -= cut
+
+    def view(self, lo, hi):
+        """Samples ``[lo, hi)`` of every channel, ``s0 <= lo``: a view."""
+        return self.data[:, lo - self.s0:hi - self.s0]
 
 
 class LiveEnhancer:
@@ -239,14 +250,9 @@ class LiveEnhancer:
     def __init__(self, model, *, norm, key, seed=0, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES, N=5, T_rev=1.0,
                  t_eps=0.03, odesolver="euler", device=None, input_rate=RATE, output_rate="16000", hop_frames=None,
                  fade_frames=0):
-        _, self.hop, _ = plan_chunks(1, chunk_frames, overlap_frames)
+        plan_chunks(1, chunk_frames, overlap_frames)       # checked in either geometry, and first
+        self.sched = schedule_for(chunk_frames, overlap_frames, hop_frames, fade_frames, "LiveEnhancer")
         self.Tc, self.To = int(chunk_frames), int(overlap_frames)
-        self.H = self.X = None                              # hop_frames: the trailing schedule (module docstring)
-        if hop_frames is not None:
-            plan_trailing(1, chunk_frames, hop_frames, fade_frames)
-            self.H, self.X = int(hop_frames), int(fade_frames)
-        elif fade_frames:
-            raise ValueError(f"LiveEnhancer: fade_frames={fade_frames} needs hop_frames (the trailing schedule)")
         self.input_rate = int(input_rate)
         if output_rate not in ("16000", "input"):
             raise ValueError(f"LiveEnhancer: output_rate is '16000' or 'input', got {output_rate!r}")
@@ -256,35 +262,22 @@ class LiveEnhancer:
             rational(self.input_rate, RATE)                       # an unsupported ratio is refused here, by name
         if key is None:
             raise ValueError("LiveEnhancer: key is required (keyed noise only; util.noise.utterance_key makes one)")
-        if isinstance(norm, str):
-            if norm != "first":
-                raise ValueError(f"LiveEnhancer: norm is a positive float or 'first', got {norm!r}")
-        elif not (float(norm) > 0.0 and np.isfinite(float(norm))):
-            raise ValueError(f"LiveEnhancer: norm is a positive float or 'first', got {norm!r}")
-        dm = getattr(model, "data_module", None)
-        dnn = getattr(model, "dnn", None)
-        if not (torch.cuda.is_available() and callable(getattr(model, "rk_sample_", None)) and hasattr(dnn, "reserve")):
-            raise RuntimeError("flowmse_amd.live runs on the MI355X HIP kernels only: a HIP-backed VFModel on a 'cuda' device "
-                               "(there is no CPU fallback)")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"flowmse_amd.live runs on the MI355X HIP kernels only, got device {self.device} (there is no "
-                               "CPU fallback)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if not (hasattr(dm, "fused_ok") and dm.fused_ok(torch.empty(0, device=self.device))):
-            raise RuntimeError("flowmse_amd.live needs the HIP spectrogram kernels: the released STFT configuration (n_fft 510, "
-                               "hop 128, hann, 'exponent')")
-        self.model, self._dm = model, dm
-        self._norm_arg = norm if isinstance(norm, str) else float(norm)
+        self._norm_arg = check_norm(norm, "LiveEnhancer")
+        self.device, self._dm = require_hip_model(model, device, "flowmse_amd.live")
+        self.model = model
         self._solver = dict(N=int(N), T_rev=T_rev, t_eps=t_eps)
         self._odesolver, self._seed = odesolver, int(seed)
-        self._keep_two = self.Tc - 2 * self.To < 3          # To = Tc / 2: the emitted range reaches a blended frame of chunk k-1
-        if self.H is not None:
-            self._keep_two = self.H - self.X < 3
+        self.H = self.X = None                              # hop_frames: the trailing schedule (module docstring)
+        if hop_frames is None:
+            self._stft, self._istft = self._overlap_calls(self.Tc, self.sched.hop)
+        else:
+            self.H, self.X = self.sched.H, self.sched.X
+            self._stft, self._istft = self._window_calls(
+                self.Tc, "flowse_stft_compress_trailing_window", lambda k: (k, self.Tc, self.H),
+                "flowse_istft_decompress_trailing_window", (self.Tc, self.H, self.X), self._refuse_past_noise)
         with torch.cuda.device(self.device):
-            dnn.reserve(1, 256, self.Tc)
-        self._buf = torch.empty(0, dtype=torch.float32, device=self.device)
+            model.dnn.reserve(1, 256, self.Tc)
+        self._buf = SampleBuffer(1, self.device)
         self._rs_in = self._rs_out = None                   # input_rate != 16000: the resamplers around the 16 kHz path
         if self.input_rate != RATE:
             from flowmse_amd.resample import StreamResampler
@@ -296,7 +289,7 @@ class LiveEnhancer:
     # ---- public state -----------------------------------------------------------------------------------------
     @property
     def latency_samples(self):
-        return latency_samples(self.Tc, self.input_rate, self.output_rate, self.To, self.H, self.X or 0)
+        return self.sched.latency(self.input_rate, self.output_rate)
 
     def state_bytes(self):
         """Device bytes this object holds between pushes: the sample buffer (its capacity), the previous chunks and the
@@ -304,7 +297,7 @@ class LiveEnhancer:
         (``reserve(1, 256, Tc)``)."""
         kept = [c for c in (self._prev, self._prev2) if c is not None]
         rs = sum(r.state_bytes() for r in (self._rs_in, self._rs_out) if r is not None)
-        return self._buf.numel() * 4 + sum(c.numel() * 8 for c in kept) + rs
+        return self._buf.capacity * 4 + sum(c.numel() * 8 for c in kept) + rs
 
     def reset(self, key=None):
         """Forget the recording (the buffer keeps its capacity); ``key``: the next recording's, default the same one."""
@@ -315,7 +308,7 @@ class LiveEnhancer:
         for r in (self._rs_in, self._rs_out):
             if r is not None:
                 r.reset()
-        self._s0 = self._n = 0                              # the buffer holds samples [s0, s0 + n) of the recording
+        self._buf.s0 = self._buf.n = 0                      # the buffer holds samples [s0, s0 + n) of the recording
         self._k = 0                                         # next chunk to sample
         self._prev = self._prev2 = None
         self._finished = False
@@ -334,10 +327,7 @@ class LiveEnhancer:
         self._append(samples)
         out = []
         with torch.cuda.device(self.device):
-            if self.H is not None:
-                while self._in16 >= _ready_trailing(self._k, self.H):
-                    out.append(self._chunk_trailing(self._k, None))
-            while self.H is None and self._in16 >= _ready_at(self._k, self.Tc, self.hop):
+            while self._in16 >= self.sched.ready_at(self._k):
                 out.append(self._chunk(self._k, None))
         return self._deliver(out, as_tensor)
 
@@ -356,24 +346,16 @@ class LiveEnhancer:
         if self._rs_in is not None:
             with torch.cuda.device(self.device):
                 self._append(self._rs_in.finish(as_tensor=True))
-        if self.H is not None:
-            K = plan_trailing(L // HOP + 1, self.Tc, self.H, self.X)[0]
-        else:
-            K = plan_chunks(L // HOP + 1, self.Tc, self.To)[0]
+        K, single = self.sched.chunks(L // HOP + 1), self.sched.single_width(L // HOP + 1)
         out = []
         with torch.cuda.device(self.device):
-            if self.H is not None:                          # no K = 1 case: a short recording is one right-aligned chunk
-                while self._k < K:
-                    out.append(self._chunk_trailing(self._k, L, last=self._k == K - 1))
-            elif K == 1:                                   # chunk 0 never became ready: enhance_waveform's one padded row
-                out.append(self._single(L))
-            else:
-                while self._k < K:
-                    out.append(self._chunk(self._k, L, last=self._k == K - 1))
+            if single is not None and K == 1:               # chunk 0 never became ready: enhance_waveform's one padded row
+                out.append(self._single(L, single))
+            while self._k < K:
+                out.append(self._chunk(self._k, L, last=self._k == K - 1))
         self._finished = True
         self._prev = self._prev2 = None
-        self._s0 += self._n
-        self._n = 0
+        self._buf.drop(self._buf.s0 + self._buf.n)
         return self._deliver(out, as_tensor, last=True)
 
     # ---- internals --------------------------------------------------------------------------------------------
@@ -387,29 +369,18 @@ class LiveEnhancer:
             samples = samples[0]
         if samples.dim() != 1:
             raise ValueError(f"LiveEnhancer.push takes one channel, 1-D or [1, n], got {tuple(samples.shape)}")
-        n = samples.numel()
-        if n == 0:
+        if samples.numel() == 0:
             return
-        if self._n + n > self._buf.numel():                 # grow once per new largest push; contents move to the front
-            size = self._n + n
-            if self.H is not None:                          # before a push at most n_k - 1 - (128 (k H - P) - 256) samples are held,
-                size = max(size, HOP * self.Tc + 382 + n)   # whatever k: the capacity follows the largest push from the first one on
-            grown = torch.empty(size, dtype=torch.float32, device=self.device)
-            grown[:self._n] = self._buf[:self._n]
-            self._buf = grown
-        self._buf[self._n:self._n + n] = samples.to(self.device)
-        self._n += n
-        self._in16 += n
+        self._buf.append(samples.to(self.device), self.sched.min_capacity)   # grows once per new largest push
+        self._in16 += samples.numel()
 
     def _normalised(self, lo, hi):
         """Samples [lo, hi) of the recording divided by ``norm`` as ``enhance_long`` divides them: on the device, one
         elementwise torch division by the Python float."""
         if self.norm is None:                               # norm="first": the peak of [0, n_0), or of all there is
-            n0 = _ready_at(0, self.Tc, self.hop) if self.H is None else _ready_trailing(0, self.H)
-            n0 = min(n0, self._in16)
-            peak = self._buf[:n0].abs().max().item()
+            peak = self._buf.view(0, min(self.sched.ready_at(0), self._in16))[0].abs().max().item()
             self.norm = peak if peak > 0.0 else 1.0
-        return self._buf[lo - self._s0:hi - self._s0] / self.norm
+        return self._buf.view(lo, hi)[0] / self.norm
 
     def _sample(self, Y, frame0):
         from flowmse_amd.sampling import get_white_box_solver
@@ -418,92 +389,67 @@ class LiveEnhancer:
             kw["noise_frame0"] = [frame0]
         return get_white_box_solver(self._odesolver, self.model.ode, self.model, Y=Y, Y_prior=Y, **self._solver, **kw)()[0]
 
-    def _stft(self, lo, hi, frame0, Tc, L_total):
+    def _window_calls(self, Tc, stft_entry, stft_ints, istft_entry, istft_ints, refuse=None):
+        """The two window entries of one geometry, bound to its integers: ``stft(lo, hi, k, L_total)`` -> chunk ``k``'s
+        ``[1,1,256,Tc]`` rows from the samples ``[lo, hi)``, and ``istft(prev2, prev, cur, k, last, L, e0, e1)`` -> the output
+        samples ``[e0, e1)``.  ``stft_ints(k)`` and ``istft_ints`` are what the entries take between the window and
+        ``L_total``, and between ``k`` and ``last``; ``refuse(k)`` may raise before anything is read."""
         from flowmse_amd import _lib
-        win = self._normalised(lo, hi)
-        Y = torch.empty(1, 1, 256, Tc, dtype=torch.complex64, device=self.device)
-        _lib.check(_lib.lib.flowse_stft_compress_window(_lib.ptr(win), lo, hi - lo, 1.0, frame0, Tc, L_total, _lib.ptr(Y),
-                                                        float(self._dm.spec_factor), float(self._dm.spec_abs_exponent),
-                                                        _lib.current_stream()))
-        return Y
 
-    def _istft(self, prev2, prev, cur, k, Tc, hop, last, L, e0, e1):
-        from flowmse_amd import _lib
-        out = torch.empty(e1 - e0, dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib.flowse_istft_decompress_window(_lib.ptr(prev2), _lib.ptr(prev), _lib.ptr(cur), k, Tc, hop,
-                                                           int(last), L, float(self._dm.spec_factor),
-                                                           float(self._dm.spec_abs_exponent), _lib.ptr(out), e0, e1 - e0,
-                                                           float(self.norm), _lib.current_stream()))
-        return out
+        def stft(lo, hi, k, L_total):
+            if refuse is not None:
+                refuse(k)
+            win = self._normalised(lo, hi)
+            Y = torch.empty(1, 1, 256, Tc, dtype=torch.complex64, device=self.device)
+            _lib.check(getattr(_lib.lib, stft_entry)(_lib.ptr(win), lo, hi - lo, 1.0, *stft_ints(k), L_total, _lib.ptr(Y),
+                                                     float(self._dm.spec_factor), float(self._dm.spec_abs_exponent),
+                                                     _lib.current_stream()))
+            return Y
+
+        def istft(prev2, prev, cur, k, last, L, e0, e1):
+            out = torch.empty(e1 - e0, dtype=torch.float32, device=self.device)
+            if e1 > e0:                                     # trailing: E_0 = 0 when the fade reaches back to the first frames
+                _lib.check(getattr(_lib.lib, istft_entry)(_lib.ptr(prev2), _lib.ptr(prev), _lib.ptr(cur), k, *istft_ints,
+                                                          int(last), L, float(self._dm.spec_factor),
+                                                          float(self._dm.spec_abs_exponent), _lib.ptr(out), e0, e1 - e0,
+                                                          float(self.norm), _lib.current_stream()))
+            return out
+        return stft, istft
+
+    def _overlap_calls(self, Tc, hop):
+        return self._window_calls(Tc, "flowse_stft_compress_window", lambda k: (k * hop, Tc),
+                                  "flowse_istft_decompress_window", (Tc, hop))
+
+    def _refuse_past_noise(self, k):
+        if k * self.H + self.Tc > NOISE_FRAME_MAX:
+            raise ValueError(f"LiveEnhancer: the noise stream is addressed up to frame {NOISE_FRAME_MAX}; chunk {k} ends at "
+                             f"stream frame k hop_frames + chunk_frames = {k * self.H + self.Tc}")
 
     def _chunk(self, k, L, last=False):
         """Sample chunk ``k`` (``L`` None: the recording is open) and return the samples that became final with it."""
-        Tc, hop = self.Tc, self.hop
-        lo = max(HOP * k * hop - PADC, 0)
-        hi = _ready_at(k, Tc, hop) if L is None else min(_ready_at(k, Tc, hop), L)
+        sched = self.sched
+        lo = sched.window_lo(k)
+        hi = sched.ready_at(k) if L is None else min(sched.ready_at(k), L)
         if L is not None:                                   # the right reflection may read one sample before the first frame
-            lo = max(min(lo, L - KEEP), self._s0)
-        cur = self._sample(self._stft(lo, hi, k * hop, Tc, -1 if L is None else L), k * hop)
+            lo = max(min(lo, L - KEEP), self._buf.s0)
+        cur = self._sample(self._stft(lo, hi, k, -1 if L is None else L), sched.noise_frame0(k))
         e0 = self._out16
-        e1 = L if last else HOP * (k + 1) * hop - PADC
-        out = self._istft(self._prev2, self._prev, cur, k, Tc, hop, last, L if last else 0, e0, e1)
+        e1 = L if last else sched.final_after(k)
+        out = self._istft(self._prev2, self._prev, cur, k, last, L if last else 0, e0, e1)
         self._out16 = e1
-        self._prev2, self._prev = (self._prev if self._keep_two else None), cur
+        self._prev2, self._prev = (self._prev if sched.keep_two else None), cur
         self._k = k + 1
-        self._drop(max(HOP * (k + 1) * hop - KEEP, 0))
+        self._buf.drop(sched.drop_before(k))
         return out
 
-    def _chunk_trailing(self, k, L, last=False):
-        """``_chunk`` on the trailing schedule: chunk ``k`` = frames ``[k H - P, k H + H)``, the keyed stream at ``k H``."""
-        from flowmse_amd import _lib
-        Tc, H, X = self.Tc, self.H, self.X
-        if k * H + Tc > NOISE_FRAME_MAX:
-            raise ValueError(f"LiveEnhancer: the noise stream is addressed up to frame {NOISE_FRAME_MAX}; chunk {k} ends at "
-                             f"stream frame k hop_frames + chunk_frames = {k * H + Tc}")
-        lo = max(HOP * max(k * H - (Tc - H), 0) - PADC, 0)
-        hi = _ready_trailing(k, H) if L is None else min(_ready_trailing(k, H), L)
-        if L is not None:                                   # the right reflection may read one sample before the first frame
-            lo = max(min(lo, L - KEEP), self._s0)
-        win = self._normalised(lo, hi)
-        Y = torch.empty(1, 1, 256, Tc, dtype=torch.complex64, device=self.device)
-        _lib.check(_lib.lib.flowse_stft_compress_trailing_window(_lib.ptr(win), lo, hi - lo, 1.0, k, Tc, H,
-                                                                 -1 if L is None else L, _lib.ptr(Y),
-                                                                 float(self._dm.spec_factor), float(self._dm.spec_abs_exponent),
-                                                                 _lib.current_stream()))
-        cur = self._sample(Y, k * H)
-        e0 = self._out16
-        e1 = L if last else _final_trailing(k, H, X)
-        out = torch.empty(e1 - e0, dtype=torch.float32, device=self.device)
-        if e1 > e0:                                         # E_0 = 0 when the fade reaches back to the first frames
-            _lib.check(_lib.lib.flowse_istft_decompress_trailing_window(
-                _lib.ptr(self._prev2), _lib.ptr(self._prev), _lib.ptr(cur), k, Tc, H, X, int(last), L if last else 0,
-                float(self._dm.spec_factor), float(self._dm.spec_abs_exponent), _lib.ptr(out), e0, e1 - e0, float(self.norm),
-                _lib.current_stream()))
-        self._out16 = e1
-        self._prev2, self._prev = (self._prev if self._keep_two else None), cur
-        self._k = k + 1
-        self._drop(max(HOP * ((k + 1) * H - (Tc - H)) - KEEP, 0))
-        return out
-
-    def _single(self, L):
+    def _single(self, L, Tpad):
         """K = 1: one row of ``T`` padded to a multiple of 64, the keyed stream from frame 0, every padded frame in the
         overlap-add -- ``enhance_waveform``'s computation through the window entries."""
-        Tpad = -(-(L // HOP + 1) // 64) * 64
-        cur = self._sample(self._stft(0, L, 0, Tpad, L), None)
-        out = self._istft(None, None, cur, 0, Tpad, Tpad, True, L, 0, L)
+        stft, istft = self._overlap_calls(Tpad, Tpad)
+        out = istft(None, None, self._sample(stft(0, L, 0, L), None), 0, True, L, 0, L)
         self._out16 = L
         self._k = 1
         return out
-
-    def _drop(self, upto):
-        """Forget the samples before ``upto``: the rest moves to the front of the same buffer."""
-        cut = min(upto, self._s0 + self._n) - self._s0
-        if cut <= 0:
-            return
-        rest = self._buf[cut:self._n].clone()
-        self._buf[:rest.numel()] = rest
-        self._s0 += cut
-        self._n -= cut
 
     def _deliver(self, out, as_tensor, last=False):
         if self._rs_in is None:                             # 16 kHz in and out: the caller's counters are the schedule's

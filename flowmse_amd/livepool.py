@@ -14,7 +14,7 @@ are cut and whenever ``step()`` is called.  At ``W = 1`` with one channel these 
 
 Readiness, the emitted ranges, the kept chunks and the dropping of old samples are ``live.py``'s, per session (its module
 docstring: ``n_k``, ``E_k``, the ``K == 1`` row of ``pad_spec`` width at ``finish()``, two previous chunks at ``To = Tc / 2``);
-the arithmetic is imported from there.  What is new is the schedule (``plan_step``, a host function of what the sessions
+both ask ``flowmse_amd.schedule.OverlapSchedule``.  What is new is the schedule (``plan_step``, a host function of what the sessions
 hold):
 
 * sessions come in the order they were opened; a session's rows are chunk-major, so a chunk's channels are emitted together;
@@ -65,9 +65,10 @@ import collections
 import numpy as np
 import torch
 
-from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, plan_chunks
-from flowmse_amd.live import KEEP, PADC, RATE, _ready_at, latency_samples, live_plan
+from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES
+from flowmse_amd.live import SampleBuffer, check_norm, require_hip_model
 from flowmse_amd.resample import RowsResampler, flush, out_len, rational, stream_plan
+from flowmse_amd.schedule import HOP, PADC, RATE, OverlapSchedule
 
 MAX_WIDTH = 16                      # FLOWSE_MAX_WINDOW_ROWS: the rows one window launch builds
 
@@ -107,16 +108,6 @@ def check_rates(input_rate, output_rate):
     return int(input_rate), up, down
 
 
-def check_norm(norm):
-    if isinstance(norm, str):
-        if norm != "first":
-            raise ValueError(f"LivePool.open: norm is a positive float or 'first', got {norm!r}")
-        return norm
-    if not (float(norm) > 0.0 and np.isfinite(float(norm))):
-        raise ValueError(f"LivePool.open: norm is a positive float or 'first', got {norm!r}")
-    return float(norm)
-
-
 class SessionPlan:
     """What the schedule knows of one session: host counters only (no device, no samples).  ``samples_in`` / ``samples_out``
     follow ``live.live_plan`` as a ``LiveEnhancer``'s do, with "sampled" in place of "arrived": ``samples_out`` moves when a
@@ -126,11 +117,11 @@ class SessionPlan:
 
     def __init__(self, keys, norm, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES, input_rate=RATE,
                  output_rate="16000"):
-        _, self.hop, _ = plan_chunks(1, chunk_frames, overlap_frames)
-        self.Tc, self.To = int(chunk_frames), int(overlap_frames)
+        self.sched = OverlapSchedule(chunk_frames, overlap_frames)
+        self.Tc, self.To = self.sched.Tc, self.sched.To
         self.keys = check_keys(keys)
         self.channels = len(self.keys)
-        self.norm_arg = check_norm(norm)
+        self.norm_arg = check_norm(norm, "LivePool.open")
         self.input_rate, self.up, self.down = check_rates(input_rate, output_rate)
         self.output_rate = output_rate
         self.pushed = self.samples_out = 0
@@ -145,7 +136,7 @@ class SessionPlan:
     @property
     def latency_samples(self):
         """Worst algorithmic latency in samples at ``input_rate`` (``live.latency_samples``)."""
-        return latency_samples(self.Tc, self.input_rate, self.output_rate, self.To)
+        return self.sched.latency(self.input_rate, self.output_rate)
 
     def accept(self, shape):
         """A push of ``shape`` ([C, n]; 1-D or [1, n] at one channel): counted, and ``n`` returned."""
@@ -169,24 +160,23 @@ class SessionPlan:
                              f"STFT), got {L}" + (f" at 16 kHz ({self.pushed} at {self.input_rate} Hz)" if self.up != self.down
                                                   else ""))
         self.finished, self.L = True, L
-        self.K = live_plan(self.L, self.Tc, self.To, finished=True)[0]
+        self.K = self.sched.chunks(L // HOP + 1)
 
     def pending(self):
         """``[(chunk, width)]`` that can be sampled now, in order."""
         if self.closed:
             return []
         if not self.finished:
-            return [(k, self.Tc) for k in range(self.k, live_plan(self.samples_in, self.Tc, self.To)[0])]
+            return [(k, self.Tc) for k in range(self.k, self.sched.plan(self.samples_in)[0])]
         if self.K == 1:                                     # enhance_waveform's one row, T padded to a multiple of 64
-            from flowmse_amd.pooled import file_geometry
-            return [] if self.k else [(0, file_geometry(self.L, self.Tc, self.To)[2])]
+            return [] if self.k else [(0, self.sched.single_width(self.L // HOP + 1))]
         return [(k, self.Tc) for k in range(self.k, self.K)]
 
     def final_after(self, k):
         """Output samples that are final once chunk ``k`` is sampled: ``E_k``, or ``L`` after the last chunk."""
         if self.finished and k == self.K - 1:
             return self.L
-        return live_plan(_ready_at(k, self.Tc, self.hop), self.Tc, self.To)[1]
+        return self.sched.final_after(k)
 
     def sampled(self, k):
         """Chunk ``k`` was sampled: the counters move, and a finished session whose last chunk it was is closed."""
@@ -204,7 +194,7 @@ def plan_step(plans, width):
     buckets = {}
     for i, p in enumerate(plans):
         for k, tw in p.pending():
-            buckets.setdefault(tw, []).extend(Row(i, k, c, k * p.hop, False) for c in range(p.channels))   # K == 1: k = 0
+            buckets.setdefault(tw, []).extend(Row(i, k, c, p.sched.noise_frame0(k), False) for c in range(p.channels))   # K == 1: k = 0
     calls = []
     for tw in sorted(buckets):
         rows = buckets[tw]
@@ -223,8 +213,7 @@ class LiveSession:
         self.pool = pool
         self.plan = SessionPlan(keys, norm, pool.Tc, pool.To, input_rate, output_rate)
         self.norm = None if isinstance(self.plan.norm_arg, str) else self.plan.norm_arg
-        self._buf = torch.empty(self.channels, 0, dtype=torch.float32, device=pool.device)
-        self._s0 = self._n = 0                              # the buffer holds samples [s0, s0 + n) of every channel
+        self._buf = SampleBuffer(self.channels, pool.device)  # the samples [s0, s0 + n) of every channel, divided by norm
         self._prev = [None] * self.channels                 # chunk k - 1 (and k - 2) per channel
         self._prev2 = [None] * self.channels
         self._rs_in = self._rs_out = None                   # input_rate != 16000: the resamplers around the 16 kHz path
@@ -258,7 +247,7 @@ class LiveSession:
         resamplers, if any."""
         kept = [c for c in self._prev + self._prev2 if c is not None]
         rs = sum(r.state_bytes() for r in (self._rs_in, self._rs_out) if r is not None)
-        return self._buf.numel() * 4 + sum(c.numel() * 8 for c in kept) + rs
+        return self._buf.capacity * self.channels * 4 + sum(c.numel() * 8 for c in kept) + rs
 
     def push(self, samples):
         """Append ``samples`` at ``input_rate``: float32 ``[C, n]`` (1-D or ``[1, n]`` at one channel), numpy, CPU or device
@@ -279,13 +268,7 @@ class LiveSession:
 
     def _take(self, samples):
         """``[C, n]`` samples of the 16 kHz signal on the device, n > 0: divided by ``norm`` (once it is known) into the buffer."""
-        n = samples.size(1)
-        if self._n + n > self._buf.size(1):                 # grow once per new largest backlog; contents move to the front
-            grown = torch.empty(self.channels, self._n + n, dtype=torch.float32, device=self.pool.device)
-            grown[:, :self._n] = self._buf[:, :self._n]
-            self._buf = grown
-        self._buf[:, self._n:self._n + n] = samples if self.norm is None else samples / self.norm
-        self._n += n
+        self._buf.append(samples if self.norm is None else samples / self.norm)
 
     def finish(self):
         """The stream has ended (more than 255 samples at 16 kHz, as everywhere): its remaining chunks become ready."""
@@ -304,26 +287,16 @@ class LiveSession:
         """``norm="first"``: read the peak back, once, and divide what is held (pushes divide from now on)."""
         if self.norm is not None:
             return
-        n0 = min(_ready_at(0, self.plan.Tc, self.plan.hop), self.plan.samples_in)    # nothing was dropped yet: s0 == 0
-        peak = self._buf[:, :n0].abs().max().item()
+        n0 = min(self.plan.sched.ready_at(0), self.plan.samples_in)                  # nothing was dropped yet: s0 == 0
+        peak = self._buf.view(0, n0).abs().max().item()
         self.norm = peak if peak > 0.0 else 1.0
-        self._buf[:, :self._n] = self._buf[:, :self._n] / self.norm
-
-    def _drop(self, upto):
-        cut = min(upto, self._s0 + self._n) - self._s0
-        if cut <= 0:
-            return
-        rest = self._buf[:, cut:self._n].clone()
-        self._buf[:, :rest.size(1)] = rest
-        self._s0 += cut
-        self._n -= cut
+        held = self._buf.view(0, self._buf.n)
+        held[:] = held / self.norm
 
     def _release(self):
-        self._buf = torch.empty(self.channels, 0, dtype=torch.float32, device=self.pool.device)
+        self._buf = SampleBuffer(self.channels, self.pool.device)
         self._prev = [None] * self.channels
         self._prev2 = [None] * self.channels
-        self._s0 += self._n
-        self._n = 0
         self._rs_in = self._rs_out = None
 
 
@@ -335,28 +308,14 @@ class LivePool:
     def __init__(self, model, *, width, seed=0, chunk_frames=CHUNK_FRAMES, overlap_frames=OVERLAP_FRAMES, N=5, T_rev=1.0,
                  t_eps=0.03, odesolver="euler", device=None):
         self.width = check_width(width)
-        _, self.hop, _ = plan_chunks(1, chunk_frames, overlap_frames)
-        self.Tc, self.To = int(chunk_frames), int(overlap_frames)
-        dm = getattr(model, "data_module", None)
-        dnn = getattr(model, "dnn", None)
-        if not (torch.cuda.is_available() and callable(getattr(model, "rk_sample_", None)) and hasattr(dnn, "reserve")):
-            raise RuntimeError("flowmse_amd.livepool runs on the MI355X HIP kernels only: a HIP-backed VFModel on a 'cuda' "
-                               "device (there is no CPU fallback)")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"flowmse_amd.livepool runs on the MI355X HIP kernels only, got device {self.device} (there "
-                               "is no CPU fallback)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if not (hasattr(dm, "fused_ok") and dm.fused_ok(torch.empty(0, device=self.device))):
-            raise RuntimeError("flowmse_amd.livepool needs the HIP spectrogram kernels: the released STFT configuration "
-                               "(n_fft 510, hop 128, hann, 'exponent')")
-        self.model, self._dm = model, dm
+        self.sched = OverlapSchedule(chunk_frames, overlap_frames)
+        self.Tc, self.To = self.sched.Tc, self.sched.To
+        self.device, self._dm = require_hip_model(model, device, "flowmse_amd.livepool")
+        self.model = model
         self._solver = dict(N=int(N), T_rev=T_rev, t_eps=t_eps)
         self._odesolver, self._seed = odesolver, int(seed)
-        self._keep_two = self.Tc - 2 * self.To < 3          # To = Tc / 2: the emitted range reaches a blended frame of chunk k-1
         with torch.cuda.device(self.device):
-            dnn.reserve(self.width, 256, self.Tc)
+            model.dnn.reserve(self.width, 256, self.Tc)
         self.sessions = []                                  # open sessions, in the order they were opened
         self.stats = dict(steps=0, calls=0, rows=0, fillers=0, resample_launches=0)
         self.last_step = dict(calls=0, rows=0, fillers={}, resample_launches=0)     # fillers: per bucket width
@@ -400,7 +359,7 @@ class LivePool:
                 for s, x in zip(feeds, new):
                     if x.size(1):
                         s._take(x)
-                    assert s._s0 + s._n == s.plan.samples_in
+                    assert s._buf.s0 + s._buf.n == s.plan.samples_in
             self.stats["resample_launches"] += self.last_step["resample_launches"]
         # (b) the sampler calls of everything that is ready
         calls = plan_step([s.plan for s in sessions], self.width)
@@ -428,8 +387,8 @@ class LivePool:
                 table = (_lib.flowse_window_row * W)()
                 for j, r in enumerate(call.rows):
                     s = sessions[r.session]
-                    table[j].buf = s._buf.data_ptr() + 4 * r.channel * s._buf.size(1)
-                    table[j].s0, table[j].n, table[j].frame0 = s._s0, s._n, r.frame0
+                    table[j].buf = s._buf.data.data_ptr() + 4 * r.channel * s._buf.capacity
+                    table[j].s0, table[j].n, table[j].frame0 = s._buf.s0, s._buf.n, r.frame0
                     table[j].L_total, table[j].scale_in = (s.plan.L if s.plan.finished else -1), 1.0
                 Y = torch.empty(W, 1, 256, Tw, dtype=torch.complex64, device=self.device)
                 _lib.check(_lib.lib.flowse_stft_compress_window_rows(table, W, Tw, _lib.ptr(Y), factor, exponent, stream))
@@ -451,9 +410,9 @@ class LivePool:
                     d.out = out.data_ptr() + 4 * (c * out.size(1) + e0 - s.plan.samples_out)
                     last = s.plan.finished and r.chunk == s.plan.K - 1
                     d.k, d.L, d.e0, d.n_out, d.last, d.scale_out = r.chunk, (s.plan.L if last else 0), e0, e1 - e0, int(last), s.norm
-                    s._prev2[c], s._prev[c] = (s._prev[c] if self._keep_two else None), cur
+                    s._prev2[c], s._prev[c] = (s._prev[c] if self.sched.keep_two else None), cur
                 # a K == 1 row of width Tc rides in the Tc bucket: at k = 0 with the last flag no frame reads the hop
-                hop = self.hop if Tw == self.Tc else Tw
+                hop = self.sched.hop if Tw == self.Tc else Tw
                 _lib.check(_lib.lib.flowse_istft_decompress_window_rows(ranges, len(real), Tw, hop, factor, exponent, stream))
                 del held
                 self.last_step["rows"] += len(real)
@@ -465,7 +424,7 @@ class LivePool:
                 for k, _ in s.plan.pending():
                     s.plan.sampled(k)
                 if not s.plan.closed:
-                    s._drop(max(s.plan.samples_out + PADC - KEEP, 0))
+                    s._buf.drop(self.sched.drop_before(s.plan.k - 1))
                 if s._rs_out is not None:
                     s._rs_out.append(outs[i])
                     back.append(i)

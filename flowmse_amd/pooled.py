@@ -36,6 +36,7 @@ import torch
 from flowmse_amd._lib import FLOWSE_MAX_SPEC_ROWS as MAX_BATCH    # the rows one flowse_stft_compress_rows launch builds
 from flowmse_amd.chunked import CHUNK_FRAMES, OVERLAP_FRAMES, plan_chunks
 from flowmse_amd.ensemble import agreements, check_draws, draw_keys
+from flowmse_amd.schedule import OverlapSchedule
 from flowmse_amd.util.noise import utterance_key
 
 HOP = 128                        # samples per frame the plan counts in; enhance_pooled checks the data module's against it
@@ -60,7 +61,7 @@ def file_geometry(L, Tc=CHUNK_FRAMES, To=OVERLAP_FRAMES):
     K, hop, _ = plan_chunks(T, Tc, To)
     if K > 1:
         return K, hop, int(Tc)
-    width = -(-T // 64) * 64
+    width = OverlapSchedule(Tc, To).single_width(T)
     return 1, width, width
 
 
