@@ -246,8 +246,16 @@ def gfp(t, W):
     return out.cpu()
 
 
-def conv3x3_gn(x1, gamma, beta, w, bias=None, x2=None, bias2=None, res=None, scale=1.0, silu=True, eps=1e-6):
-    """(conv3x3(act(GN(cat[x1,x2]))) + bias + bias2 + res) * scale through the fused halo kernel."""
+def staged_gn(scratch, B, HW, C):
+    """The (mean, scale) [B, C] pair (cpu) that op_gn_prologue left in an entry's scratch: floats [n - 2BC, n - BC) and
+    [n - BC, n) with n = flowse_op_group_norm_scratch_floats(B, HW, C) -- what the conv that followed normalised with."""
+    n = L.flowse_op_group_norm_scratch_floats(B, HW, C)
+    return scratch[n - 2 * B * C:n - B * C].view(B, C).cpu(), scratch[n - B * C:n].view(B, C).cpu()
+
+
+def conv3x3_gn(x1, gamma, beta, w, bias=None, x2=None, bias2=None, res=None, scale=1.0, silu=True, eps=1e-6, staged=None):
+    """(conv3x3(act(GN(cat[x1,x2]))) + bias + bias2 + res) * scale through the fused halo kernel.  staged: a list that
+    receives the (mean, scale) pair the kernel normalised with (staged_gn)."""
     Cout, Cin, k, _ = w.shape
     a1, a2, wp, bb, b2, rr = conv_operands(x1, x2, w, 9, bias, bias2, res)
     B, H, W, C1 = a1.shape
@@ -260,13 +268,15 @@ def conv3x3_gn(x1, gamma, beta, w, bias=None, x2=None, bias2=None, res=None, sca
                                       _lib.ptr(rr), _lib.ptr(out), B, H, W, Cout, float(scale), _lib.ptr(scratch),
                                       stream()))
     torch.cuda.synchronize()
+    if staged is not None:
+        staged.extend(staged_gn(scratch, B, H * W, C1 + C2))
     return nchw(out)
 
 
 def conv3x3_f43(x1, w, gamma=None, beta=None, bias=None, x2=None, bias2=None, res=None, scale=1.0, silu=True,
-                eps=1e-6, form="f43"):
-    """Same contract as conv3x3_gn (gamma None: no normalisation) through the F(4,3) Winograd kernel (form "f43") or the
-    two-dimensional F(4,3) x F(2,3) kernel (form "w2d")."""
+                eps=1e-6, form="f43", staged=None):
+    """Same contract as conv3x3_gn (gamma None: no normalisation; staged as there) through the F(4,3) Winograd kernel
+    (form "f43") or the two-dimensional F(4,3) x F(2,3) kernel (form "w2d")."""
     Cout, Cin, k, _ = w.shape
     a1, a2, wp, bb, b2, rr = conv_operands(x1, x2, w, 9, bias, bias2, res)
     B, H, W, C1 = a1.shape
@@ -281,6 +291,8 @@ def conv3x3_f43(x1, w, gamma=None, beta=None, bias=None, x2=None, bias2=None, re
                                        b2.shape[1] if b2 is not None else 0, _lib.ptr(rr), _lib.ptr(out), B, H, W, Cout,
                                        float(scale), _lib.ptr(scratch), stream()))
     torch.cuda.synchronize()
+    if staged is not None and gamma is not None:
+        staged.extend(staged_gn(scratch, B, H * W, C1 + C2))
     return nchw(out)
 
 
