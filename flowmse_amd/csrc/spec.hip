@@ -86,41 +86,73 @@ __device__ __forceinline__ void stft_frame(const float* __restrict__ sig, int64_
     *dst = make_float2(re * s, im * s);
 }
 
-// grid (Tpad, B), 256 threads = 256 bins.  Row b of the output holds frames row_frame0 * b + [0, Tpad) of signal
-// sig + row_sig * b: (row_frame0, row_sig) = (0, L) for a batch of utterances, (hop, 0) for the chunks of one recording.
-__global__ __launch_bounds__(256) void stft_compress_kernel(const float* __restrict__ sig, int L, float scale_in,
-                                                            const float* __restrict__ tab, float2* __restrict__ out,
-                                                            int T, int Tpad, float factor, float exponent,
-                                                            int row_frame0, int row_sig) {
-    const int b = blockIdx.y;
-    stft_frame(sig + (int64_t)b * row_sig, L, scale_in, tab, out + ((int64_t)b * NBIN + threadIdx.x) * Tpad + blockIdx.x,
-               b * row_frame0 + blockIdx.x, T, factor, exponent);
-}
+// One row of an STFT launch: frames frame0 + [0, Tw) of the signal of L samples and T frames of which `buf` holds the
+// samples from s0 on, under its own scale.  frame0 may be negative (the lead of the first trailing chunks); L and T are
+// INT64_MAX / 4 while a recording is open.
+struct SignalRow {
+    const float* buf;
+    int64_t s0, L, frame0, T;
+    float scale_in;
+};
 
-// The rows of ONE sampler call from up to FLOWSE_MAX_SPEC_ROWS different signals: grid (Tw, R), row r = frames
-// [frame0_r, frame0_r + Tw) of signal r under its own scale.  The table travels in the kernel's argument block (by value:
-// no allocation, no upload, nothing for the host to keep alive) and is indexed by the block's row only.
+// Where the row descriptor of block row b comes from.  Affine in b: row b = signal buf + b row_sig at frames
+// frame0 + b row_frame0 -- (row_sig, row_frame0) = (L, 0) for a batch of utterances, (0, hop) for the chunks of one
+// recording, (0, H) with frame0 = -P for its trailing chunks, one row for a window of a live session.
+struct AffineRows {
+    SignalRow row0;
+    int64_t row_sig, row_frame0;
+    __device__ __forceinline__ SignalRow operator()(int b) const {
+        SignalRow r = row0;
+        r.buf += b * row_sig;
+        r.frame0 += b * row_frame0;
+        return r;
+    }
+};
+
+// Or a table: the rows of ONE sampler call from up to FLOWSE_MAX_SPEC_ROWS different signals, or from the windows of up to
+// FLOWSE_MAX_WINDOW_ROWS live sessions (flowmse_amd.livepool; already checked and reduced on the host to what the device
+// code reads).  A table travels in the kernel's argument block (by value: no allocation, no upload, nothing for the host to
+// keep alive) and is indexed by the block's row only.  Two descriptor types, because 64 SignalRows would not fit.
 struct SpecRowTable {
     flowse_spec_row row[FLOWSE_MAX_SPEC_ROWS];
+    __device__ __forceinline__ SignalRow operator()(int r) const {
+        return SignalRow{row[r].sig, 0, row[r].L, row[r].frame0, row[r].L / HOP + 1, row[r].scale_in};
+    }
+};
+struct WindowInTable {
+    SignalRow row[FLOWSE_MAX_WINDOW_ROWS];
+    __device__ __forceinline__ SignalRow operator()(int r) const { return row[r]; }
 };
 static_assert(sizeof(flowse_spec_row) == 24 && sizeof(SpecRowTable) <= 2048, "the table must fit the argument block");
 
-__global__ __launch_bounds__(256) void stft_compress_rows_kernel(const SpecRowTable rows, const float* __restrict__ tab,
-                                                                 float2* __restrict__ out, int Tw, float factor,
-                                                                 float exponent) {
-    const int r = blockIdx.y;
-    const float* sig = rows.row[r].sig;
-    const int L = rows.row[r].L, frame0 = rows.row[r].frame0;
-    const float scale_in = rows.row[r].scale_in;
-    stft_frame(sig, L, scale_in, tab, out + ((int64_t)r * NBIN + threadIdx.x) * Tw + blockIdx.x, frame0 + blockIdx.x,
-               L / HOP + 1, factor, exponent);
+// grid (Tw, R), 256 threads = 256 bins: row r of out [R][NBIN][Tw] holds the frames of rows(r); frames < 0 or >= T are zero
+template <class Rows>
+__global__ __launch_bounds__(256) void stft_kernel(const Rows rows, const float* __restrict__ tab, float2* __restrict__ out,
+                                                   int Tw, float factor, float exponent) {
+    const SignalRow w = rows(blockIdx.y);
+    const int64_t t = w.frame0 + blockIdx.x;
+    float2* dst = out + ((int64_t)blockIdx.y * NBIN + threadIdx.x) * Tw + blockIdx.x;
+    if (t < 0) {                                        // the whole block: no barrier is skipped by part of it
+        *dst = make_float2(0.f, 0.f);
+        return;
+    }
+    stft_frame(w.buf, w.L, w.scale_in, tab, dst, t, w.T, factor, exponent, w.s0);
 }
 
-// Frame t of a recording held as K chunks [K][NBIN][Tc] that start `hop` frames apart (To = Tc - hop <= hop frames of
-// overlap, so at most two chunks cover a frame): chunk k = min(t / hop, K - 1) at j = t - k hop; in the first To frames
-// of every chunk but the first, the linear cross-fade  a + w (b - a),  w = (j + 0.5) / To,  from the previous chunk's
-// tail a to this chunk's head b -- on the compressed value, before spec_back.  `rows(k)` is chunk k's [NBIN][Tc]: StackRows
-// for a contiguous stack, WindowRows for the chunks a live session still holds.
+// ---- the seam rule.  A recording is held as K chunks [K][NBIN][Tc] whose kept parts start H frames apart: chunk k holds
+// the recording's frames [k H - P, k H + H), P = Tc - H frames of lead, counted from chunk 0's frame P.  Frame u belongs to
+// chunk k = min((u + X) / H, K - 1) at j = u - k H + P; in the X frames before k H the linear cross-fade  a + w (b - a),
+// w = (i + 0.5) / X,  i = u - (k H - X), from chunk k - 1 (a, at j + H) to chunk k (b) -- on the compressed value, before
+// spec_back.  H + X <= Tc keeps j >= 0 and j + H < Tc.  The caller counts frames from u = -shift:
+//   trailing chunks (flowmse_amd.chunked.enhance_trailing)  {Tc, H, X, 0}: frames before the recording are zero rows;
+//   overlap chunks `hop` apart, To = Tc - hop <= hop shared  {Tc, hop, To, To}: the same rule at X = P with the lead of
+//   chunk 0 counted in -- k = min(t / hop, K - 1) at j = t - k hop, the fade over j < To with w = (j + 0.5) / To.
+// u + X >= 0 in both, so the truncating division is the floor.
+struct ChunkGeom {
+    int Tc, H, X, shift;
+};
+
+// `rows(k)` is chunk k's [NBIN][Tc]: StackRows for a contiguous stack, WindowRows for the chunks a live session still holds.
 struct StackRows {
     const float2* base;
     int Tc;
@@ -128,14 +160,15 @@ struct StackRows {
 };
 
 template <class Rows>
-__device__ __forceinline__ float2 seam_frame(const Rows& rows, int f, int t, int K, int Tc, int hop) {
-    int k = t / hop;
+__device__ __forceinline__ float2 chunk_frame(const Rows& rows, int f, int t, int K, const ChunkGeom& g) {
+    const int u = t - g.shift;
+    int k = (u + g.X) / g.H;
     if (k > K - 1) k = K - 1;
-    const int j = t - k * hop, To = Tc - hop;
-    const float2 b = rows(k)[(int64_t)f * Tc + j];
-    if (k == 0 || j >= To) return b;
-    const float2 a = rows(k - 1)[(int64_t)f * Tc + j + hop];
-    const float w = ((float)j + 0.5f) / (float)To;
+    const int j = u - k * g.H + g.Tc - g.H;
+    const float2 b = rows(k)[(int64_t)f * g.Tc + j];
+    if (k == 0 || u >= k * g.H) return b;
+    const float2 a = rows(k - 1)[(int64_t)f * g.Tc + j + g.H];
+    const float w = ((float)(u - (k * g.H - g.X)) + 0.5f) / (float)g.X;
     return make_float2(a.x + w * (b.x - a.x), a.y + w * (b.y - a.y));
 }
 
@@ -160,27 +193,30 @@ struct DrawLayout {
     int64_t stack_rows, draw_rows;
 };
 
-// The linear STFT value of draw d at (f, t): the seam rule on that draw's compressed rows, then spec_back.
-template <bool SEAM>
-__device__ __forceinline__ float2 draw_value(const float2* __restrict__ spec, int b, int d, int f, int t, int Tpad,
-                                             float factor, float exponent, int K, int Tc, int hop, const DrawLayout& lay) {
-    const float2 z = SEAM ? seam_frame(StackRows{spec + (b * lay.stack_rows + d * lay.draw_rows) * NBIN * Tc, Tc}, f, t, K, Tc,
-                                       hop)
-                          : spec[((int64_t)b * NBIN + f) * Tpad + t];
-    return spec_back_value(z, factor, exponent);
+// Chunk stacks of one geometry, of lay.D draws each.  [B][NBIN][Tpad] is B stacks of one chunk: K = 1, {Tpad, Tpad, 0, 0}.
+struct Stacks {
+    const float2* spec;
+    int K;
+    ChunkGeom g;
+    float factor, exponent;
+    DrawLayout lay;
+};
+
+// The linear STFT value of draw d of stack b at (f, t): the seam rule on that draw's compressed rows, then spec_back.
+__device__ __forceinline__ float2 draw_value(const Stacks& s, int b, int d, int f, int t) {
+    const StackRows rows{s.spec + (b * s.lay.stack_rows + d * s.lay.draw_rows) * NBIN * s.g.Tc, s.g.Tc};
+    return spec_back_value(chunk_frame(rows, f, t, s.K, s.g), s.factor, s.exponent);
 }
 
 // The mean over the draws, summed in the order d = 0 .. D-1 and multiplied by 1 / D.  D == 1: the draw itself (z * 1.f).
-template <bool SEAM>
-__device__ __forceinline__ float2 mean_value(const float2* __restrict__ spec, int b, int f, int t, int Tpad, float factor,
-                                             float exponent, int K, int Tc, int hop, const DrawLayout& lay) {
-    float2 m = draw_value<SEAM>(spec, b, 0, f, t, Tpad, factor, exponent, K, Tc, hop, lay);
-    for (int d = 1; d < lay.D; ++d) {
-        const float2 z = draw_value<SEAM>(spec, b, d, f, t, Tpad, factor, exponent, K, Tc, hop, lay);
+__device__ __forceinline__ float2 mean_value(const Stacks& s, int b, int f, int t) {
+    float2 m = draw_value(s, b, 0, f, t);
+    for (int d = 1; d < s.lay.D; ++d) {
+        const float2 z = draw_value(s, b, d, f, t);
         m.x += z.x;
         m.y += z.y;
     }
-    return make_float2(m.x * lay.inv_D, m.y * lay.inv_D);
+    return make_float2(m.x * s.lay.inv_D, m.y * s.lay.inv_D);
 }
 
 // The HOP output samples [n0, n0 + 128) by one block of 256 threads: sample = tid & 127, the two halves split the bins.
@@ -245,35 +281,37 @@ __device__ __forceinline__ void istft_gather(const Frames& frames, const float* 
     }
 }
 
-// grid (ceil(Lout / 128), B), 256 threads.
-// SEAM: `spec` holds B chunk stacks as above, T == Tpad == Tg frames each, of lay.D draws each (DrawLayout; B == 1 and one
-// draw for the chunks of one recording); the frame that is transformed back is the mean of the draws' linear values.
-// else [B][NBIN][Tpad], one draw.
-template <bool SEAM>
-struct SpecFrames {
-    const float2* spec;
+// ---- frame sources of istft_gather, and what one row of an iSTFT launch stores: out[i] = sample e0 + i of the signal whose
+// frames are `frames`, for 0 <= i < n_out.  A single range is its own one-row source.
+template <class Frames>
+struct OutputRange {
+    Frames frames;
+    float* out;
+    int64_t e0, n_out;
+    float scale_out;
+    __device__ __forceinline__ const OutputRange& operator()(int) const { return *this; }
+};
+
+// Stack b of `st`, T frames: the frame that is transformed back is the mean of the draws' linear values.
+struct StackFrames {
+    Stacks st;
     int64_t T;
-    int b, Tpad, K, Tc, hop;
-    float factor, exponent;
-    DrawLayout lay;
-    __device__ __forceinline__ float2 operator()(int64_t t, int f) const {
-        return mean_value<SEAM>(spec, b, f, (int)t, Tpad, factor, exponent, K, Tc, hop, lay);
+    int b;
+    __device__ __forceinline__ float2 operator()(int64_t t, int f) const { return mean_value(st, b, f, (int)t); }
+};
+// row b = all Lout samples of stack b -> out [B][Lout]
+struct StackOutputs {
+    Stacks st;
+    int T, Lout;
+    float* out;
+    float scale_out;
+    __device__ __forceinline__ OutputRange<StackFrames> operator()(int b) const {
+        return OutputRange<StackFrames>{StackFrames{st, T, b}, out + (int64_t)b * Lout, 0, Lout, scale_out};
     }
 };
 
-template <bool SEAM>
-__global__ __launch_bounds__(256) void istft_decompress_kernel(const float2* __restrict__ spec, int T, int Tpad,
-                                                               float factor, float exponent,
-                                                               const float* __restrict__ tab, float* __restrict__ out,
-                                                               int Lout, float scale_out, int K, int Tc, int hop,
-                                                               const DrawLayout lay) {
-    const int b = blockIdx.y;
-    istft_gather(SpecFrames<SEAM>{spec, T, b, Tpad, K, Tc, hop, factor, exponent, lay}, tab, out + (int64_t)b * Lout,
-                 (int64_t)blockIdx.x * HOP, 0, Lout, scale_out);
-}
-
 // The chunks a live session holds when chunk k has been sampled: c[i] = chunk m + i of the recording, m = max(k - 2, 0),
-// as rows of a stack whose frame 0 is the recording's frame m hop.  Chunk m is read as the head of that stack -- WITHOUT
+// as rows of a stack whose frame 0 is the recording's frame m H.  Chunk m is read as the head of that stack -- WITHOUT
 // the blend into chunk m - 1 -- so the host admits only frames that do not need it: [t_lo, t_hi), checked there against
 // the seam rule.  Frames outside that range are read as zero; no sample that is stored lies under one.
 struct WindowRows {
@@ -281,106 +319,27 @@ struct WindowRows {
     __device__ __forceinline__ const float2* operator()(int k) const { return k == 0 ? c[0] : (k == 1 ? c[1] : c[2]); }
 };
 
-struct WindowFrames {
-    WindowRows rows;
+// A window of a recording: Rows = WindowRows as above, or StackRows for the K chunks of a file (base = 0, every frame
+// < T = Tg is served).
+template <class Rows>
+struct ChunkWindow {
+    Rows rows;
     int64_t T;                                          // frames >= T take no part: Tg after the last chunk, else none
-    int64_t base, t_lo, t_hi;                           // base = m hop
-    int Kw, Tc, hop;                                    // Kw: chunks of the local stack (one more while the recording is open)
+    int64_t base, t_lo, t_hi;                           // base = m H
+    int Kw;                                             // chunks of the local stack (one more while the recording is open)
+    ChunkGeom g;
     float factor, exponent;
     __device__ __forceinline__ float2 operator()(int64_t t, int f) const {
         if (t < t_lo || t >= t_hi) return make_float2(0.f, 0.f);
         // mean_value of one draw multiplies by 1.f, which is exact
-        return spec_back_value(seam_frame(rows, f, (int)(t - base), Kw, Tc, hop), factor, exponent);
+        return spec_back_value(chunk_frame(rows, f, (int)(t - base), Kw, g), factor, exponent);
     }
 };
 
-// grid (blocks of 128 samples that meet [e0, e0 + n_out)), 256 threads: out[i] = sample e0 + i of the recording
-__global__ __launch_bounds__(256) void istft_decompress_window_kernel(const WindowFrames frames,
-                                                                      const float* __restrict__ tab,
-                                                                      float* __restrict__ out, int64_t e0, int64_t n_out,
-                                                                      float scale_out) {
-    istft_gather(frames, tab, out, (e0 / HOP + blockIdx.x) * HOP, e0, e0 + n_out, scale_out);
-}
-
-// grid (Tc), 256 threads = 256 bins: frames [frame0, frame0 + Tc) of a recording of which `buf` holds the samples from s0 on
-__global__ __launch_bounds__(256) void stft_compress_window_kernel(const float* __restrict__ buf, int64_t s0, int64_t L,
-                                                                   float scale_in, const float* __restrict__ tab,
-                                                                   float2* __restrict__ out, int64_t frame0, int64_t T,
-                                                                   int Tc, float factor, float exponent) {
-    stft_frame(buf, L, scale_in, tab, out + (int64_t)threadIdx.x * Tc + blockIdx.x, frame0 + blockIdx.x, T, factor,
-               exponent, s0);
-}
-
-// ---- trailing chunks (flowmse_amd.chunked.enhance_trailing): chunk k holds the recording's frames [k H - P, k H + H),
-// P = Tc - H lead frames of context, of which only the last H (+ X of cross-fade) are kept.
-// grid (Tc, rows), 256 threads = 256 bins: row b = chunk k0 + b, frame0 = k0 H - P (negative for the first chunks: the
-// frames before the recording are zero, like those >= T).  Every other frame is stft_frame's.
-__global__ __launch_bounds__(256) void stft_compress_trailing_kernel(const float* __restrict__ buf, int64_t s0, int64_t L,
-                                                                     float scale_in, const float* __restrict__ tab,
-                                                                     float2* __restrict__ out, int64_t frame0, int H,
-                                                                     int64_t T, int Tc, float factor, float exponent) {
-    const int b = blockIdx.y;
-    const int64_t t = frame0 + (int64_t)b * H + blockIdx.x;
-    float2* dst = out + ((int64_t)b * NBIN + threadIdx.x) * Tc + blockIdx.x;
-    if (t < 0) {                                        // the whole block: no barrier is skipped by part of it
-        *dst = make_float2(0.f, 0.f);
-        return;
-    }
-    stft_frame(buf, L, scale_in, tab, dst, t, T, factor, exponent, s0);
-}
-
-// Frame t of a recording held as trailing chunks [K][NBIN][Tc] (t counted from chunk `rows(0)`'s frame P): chunk
-// k = min((t + X) / H, K - 1) at j = t - k H + P; in the X frames before k H the linear cross-fade  a + w (b - a),
-// w = (i + 0.5) / X,  i = t - (k H - X), from chunk k - 1 (a, at j + H) to chunk k (b) -- on the compressed value, before
-// spec_back.  H + X <= Tc keeps j >= 0 and j + H < Tc.
-template <class Rows>
-__device__ __forceinline__ float2 trailing_frame(const Rows& rows, int f, int t, int K, int Tc, int H, int X) {
-    int k = (t + X) / H;
-    if (k > K - 1) k = K - 1;
-    const int j = t - k * H + Tc - H;
-    const float2 b = rows(k)[(int64_t)f * Tc + j];
-    if (k == 0 || t >= k * H) return b;
-    const float2 a = rows(k - 1)[(int64_t)f * Tc + j + H];
-    const float w = ((float)(t - (k * H - X)) + 0.5f) / (float)X;
-    return make_float2(a.x + w * (b.x - a.x), a.y + w * (b.y - a.y));
-}
-
-// Rows: StackRows for the K chunks of a file (base = 0, every frame < T = Tg is served), WindowRows for the chunks a live
-// session holds (as WindowFrames: chunk m + i, base = m H, and only the frames [t_lo, t_hi) the host admitted).
-template <class Rows>
-struct TrailingFrames {
-    Rows rows;
-    int64_t T, base, t_lo, t_hi;
-    int Kw, Tc, H, X;
-    float factor, exponent;
-    __device__ __forceinline__ float2 operator()(int64_t t, int f) const {
-        if (t < t_lo || t >= t_hi) return make_float2(0.f, 0.f);
-        return spec_back_value(trailing_frame(rows, f, (int)(t - base), Kw, Tc, H, X), factor, exponent);
-    }
-};
-
-// grid (blocks of 128 samples that meet [e0, e0 + n_out)), 256 threads: out[i] = sample e0 + i of the recording
-template <class Rows>
-__global__ __launch_bounds__(256) void istft_decompress_trailing_kernel(const TrailingFrames<Rows> frames,
-                                                                        const float* __restrict__ tab,
-                                                                        float* __restrict__ out, int64_t e0, int64_t n_out,
-                                                                        float scale_out) {
-    istft_gather(frames, tab, out, (e0 / HOP + blockIdx.x) * HOP, e0, e0 + n_out, scale_out);
-}
-
-// The same two kernels for the rows of SEVERAL live sessions (flowmse_amd.livepool): the descriptors travel by value in the
-// argument block, as SpecRowTable does, already checked and reduced on the host to what the device code reads.
-struct WindowInRow {
-    const float* buf;
-    int64_t s0, L, frame0, T;                           // L, T: INT64_MAX / 4 while the recording is open
-    float scale_in;
-};
-struct WindowInTable {
-    WindowInRow row[FLOWSE_MAX_WINDOW_ROWS];
-};
+// The output ranges of SEVERAL live sessions of one geometry (flowmse_amd.livepool), by value like the tables above.
 struct WindowOutRow {
     WindowRows rows;
-    int64_t T, base, t_lo, t_hi;                        // WindowFrames' own, per row
+    int64_t T, base, t_lo, t_hi;                        // ChunkWindow's own, per row
     float* out;
     int64_t e0, n_out;
     int Kw;
@@ -388,29 +347,25 @@ struct WindowOutRow {
 };
 struct WindowOutTable {
     WindowOutRow row[FLOWSE_MAX_WINDOW_ROWS];
+    ChunkGeom g;
+    float factor, exponent;
+    __device__ __forceinline__ OutputRange<ChunkWindow<WindowRows>> operator()(int r) const {
+        const WindowOutRow& w = row[r];
+        return OutputRange<ChunkWindow<WindowRows>>{{w.rows, w.T, w.base, w.t_lo, w.t_hi, w.Kw, g, factor, exponent},
+                                                    w.out, w.e0, w.n_out, w.scale_out};
+    }
 };
-static_assert(sizeof(WindowInRow) == 48 && sizeof(WindowOutRow) == 88 && sizeof(WindowInTable) <= 2048 &&
+static_assert(sizeof(SignalRow) == 48 && sizeof(WindowOutRow) == 88 && sizeof(WindowInTable) <= 2048 &&
               sizeof(WindowOutTable) <= 2048, "the tables must fit the argument block");
 
-// grid (Tw, R), 256 threads = 256 bins: row r = frames [frame0_r, frame0_r + Tw) from the window of session r
-__global__ __launch_bounds__(256) void stft_compress_window_rows_kernel(const WindowInTable rows,
-                                                                        const float* __restrict__ tab,
-                                                                        float2* __restrict__ out, int Tw, float factor,
-                                                                        float exponent) {
-    const WindowInRow& w = rows.row[blockIdx.y];
-    stft_frame(w.buf, w.L, w.scale_in, tab, out + ((int64_t)blockIdx.y * NBIN + threadIdx.x) * Tw + blockIdx.x,
-               w.frame0 + blockIdx.x, w.T, factor, exponent, w.s0);
-}
-
-// grid (largest block count of any row, R), 256 threads: a block past its row's range returns without storing
-__global__ __launch_bounds__(256) void istft_decompress_window_rows_kernel(const WindowOutTable rows,
-                                                                           const float* __restrict__ tab, int Tc, int hop,
-                                                                           float factor, float exponent) {
-    const WindowOutRow& w = rows.row[blockIdx.y];
-    const int64_t b0 = w.e0 / HOP;
-    if ((int64_t)blockIdx.x > (w.e0 + w.n_out - 1) / HOP - b0) return;
-    const WindowFrames frames{w.rows, w.T, w.base, w.t_lo, w.t_hi, w.Kw, Tc, hop, factor, exponent};
-    istft_gather(frames, tab, w.out, (b0 + blockIdx.x) * HOP, w.e0, w.e0 + w.n_out, w.scale_out);
+// grid (blocks of 128 samples that meet the longest row's [e0, e0 + n_out), R), 256 threads: a block past its row's range
+// returns (all of it) without storing
+template <class Outputs>
+__global__ __launch_bounds__(256) void istft_kernel(const Outputs outputs, const float* __restrict__ tab) {
+    const auto r = outputs(blockIdx.y);
+    const int64_t b0 = r.e0 / HOP;
+    if ((int64_t)blockIdx.x > (r.e0 + r.n_out - 1) / HOP - b0) return;
+    istft_gather(r.frames, tab, r.out, (b0 + blockIdx.x) * HOP, r.e0, r.e0 + r.n_out, r.scale_out);
 }
 
 // Per-frame agreement tracks of an ensemble: grid (ceil(Tg / 64), S), 256 threads = 64 frames (lanes along t, the
@@ -419,19 +374,17 @@ __global__ __launch_bounds__(256) void istft_decompress_window_rows_kernel(const
 // (f, t): the mean first, the deviations from the finished mean second -- never sum |Z_d|^2 - D |M|^2, which finds a small
 // term by cancellation.  A thread sums its 64 bins in ascending order, the quarters are added in ascending order by one
 // thread: no atomics, the same bits on every call.
-__global__ __launch_bounds__(256) void ensemble_tracks_kernel(const float2* __restrict__ spec, int Tg, float factor,
-                                                              float exponent, float* __restrict__ tracks, int K, int Tc,
-                                                              int hop, const DrawLayout lay) {
+__global__ __launch_bounds__(256) void ensemble_tracks_kernel(const Stacks st, int Tg, float* __restrict__ tracks) {
     __shared__ float sdev[4][64], spow[4][64];
     const int b = blockIdx.y, lane = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int t = blockIdx.x * 64 + lane;
     float dev = 0.f, pw = 0.f;
     if (t < Tg) {
         for (int f = q * 64; f < q * 64 + 64; ++f) {
-            const float2 m = mean_value<true>(spec, b, f, t, Tg, factor, exponent, K, Tc, hop, lay);
+            const float2 m = mean_value(st, b, f, t);
             pw += m.x * m.x + m.y * m.y;
-            for (int d = 0; d < lay.D; ++d) {
-                const float2 z = draw_value<true>(spec, b, d, f, t, Tg, factor, exponent, K, Tc, hop, lay);
+            for (int d = 0; d < st.lay.D; ++d) {
+                const float2 z = draw_value(st, b, d, f, t);
                 const float ex = z.x - m.x, ey = z.y - m.y;
                 dev += ex * ex + ey * ey;
             }
@@ -444,7 +397,7 @@ __global__ __launch_bounds__(256) void ensemble_tracks_kernel(const float2* __re
         dev = ((sdev[0][lane] + sdev[1][lane]) + sdev[2][lane]) + sdev[3][lane];
         pw = ((spow[0][lane] + spow[1][lane]) + spow[2][lane]) + spow[3][lane];
         float* row = tracks + (int64_t)b * 2 * Tg;
-        row[t] = dev / (float)(lay.D - 1);
+        row[t] = dev / (float)(st.lay.D - 1);
         row[(int64_t)Tg + t] = pw;
     }
 }
@@ -452,6 +405,32 @@ __global__ __launch_bounds__(256) void ensemble_tracks_kernel(const float2* __re
 }  // namespace flowse
 
 using namespace flowse;
+
+// The tail of every entry: the tables of the current device, the launch, its check.
+template <class Rows>
+static int launch_stft(const Rows& rows, int Tw, int R, void* out_c64, float factor, float exponent, void* stream) {
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(stft_kernel<Rows>, dim3(Tw, R), dim3(256), 0, static_cast<hipStream_t>(stream), rows, tab,
+                       reinterpret_cast<float2*>(out_c64), Tw, factor, exponent);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+template <class Outputs>
+static int launch_istft(const Outputs& outputs, int64_t blocks, int R, void* stream) {
+    float* tab = nullptr;
+    int rc = ensure_tables(&tab);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(istft_kernel<Outputs>, dim3((unsigned)blocks, R), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       outputs, tab);
+    FLOWSE_LAUNCH_CHECK();
+    return OK;
+}
+
+static ChunkGeom overlap_geom(int Tc, int hop) { return ChunkGeom{Tc, hop, Tc - hop, Tc - hop}; }
+static ChunkGeom trailing_geom(int Tc, int H, int X) { return ChunkGeom{Tc, H, X, 0}; }
 
 // ================================================================================================ C ABI
 // Each entry: the null check (ERR_ARG), the shape checks (ERR_SHAPE), the launch.
@@ -464,18 +443,11 @@ int flowse_stft_compress(const float* sig, int B, int L, float scale_in, void* o
         set_error("flowse_stft_compress: null argument");
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (L <= PADC || T != L / HOP + 1 || Tpad < T || B < 1 || B > 65535) {
         set_error("stft: need L > %d, T == L / %d + 1 (got L=%d T=%d Tpad=%d B=%d)", PADC, HOP, L, T, Tpad, B);
         return ERR_SHAPE;
     }
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    hipLaunchKernelGGL(stft_compress_kernel, dim3(Tpad, B), dim3(256), 0, s, sig, L, scale_in, tab,
-                       reinterpret_cast<float2*>(out_c64), T, Tpad, factor, exponent, 0, L);
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    return launch_stft(AffineRows{{sig, 0, L, 0, T, scale_in}, L, 0}, Tpad, B, out_c64, factor, exponent, stream);
 }
 
 // geometry of a chunk stack: K chunks of Tc frames, `hop` apart, at most two over any frame
@@ -492,20 +464,13 @@ int flowse_stft_compress_chunks(const float* sig, int L, float scale_in, void* o
         set_error("flowse_stft_compress_chunks: null argument");
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const int T = L / HOP + 1;
     if (L <= PADC || !chunks_ok(K, Tc, hop) || (int64_t)(K - 1) * hop + Tc < T) {
         set_error("stft chunks: need L > %d, 1 <= hop <= Tc <= 2 hop, 1 <= K <= 65535 and (K - 1) hop + Tc >= L / %d + 1 "
                   "(got L=%d K=%d Tc=%d hop=%d)", PADC, HOP, L, K, Tc, hop);
         return ERR_SHAPE;
     }
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    hipLaunchKernelGGL(stft_compress_kernel, dim3(Tc, K), dim3(256), 0, s, sig, L, scale_in, tab,
-                       reinterpret_cast<float2*>(out_c64), T, Tc, factor, exponent, hop, 0);
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    return launch_stft(AffineRows{{sig, 0, L, 0, T, scale_in}, 0, hop}, Tc, K, out_c64, factor, exponent, stream);
 }
 
 int flowse_istft_decompress(const void* spec_c64, int B, int T, int Tpad, float factor, float exponent, float* out,
@@ -514,26 +479,20 @@ int flowse_istft_decompress(const void* spec_c64, int B, int T, int Tpad, float 
         set_error("flowse_istft_decompress: null argument");
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (T < 1 || Tpad < T || Lout < 1 || Lout > (T - 1) * HOP + NFFT - PADC || B < 1 || B > 65535 || factor == 0.f) {
         set_error("istft: bad shape T=%d Tpad=%d Lout=%d B=%d", T, Tpad, Lout, B);
         return ERR_SHAPE;
     }
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    hipLaunchKernelGGL(istft_decompress_kernel<false>, dim3((Lout + HOP - 1) / HOP, B), dim3(256), 0, s,
-                       reinterpret_cast<const float2*>(spec_c64), T, Tpad, factor, exponent, tab, out, Lout,
-                       scale_out, 0, 0, 0, DrawLayout{1, 1.f, 0, 0});
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    const Stacks st{reinterpret_cast<const float2*>(spec_c64), 1, ChunkGeom{Tpad, Tpad, 0, 0}, factor, exponent,
+                    DrawLayout{1, 1.f, 1, 0}};
+    return launch_istft(StackOutputs{st, T, Lout, out, scale_out}, (Lout + HOP - 1) / HOP, B, stream);
 }
 
 // S chunk stacks of one geometry and D draws each -> [S][Lout] (and the tracks [S][2][Tg] of the ensemble call); chunk k of
 // draw d of stack s is row s stack_rows + d draw_rows + k.  `who` names the entry in the error text
 static int launch_istft_stacks(const char* who, const float* chunks_c64, int S, int D, int K, int Tc, int hop,
                                int64_t stack_rows, int64_t draw_rows, float factor, float exponent, float* out, int Lout,
-                               float scale_out, float* tracks, hipStream_t s) {
+                               float scale_out, float* tracks, void* stream) {
     const int64_t Tg = (int64_t)(K - 1) * hop + Tc;
     if (S < 1 || S > 65535 || !chunks_ok(K, Tc, hop) || Lout < 1 || Lout > (Tg - 1) * HOP + NFFT - PADC || factor == 0.f) {
         set_error("istft %s: need 1 <= hop <= Tc <= 2 hop, 1 <= K <= 65535, 1 <= S <= 65535, 1 <= Lout <= 128 (Tg - 1) + 255 "
@@ -557,19 +516,13 @@ static int launch_istft_stacks(const char* who, const float* chunks_c64, int S, 
                   "stack_stride=%lld draw_stride=%lld)", who, S, D, K, (long long)stack_rows, (long long)draw_rows);
         return ERR_SHAPE;
     }
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    const DrawLayout lay{D, 1.f / (float)D, stack_rows, draw_rows};
-    hipLaunchKernelGGL(istft_decompress_kernel<true>, dim3((Lout + HOP - 1) / HOP, S), dim3(256), 0, s,
-                       reinterpret_cast<const float2*>(chunks_c64), (int)Tg, (int)Tg, factor, exponent, tab, out, Lout,
-                       scale_out, K, Tc, hop, lay);
+    const Stacks st{reinterpret_cast<const float2*>(chunks_c64), K, overlap_geom(Tc, hop), factor, exponent,
+                    DrawLayout{D, 1.f / (float)D, stack_rows, draw_rows}};
+    const int rc = launch_istft(StackOutputs{st, (int)Tg, Lout, out, scale_out}, (Lout + HOP - 1) / HOP, S, stream);
+    if (rc != OK || !tracks) return rc;
+    hipLaunchKernelGGL(ensemble_tracks_kernel, dim3((unsigned)((Tg + 63) / 64), S), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), st, (int)Tg, tracks);
     FLOWSE_LAUNCH_CHECK();
-    if (tracks) {
-        hipLaunchKernelGGL(ensemble_tracks_kernel, dim3((unsigned)((Tg + 63) / 64), S), dim3(256), 0, s,
-                           reinterpret_cast<const float2*>(chunks_c64), (int)Tg, factor, exponent, tracks, K, Tc, hop, lay);
-        FLOWSE_LAUNCH_CHECK();
-    }
     return OK;
 }
 
@@ -580,7 +533,7 @@ int flowse_istft_decompress_chunks(const void* chunks_c64, int K, int Tc, int ho
         return ERR_ARG;
     }
     return launch_istft_stacks("chunks", static_cast<const float*>(chunks_c64), 1, 1, K, Tc, hop, K, 0, factor, exponent, out,
-                               Lout, scale_out, nullptr, static_cast<hipStream_t>(stream));
+                               Lout, scale_out, nullptr, stream);
 }
 
 // the chunk synthesis for S stacks of one geometry in one launch: [S][K][256][Tc] -> [S][Lout]
@@ -591,7 +544,7 @@ int flowse_istft_decompress_stacks(const void* chunks_c64, int S, int K, int Tc,
         return ERR_ARG;
     }
     return launch_istft_stacks("stacks", static_cast<const float*>(chunks_c64), S, 1, K, Tc, hop, K, 0, factor, exponent, out,
-                               Lout, scale_out, nullptr, static_cast<hipStream_t>(stream));
+                               Lout, scale_out, nullptr, stream);
 }
 
 // the stack synthesis over D draws per stack: the mean of the draws' linear spectra -> [S][Lout], and (tracks != null,
@@ -604,7 +557,7 @@ int flowse_istft_decompress_ensemble(const void* chunks_c64, int S, int D, int K
         return ERR_ARG;
     }
     return launch_istft_stacks("ensemble", static_cast<const float*>(chunks_c64), S, D, K, Tc, hop, stack_stride, draw_stride,
-                               factor, exponent, out, Lout, scale_out, tracks, static_cast<hipStream_t>(stream));
+                               factor, exponent, out, Lout, scale_out, tracks, stream);
 }
 
 // the R rows [R,1,256,Tw] of one sampler call from up to FLOWSE_MAX_SPEC_ROWS signals; `rows`: HOST table
@@ -614,7 +567,6 @@ int flowse_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, void* 
         set_error("flowse_stft_compress_rows: null argument");
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (R < 1 || R > FLOWSE_MAX_SPEC_ROWS || Tw < 1 || Tw > (1 << 23)) {
         set_error("stft rows: need 1 <= R <= %d and 1 <= Tw <= 2^23 (got R=%d Tw=%d)", FLOWSE_MAX_SPEC_ROWS, R, Tw);
         return ERR_SHAPE;
@@ -633,13 +585,7 @@ int flowse_stft_compress_rows(const flowse_spec_row* rows, int R, int Tw, void* 
             return ERR_SHAPE;
         }
     }
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    hipLaunchKernelGGL(stft_compress_rows_kernel, dim3(Tw, R), dim3(256), 0, s, t, tab, reinterpret_cast<float2*>(out_c64),
-                       Tw, factor, exponent);
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    return launch_stft(t, Tw, R, out_c64, factor, exponent, stream);
 }
 
 // ---- windows of a recording that is still arriving (flowmse_amd.live) -------------------------------------------------
@@ -692,31 +638,20 @@ int flowse_stft_compress_window(const float* buf, int64_t s0, int64_t n, float s
         set_error("flowse_stft_compress_window: null argument");
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     int64_t T = 0;
-    int rc = check_stft_window("stft window", s0, n, frame0, Tc, L_total, &T);
+    const int rc = check_stft_window("stft window", s0, n, frame0, Tc, L_total, &T);
     if (rc != OK) return rc;
-    float* tab = nullptr;
-    rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    hipLaunchKernelGGL(stft_compress_window_kernel, dim3(Tc), dim3(256), 0, s, buf, s0, L_total >= 0 ? L_total : INT64_MAX / 4,
-                       scale_in, tab, reinterpret_cast<float2*>(out_c64), frame0, T, Tc, factor, exponent);
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    return launch_stft(AffineRows{{buf, s0, L_total >= 0 ? L_total : INT64_MAX / 4, frame0, T, scale_in}, 0, 0}, Tc, 1, out_c64,
+                       factor, exponent, stream);
 }
 
-// The shape checks of one output range, shared likewise; on success *fr is what the kernel reads for it.
-static int check_istft_window(const char* who, const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k,
-                              int Tc, int hop, int last, int64_t L, float factor, float exponent, int64_t e0, int64_t n_out,
-                              WindowFrames* fr) {
-    if (k < 0 || k > WINDOW_MAX || Tc < 1 || Tc > (1 << 23) || hop < 1 || hop > Tc || 2 * (int64_t)hop < Tc || e0 < 0 ||
-        n_out < 1 || n_out > ((int64_t)1 << 30) || e0 > WINDOW_MAX * HOP || factor == 0.f) {
-        set_error("%s: need 0 <= k <= 2^40, 1 <= hop <= Tc <= 2 hop, Tc <= 2^23, e0 >= 0, 1 <= n_out <= 2^30 and "
-                  "factor != 0 (got k=%lld Tc=%d hop=%d e0=%lld n_out=%lld)", who, (long long)k, Tc, hop, (long long)e0,
-                  (long long)n_out);
-        return ERR_SHAPE;
-    }
-    const int64_t Tg = k * hop + Tc, To = Tc - hop;
+// The shape checks of one output range [e0, e0 + n_out) after chunk k, past the entry's own argument checks, for either
+// geometry; on success *fr is what the kernel reads for it.  `who` names the entry (and the row); `open_note` ends the error text
+// while the recording is open: the first frame that waits for chunk k + 1, in the entry's own symbols.
+static int check_istft_window(const char* who, const char* open_note, const void* prev2_c64, const void* prev_c64,
+                              const void* cur_c64, int64_t k, const ChunkGeom& g, int last, int64_t L, float factor,
+                              float exponent, int64_t e0, int64_t n_out, ChunkWindow<WindowRows>* fr) {
+    const int64_t Tg = (k + 1) * g.H + g.shift;         // frames of a recording that ends with chunk k
     if (last && (e0 + n_out > L || L > (Tg - 1) * HOP + NFFT - PADC)) {
         set_error("%s: after the last chunk need e0 + n_out <= L <= 128 (Tg - 1) + 255 (got e0=%lld n_out=%lld "
                   "L=%lld Tg=%lld)", who, (long long)e0, (long long)n_out, (long long)L, (long long)Tg);
@@ -726,17 +661,18 @@ static int check_istft_window(const char* who, const void* prev2_c64, const void
     const int64_t t_first = e0 <= NFFT - 1 - PADC ? 0 : (e0 - (NFFT - 1 - PADC) + HOP - 1) / HOP;
     int64_t t_last = (e0 + n_out - 1 + PADC) / HOP;
     if (last && t_last > Tg - 1) t_last = Tg - 1;
-    // the chunks the seam rule reads for them
-    const int64_t c_hi = last && t_last / hop > k ? k : t_last / hop;
-    int64_t c_lo = last && t_first / hop > k ? k : t_first / hop;
-    if (c_lo > 0 && t_first - c_lo * hop < To) c_lo -= 1;
+    // the chunks the seam rule reads for them: the owner of a frame, and the chunk before it inside the fade; both grow with t
+    int64_t c_hi = (t_last - g.shift + g.X) / g.H, c_lo = (t_first - g.shift + g.X) / g.H;
+    if (last && c_hi > k) c_hi = k;
+    if (last && c_lo > k) c_lo = k;
+    if (c_lo > 0 && t_first - g.shift < c_lo * g.H) c_lo -= 1;
     const int64_t m = k >= 2 ? k - 2 : 0;
     if (c_hi > k || c_lo < m || (c_lo <= k - 1 && !prev_c64) || (c_lo <= k - 2 && !prev2_c64)) {
         set_error("%s: samples [%lld, %lld) lie under frames [%lld, %lld], which the seam rule takes from chunks "
-                  "%lld..%lld; given are chunk k=%lld%s%s%s", who, (long long)e0, (long long)(e0 + n_out), (long long)t_first,
-                  (long long)t_last, (long long)c_lo, (long long)c_hi, (long long)k,
+                  "%lld..%lld; given are chunk k=%lld%s%s%s", who, (long long)e0, (long long)(e0 + n_out),
+                  (long long)t_first, (long long)t_last, (long long)c_lo, (long long)c_hi, (long long)k,
                   (k >= 1 && prev_c64) ? ", k-1" : "", (k >= 2 && prev2_c64) ? ", k-2" : "",
-                  last ? " (the last)" : " (not the last: frames from (k+1) hop on wait for chunk k+1)");
+                  last ? " (the last)" : open_note);
         return ERR_SHAPE;
     }
     const float2* given[3] = {reinterpret_cast<const float2*>(prev2_c64), reinterpret_cast<const float2*>(prev_c64),
@@ -744,15 +680,29 @@ static int check_istft_window(const char* who, const void* prev2_c64, const void
     const int held = (int)(k - m) + 1;                  // chunks m .. k
     for (int i = 0; i < 3; ++i) fr->rows.c[i] = i < held ? given[3 - held + i] : nullptr;
     fr->T = last ? Tg : INT64_MAX / 4;
-    fr->base = m * hop;
+    fr->base = m * g.H;
     fr->t_lo = t_first;
     fr->t_hi = t_last + 1;
     fr->Kw = held + (last ? 0 : 1);
-    fr->Tc = Tc;
-    fr->hop = hop;
+    fr->g = g;
     fr->factor = factor;
     fr->exponent = exponent;
     return OK;
+}
+
+// the overlap entries' own argument checks, then the above
+static int check_overlap_window(const char* who, const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k,
+                                int Tc, int hop, int last, int64_t L, float factor, float exponent, int64_t e0, int64_t n_out,
+                                ChunkWindow<WindowRows>* fr) {
+    if (k < 0 || k > WINDOW_MAX || Tc < 1 || Tc > (1 << 23) || hop < 1 || hop > Tc || 2 * (int64_t)hop < Tc || e0 < 0 ||
+        n_out < 1 || n_out > ((int64_t)1 << 30) || e0 > WINDOW_MAX * HOP || factor == 0.f) {
+        set_error("%s: need 0 <= k <= 2^40, 1 <= hop <= Tc <= 2 hop, Tc <= 2^23, e0 >= 0, 1 <= n_out <= 2^30 and "
+                  "factor != 0 (got k=%lld Tc=%d hop=%d e0=%lld n_out=%lld)", who, (long long)k, Tc, hop, (long long)e0,
+                  (long long)n_out);
+        return ERR_SHAPE;
+    }
+    return check_istft_window(who, " (not the last: frames from (k+1) hop on wait for chunk k+1)", prev2_c64, prev_c64, cur_c64,
+                              k, overlap_geom(Tc, hop), last, L, factor, exponent, e0, n_out, fr);
 }
 
 int flowse_istft_decompress_window(const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k, int Tc,
@@ -762,19 +712,11 @@ int flowse_istft_decompress_window(const void* prev2_c64, const void* prev_c64, 
         set_error("flowse_istft_decompress_window: null argument");
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    WindowFrames fr;
-    int rc = check_istft_window("istft window", prev2_c64, prev_c64, cur_c64, k, Tc, hop, last, L, factor, exponent, e0, n_out,
-                                &fr);
+    OutputRange<ChunkWindow<WindowRows>> range{{}, out, e0, n_out, scale_out};
+    const int rc = check_overlap_window("istft window", prev2_c64, prev_c64, cur_c64, k, Tc, hop, last, L, factor, exponent, e0,
+                                        n_out, &range.frames);
     if (rc != OK) return rc;
-    float* tab = nullptr;
-    rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    const int64_t blocks = (e0 + n_out - 1) / HOP - e0 / HOP + 1;
-    hipLaunchKernelGGL(istft_decompress_window_kernel, dim3((unsigned)blocks), dim3(256), 0, s, fr, tab, out, e0, n_out,
-                       scale_out);
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    return launch_istft(range, (e0 + n_out - 1) / HOP - e0 / HOP + 1, 1, stream);
 }
 
 // ---- trailing chunks: the file pair and the window pair (flowmse_amd.chunked.enhance_trailing, flowmse_amd.live) -----------
@@ -791,20 +733,14 @@ int flowse_stft_compress_trailing(const float* sig, int L, float scale_in, void*
         set_error("flowse_stft_compress_trailing: null argument");
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const int T = L / HOP + 1;
     if (L <= PADC || !trailing_ok(Tc, H, -1) || K < 1 || K > 65535 || (int64_t)K * H < T || (int64_t)K * H + Tc > (1 << 23)) {
         set_error("flowse_stft_compress_trailing: need L > %d, " TRAILING_GEOMETRY ", 1 <= K <= 65535 and L / %d + 1 <= K H <= "
                   "2^23 - Tc (got L=%d K=%d Tc=%d H=%d)", PADC, HOP, L, K, Tc, H);
         return ERR_SHAPE;
     }
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    hipLaunchKernelGGL(stft_compress_trailing_kernel, dim3(Tc, K), dim3(256), 0, s, sig, (int64_t)0, (int64_t)L, scale_in, tab,
-                       reinterpret_cast<float2*>(out_c64), (int64_t)H - Tc, H, (int64_t)T, Tc, factor, exponent);
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    // row b = chunk b, from frame b H - P on
+    return launch_stft(AffineRows{{sig, 0, L, (int64_t)H - Tc, T, scale_in}, 0, H}, Tc, K, out_c64, factor, exponent, stream);
 }
 
 int flowse_istft_decompress_trailing(const void* chunks_c64, int K, int Tc, int H, int X, float factor, float exponent,
@@ -813,7 +749,6 @@ int flowse_istft_decompress_trailing(const void* chunks_c64, int K, int Tc, int 
         set_error("flowse_istft_decompress_trailing: null argument");
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t Tg = (int64_t)K * H;
     if (!trailing_ok(Tc, H, X) || X < 0 || K < 1 || K > 65535 || Tg + Tc > (1 << 23) || Lout < 1 ||
         Lout > (Tg - 1) * HOP + NFFT - PADC || factor == 0.f) {
@@ -822,15 +757,9 @@ int flowse_istft_decompress_trailing(const void* chunks_c64, int K, int Tc, int 
                   H, X, Lout);
         return ERR_SHAPE;
     }
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    const TrailingFrames<StackRows> fr{StackRows{reinterpret_cast<const float2*>(chunks_c64), Tc}, Tg, 0, 0, Tg, K, Tc, H, X,
-                                       factor, exponent};
-    hipLaunchKernelGGL(istft_decompress_trailing_kernel<StackRows>, dim3((Lout + HOP - 1) / HOP), dim3(256), 0, s, fr, tab, out,
-                       (int64_t)0, (int64_t)Lout, scale_out);
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    const ChunkWindow<StackRows> frames{StackRows{reinterpret_cast<const float2*>(chunks_c64), Tc}, Tg, 0, 0, Tg, K,
+                                        trailing_geom(Tc, H, X), factor, exponent};
+    return launch_istft(OutputRange<ChunkWindow<StackRows>>{frames, out, 0, Lout, scale_out}, (Lout + HOP - 1) / HOP, 1, stream);
 }
 
 int flowse_stft_compress_trailing_window(const float* buf, int64_t s0, int64_t n, float scale_in, int64_t k, int Tc, int H,
@@ -839,7 +768,6 @@ int flowse_stft_compress_trailing_window(const float* buf, int64_t s0, int64_t n
         set_error("flowse_stft_compress_trailing_window: null argument");
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (!trailing_ok(Tc, H, -1) || k < 0 || k > WINDOW_MAX / H - 1) {
         set_error("flowse_stft_compress_trailing_window: need " TRAILING_GEOMETRY " and 0 <= k, (k + 1) H <= 2^40 (got k=%lld "
                   "Tc=%d H=%d)", (long long)k, Tc, H);
@@ -848,16 +776,10 @@ int flowse_stft_compress_trailing_window(const float* buf, int64_t s0, int64_t n
     // the frames that read samples start at max(k H - P, 0): the checks of the plain window over those
     const int64_t frame0 = k * H - (Tc - H), first = frame0 < 0 ? 0 : frame0;
     int64_t T = 0;
-    int rc = check_stft_window("flowse_stft_compress_trailing_window", s0, n, first, (int)(frame0 + Tc - first), L_total, &T);
+    const int rc = check_stft_window("flowse_stft_compress_trailing_window", s0, n, first, (int)(frame0 + Tc - first), L_total, &T);
     if (rc != OK) return rc;
-    float* tab = nullptr;
-    rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    hipLaunchKernelGGL(stft_compress_trailing_kernel, dim3(Tc, 1), dim3(256), 0, s, buf, s0,
-                       L_total >= 0 ? L_total : INT64_MAX / 4, scale_in, tab, reinterpret_cast<float2*>(out_c64), frame0, H, T, Tc,
-                       factor, exponent);
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    return launch_stft(AffineRows{{buf, s0, L_total >= 0 ? L_total : INT64_MAX / 4, frame0, T, scale_in}, 0, 0}, Tc, 1, out_c64,
+                       factor, exponent, stream);
 }
 
 int flowse_istft_decompress_trailing_window(const void* prev2_c64, const void* prev_c64, const void* cur_c64, int64_t k, int Tc,
@@ -868,7 +790,6 @@ int flowse_istft_decompress_trailing_window(const void* prev2_c64, const void* p
         set_error("%s: null argument", who);
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (!trailing_ok(Tc, H, X) || X < 0 || k < 0 || k > WINDOW_MAX / H - 1 || e0 < 0 || n_out < 1 ||
         n_out > ((int64_t)1 << 30) || e0 > WINDOW_MAX * HOP || factor == 0.f) {
         set_error("%s: need " TRAILING_GEOMETRY ", 0 <= X <= H, H + X <= Tc, 0 <= k, (k + 1) H <= 2^40, e0 >= 0, 1 <= n_out <= "
@@ -876,53 +797,11 @@ int flowse_istft_decompress_trailing_window(const void* prev2_c64, const void* p
                   (long long)e0, (long long)n_out);
         return ERR_SHAPE;
     }
-    const int64_t Tg = (k + 1) * H;
-    if (last && (e0 + n_out > L || L > (Tg - 1) * HOP + NFFT - PADC)) {
-        set_error("%s: after the last chunk need e0 + n_out <= L <= 128 (Tg - 1) + 255 (got e0=%lld n_out=%lld L=%lld "
-                  "Tg=%lld)", who, (long long)e0, (long long)n_out, (long long)L, (long long)Tg);
-        return ERR_SHAPE;
-    }
-    // the frames over the samples [e0, e0 + n_out): the index range of istft_gather for one sample, over all of them
-    const int64_t t_first = e0 <= NFFT - 1 - PADC ? 0 : (e0 - (NFFT - 1 - PADC) + HOP - 1) / HOP;
-    int64_t t_last = (e0 + n_out - 1 + PADC) / HOP;
-    if (last && t_last > Tg - 1) t_last = Tg - 1;
-    // the chunks the seam rule reads for them: the owner of a frame, and the chunk before it inside the fade; both grow with t
-    int64_t c_hi = (t_last + X) / H, c_lo = (t_first + X) / H;
-    if (last && c_hi > k) c_hi = k;
-    if (last && c_lo > k) c_lo = k;
-    if (c_lo > 0 && t_first < c_lo * H) c_lo -= 1;
-    const int64_t m = k >= 2 ? k - 2 : 0;
-    if (c_hi > k || c_lo < m || (c_lo <= k - 1 && !prev_c64) || (c_lo <= k - 2 && !prev2_c64)) {
-        set_error("%s: samples [%lld, %lld) lie under frames [%lld, %lld], which the seam rule takes from chunks %lld..%lld; "
-                  "given are chunk k=%lld%s%s%s", who, (long long)e0, (long long)(e0 + n_out), (long long)t_first,
-                  (long long)t_last, (long long)c_lo, (long long)c_hi, (long long)k, (k >= 1 && prev_c64) ? ", k-1" : "",
-                  (k >= 2 && prev2_c64) ? ", k-2" : "",
-                  last ? " (the last)" : " (not the last: frames from (k+1) H - X on wait for chunk k+1)");
-        return ERR_SHAPE;
-    }
-    const float2* given[3] = {reinterpret_cast<const float2*>(prev2_c64), reinterpret_cast<const float2*>(prev_c64),
-                              reinterpret_cast<const float2*>(cur_c64)};
-    const int held = (int)(k - m) + 1;                  // chunks m .. k
-    TrailingFrames<WindowRows> fr;
-    for (int i = 0; i < 3; ++i) fr.rows.c[i] = i < held ? given[3 - held + i] : nullptr;
-    fr.T = last ? Tg : INT64_MAX / 4;
-    fr.base = m * H;
-    fr.t_lo = t_first;
-    fr.t_hi = t_last + 1;
-    fr.Kw = held + (last ? 0 : 1);
-    fr.Tc = Tc;
-    fr.H = H;
-    fr.X = X;
-    fr.factor = factor;
-    fr.exponent = exponent;
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
+    OutputRange<ChunkWindow<WindowRows>> range{{}, out, e0, n_out, scale_out};
+    const int rc = check_istft_window(who, " (not the last: frames from (k+1) H - X on wait for chunk k+1)", prev2_c64, prev_c64,
+                                      cur_c64, k, trailing_geom(Tc, H, X), last, L, factor, exponent, e0, n_out, &range.frames);
     if (rc != OK) return rc;
-    const int64_t blocks = (e0 + n_out - 1) / HOP - e0 / HOP + 1;
-    hipLaunchKernelGGL(istft_decompress_trailing_kernel<WindowRows>, dim3((unsigned)blocks), dim3(256), 0, s, fr, tab, out, e0,
-                       n_out, scale_out);
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    return launch_istft(range, (e0 + n_out - 1) / HOP - e0 / HOP + 1, 1, stream);
 }
 
 // ---- the windows of several sessions in one launch each (flowmse_amd.livepool); `rows`: HOST tables ---------------------
@@ -932,7 +811,6 @@ int flowse_stft_compress_window_rows(const flowse_window_row* rows, int R, int T
         set_error("flowse_stft_compress_window_rows: null argument");
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (R < 1 || R > FLOWSE_MAX_WINDOW_ROWS) {
         set_error("stft window rows: need 1 <= R <= %d (got R=%d)", FLOWSE_MAX_WINDOW_ROWS, R);
         return ERR_SHAPE;
@@ -953,15 +831,9 @@ int flowse_stft_compress_window_rows(const flowse_window_row* rows, int R, int T
         int64_t T = 0;
         const int rc = check_stft_window(who, w.s0, w.n, w.frame0, Tw, w.L_total, &T);
         if (rc != OK) return rc;
-        t.row[r] = WindowInRow{w.buf, w.s0, w.L_total >= 0 ? w.L_total : INT64_MAX / 4, w.frame0, T, w.scale_in};
+        t.row[r] = SignalRow{w.buf, w.s0, w.L_total >= 0 ? w.L_total : INT64_MAX / 4, w.frame0, T, w.scale_in};
     }
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    hipLaunchKernelGGL(stft_compress_window_rows_kernel, dim3(Tw, R), dim3(256), 0, s, t, tab,
-                       reinterpret_cast<float2*>(out_c64), Tw, factor, exponent);
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    return launch_stft(t, Tw, R, out_c64, factor, exponent, stream);
 }
 
 int flowse_istft_decompress_window_rows(const flowse_window_out* rows, int R, int Tc, int hop, float factor, float exponent,
@@ -970,7 +842,6 @@ int flowse_istft_decompress_window_rows(const flowse_window_out* rows, int R, in
         set_error("flowse_istft_decompress_window_rows: null argument");
         return ERR_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (R < 1 || R > FLOWSE_MAX_WINDOW_ROWS) {
         set_error("istft window rows: need 1 <= R <= %d (got R=%d)", FLOWSE_MAX_WINDOW_ROWS, R);
         return ERR_SHAPE;
@@ -989,21 +860,18 @@ int flowse_istft_decompress_window_rows(const flowse_window_out* rows, int R, in
             return ERR_ARG;
         }
         snprintf(who, sizeof(who), "istft window rows: row %d", r);
-        WindowFrames fr;
-        const int rc = check_istft_window(who, w.prev2_c64, w.prev_c64, w.cur_c64, w.k, Tc, hop, w.last, w.L, factor, exponent,
-                                          w.e0, w.n_out, &fr);
+        ChunkWindow<WindowRows> fr;
+        const int rc = check_overlap_window(who, w.prev2_c64, w.prev_c64, w.cur_c64, w.k, Tc, hop, w.last, w.L, factor, exponent,
+                                            w.e0, w.n_out, &fr);
         if (rc != OK) return rc;
         t.row[r] = WindowOutRow{fr.rows, fr.T, fr.base, fr.t_lo, fr.t_hi, w.out, w.e0, w.n_out, fr.Kw, w.scale_out};
         const int64_t b = (w.e0 + w.n_out - 1) / HOP - w.e0 / HOP + 1;
         if (b > blocks) blocks = b;
     }
-    float* tab = nullptr;
-    int rc = ensure_tables(&tab);
-    if (rc != OK) return rc;
-    hipLaunchKernelGGL(istft_decompress_window_rows_kernel, dim3((unsigned)blocks, R), dim3(256), 0, s, t, tab, Tc, hop, factor,
-                       exponent);
-    FLOWSE_LAUNCH_CHECK();
-    return OK;
+    t.g = overlap_geom(Tc, hop);
+    t.factor = factor;
+    t.exponent = exponent;
+    return launch_istft(t, blocks, R, stream);
 }
 
 }  // extern "C"

@@ -111,6 +111,34 @@ def test_chunks_cut_from_one_spectrogram_synthesize_bit_for_bit(dm, H, X):
     assert float(want.abs().max()) > 0
 
 
+@pytest.mark.parametrize("hop,To", [(48, 16), (32, 32), (64, 0)], ids=lambda v: str(v))
+def test_the_overlap_synthesis_is_the_trailing_synthesis_bit_for_bit(hop, To):
+    """Overlap chunks ``hop`` apart are trailing chunks at H = hop, X = P = To whose frame origin lies To frames later: on
+    independent random chunks, trailing sample n is overlap sample n + 128 To.  From n = 256 on: below that, the overlap
+    stack's first To frames -- which the trailing recording does not have -- lie over the sample or in its block."""
+    s, p = _lib.current_stream(), _lib.ptr
+    K = 3
+    chunks = C.c64(synth.synth_spectrogram(60 + hop, K, 256, TC)).cuda()
+    over = torch.empty(128 * ((K - 1) * hop + TC - 1), device="cuda")
+    trail = torch.empty(128 * (K * hop - 1), device="cuda")
+    _lib.check(L.flowse_istft_decompress_chunks(p(chunks), K, TC, hop, FACTOR, EXPONENT, p(over), over.numel(), 0.7, s))
+    _lib.check(L.flowse_istft_decompress_trailing(p(chunks), K, TC, hop, To, FACTOR, EXPONENT, p(trail), trail.numel(), 0.7, s))
+    torch.cuda.synchronize()
+    assert over.numel() == trail.numel() + 128 * To
+    got, want = trail[256:], over[256 + 128 * To:]
+    assert got.numel() > 0 and float(want.abs().max()) > 0
+    assert torch.equal(got, want), (hop, To, int((got != want).nonzero()[0]))
+
+
+def test_the_overlap_rows_are_trailing_rows(dm):
+    """97 frames at Tc = 64, hop = H = 32: overlap chunk k holds the frames [32 k, 32 k + 64) that trailing chunk k + 1 holds."""
+    sig = _signal(3, 128 * 96 + 127).cuda()
+    over, trail = dm.analyze_chunks(sig, TC, 32, 0.37), dm.analyze_trailing(sig, TC, 32, 0.37)
+    torch.cuda.synchronize()
+    assert over.shape == (3, 1, 256, TC) and trail.shape == (4, 1, 256, TC)
+    assert torch.equal(over, trail[1:]) and float(over[2].abs().max()) > 0
+
+
 # ---------------------------------------------------------------------------------------------------- 3
 def test_refusals_return_a_status_name_the_entry_and_launch_nothing():
     s, p = _lib.current_stream(), _lib.ptr

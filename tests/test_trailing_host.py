@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from flowmse_amd import enhance
-from flowmse_amd.chunked import blend_trailing_reference, plan_chunks, plan_trailing
+from flowmse_amd.chunked import blend_chunks_reference, blend_trailing_reference, plan_chunks, plan_trailing
 from flowmse_amd.live import latency_samples, live_plan
 from flowmse_amd.util import synth
 
@@ -61,6 +61,20 @@ def test_blend_returns_a_spectrogram_cut_into_chunks_exactly(H, X):
         assert np.array_equal(out[0, 0, :, t], want), t
     with pytest.raises(ValueError):
         blend_trailing_reference(c, H, H + 1)
+
+
+def test_the_overlap_blend_is_the_trailing_blend_with_the_fade_over_the_whole_lead():
+    """Chunks ``hop`` apart that share To = Tc - hop frames are trailing chunks at H = hop, X = P = To, counted from To frames
+    later: the two float64 statements of the seam rule agree exactly on independent random chunks, and the To frames before
+    the trailing origin are chunk 0's."""
+    Tc, K, F = 64, 3, 8
+    for To in range(0, 33, 2):
+        hop = Tc - To
+        c = synth.synth_spectrogram(70 + To, K, F, Tc).astype(np.complex128)
+        over, trail = blend_chunks_reference(c, hop), blend_trailing_reference(c, hop, To)
+        assert over.shape == (1, 1, F, (K - 1) * hop + Tc) and trail.shape == (1, 1, F, K * hop)
+        assert np.array_equal(over[..., To:], trail), To
+        assert np.array_equal(over[..., :To], c[:1, :, :, :To]) and np.abs(trail).max() > 0
 
 
 @pytest.mark.parametrize("H,X", GEOMETRIES[:4], ids=lambda v: str(v))
